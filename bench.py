@@ -2,8 +2,17 @@
 """Benchmark: verified GB/s of SHA-1 piece verification, HBM-resident (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg4|suppl|p262k] [--weak|--strong]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what `value` needs and no more: it sets the timed workload up, warms up, times the K steps, writes
+the outputs when --dump-outputs is given, and prints the result line.  --full adds everything else described below
+(the creation-mode hash check of the timed workload, the legs beside `value`, the CPU baseline).
+--dump-outputs DIR writes what the last timed step returned to its caller, as float32 .npy files: bitfield.npy (one
+0 / 1 value per piece of the rank's shard, in piece order) and bitfield_bytes.npy (the tv_verify bitfield bytes as they
+came back, one value per byte); at N > 1 every rank writes its shard's as <name>.rank<r>.npy.  The payload, the
+digests and the corrupted pieces are functions of the arguments alone, so two builds can be compared file for file.
 
 `value` (the timed workload): BASELINE configs[1] = cfg2, a 16 GiB synthetic single-file torrent in 16,384 pieces
 of 1 MiB, HBM-resident on one MI355X; at N > 1 weak-scaled (the pieces are independent units, sharded with no
@@ -15,9 +24,10 @@ so the driver's 1 -> 8 curve is one configuration.  `--workload cfg4 --strong` t
 
 Expected values are the CPU ORACLE's (oracle/sha1_oracle.c, pinned by the reference's own test_data
 digests): the rank's whole shard is hashed on the host's cores before the timed region and 1 % of the
-digests are corrupted, so `bitfield_exact` means "equal, on every piece, to the oracle's bitfield".
+digests are corrupted, so `bitfield_exact` means "equal, on every piece, to the oracle's bitfield" (with --full
+also: the creation-mode hash of the whole shard, tv_hash, equals the oracle's digests).
 
-Legs reported beside `value` (never as it):
+Legs reported beside `value` (never as it), with --full:
   * cfg4: BASELINE configs[3], ONE 200 GiB torrent in 51,200 pieces of 4 MiB, strong-scaled: rank r verifies
     the contiguous 8-aligned shard shard_ranges(51200, N)[r] (the bitfield slices are whole bytes and
     concatenate); at N = 1 the whole torrent on one GPU.  Piece-bound past one GPU.
@@ -263,9 +273,12 @@ def _traffic(workload: str, bytes_per_launch: int) -> tuple:
 
 
 def resident_leg(dist, ws: int, rank: int, device: int, workload: str, strong: bool, steps: int, warmup: int,
-                 kernel_opt: int, threads: int, want_digests: bool = False) -> dict:
+                 kernel_opt: int, threads: int, want_digests: bool = False, check_creation: bool = True,
+                 want_bitfield: bool = False) -> dict:
     """One resident workload on every rank: synthetic payload filled in HBM by the device generator, oracle
-    digests with 1 % corrupted, W + K timed verify steps.  Every rank runs it (barriers inside)."""
+    digests with 1 % corrupted, W + K timed verify steps.  Every rank runs it (barriers inside).
+    check_creation: also hash the whole shard in creation mode and compare with the oracle's digests, before the
+    warmup.  want_bitfield: return the last timed step's bitfield as `_bitfield`."""
     L, n, seed, desc = WORKLOADS[workload]
     if strong:
         P = n
@@ -288,7 +301,8 @@ def resident_leg(dist, ws: int, rank: int, device: int, workload: str, strong: b
             raise RuntimeError(f"{workload}: the shard does not fit the device budget "
                                f"({ctx.counter(_native.TV_COUNTER_BUDGET)} B); the resident bench needs it whole")
         ctx.fill_synthetic(seed)
-        creation_exact = ctx.hash() == dig            # creation mode (make_torrent.ts:28-31) at full size
+        # creation mode (make_torrent.ts:28-31) at full size
+        creation_exact = ctx.hash() == dig if check_creation else True
         d2 = bytearray(dig)
         bad = _corrupt(d2, count, seed)
         pieces = bytearray(20 * P)
@@ -367,7 +381,21 @@ def resident_leg(dist, ws: int, rank: int, device: int, workload: str, strong: b
     if want_digests:
         out["_digests"] = dig
         out["_first"] = first
+    if want_bitfield:
+        out["_bitfield"] = bytes(bf)
     return out
+
+
+def dump_outputs(path: str, bitfield: bytes, count: int, rank: int, ws: int) -> None:
+    """--dump-outputs: the bitfield the last timed tv_verify handed back for this rank's `count` pieces, as float32
+    arrays: `bitfield` one 0 / 1 value per piece (MSB-first within a byte, as the library packs them), `bitfield_bytes`
+    the returned bytes themselves."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    raw = np.frombuffer(bitfield, dtype=np.uint8)
+    suffix = f".rank{rank}" if ws > 1 else ""
+    np.save(os.path.join(path, f"bitfield{suffix}.npy"), np.unpackbits(raw)[:count].astype(np.float32))
+    np.save(os.path.join(path, f"bitfield_bytes{suffix}.npy"), raw.astype(np.float32))
 
 
 def producer_rate(ctx, seed: int, seconds: float = 1.0) -> float:
@@ -677,6 +705,11 @@ def main() -> int:
     ap.add_argument("--no-cfg3", action="store_true", help="skip the cfg3 multi-file leg (N=1)")
     ap.add_argument("--e2e-steps", type=int, default=1, help="timed e2e_cfg5 passes (0 = skip the leg)")
     ap.add_argument("--leg-steps", type=int, default=5, help="timed steps of the cfg4 / suppl legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what a plain run leaves out: the creation-mode hash check, the cfg4 / e2e_cfg5 / "
+                         "cfg3 / piece_saturated legs and the CPU baseline (each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's bitfield to DIR as float32 .npy files")
     a = ap.parse_args()
 
     dist, rank, ws, local = _dist()
@@ -696,32 +729,35 @@ def main() -> int:
     strong = a.strong
 
     main_leg = resident_leg(dist, ws, rank, device, workload, strong, a.steps, a.warmup, a.kernel, threads,
-                            want_digests=(workload == "cfg4" and strong))
+                            want_digests=(workload == "cfg4" and strong), check_creation=a.full, want_bitfield=True)
+    last_bitfield = main_leg.pop("_bitfield")
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, last_bitfield, main_leg["pieces_per_gpu"], rank, ws)
     legs = {}
     cfg4_digests = None
     if workload == "cfg4" and strong:
         cfg4_digests = main_leg.pop("_digests")
         main_leg.pop("_first")
-    elif not a.no_cfg4:
+    elif a.full and not a.no_cfg4:
         legs["cfg4"] = resident_leg(dist, ws, rank, device, "cfg4", True, a.leg_steps, 1, a.kernel, threads,
                                     want_digests=True)
         cfg4_digests = legs["cfg4"].pop("_digests")
         legs["cfg4"].pop("_first")
-    if a.e2e_steps > 0:
+    if a.full and a.e2e_steps > 0:
         try:
             legs["e2e_cfg5"] = e2e_cfg5(dist, ws, rank, device, a.e2e_steps, threads, cfg4_digests, share,
                                         physical)
         except Exception as exc:  # reported, never fatal to the bench line
             legs["e2e_cfg5"] = {"skipped": f"{type(exc).__name__}: {exc}"}
     cfg4_digests = None
-    if ws == 1 and workload == "cfg2" and not a.no_cfg3:
+    if a.full and ws == 1 and workload == "cfg2" and not a.no_cfg3:
         try:
             # (3 ms launches: 20 warm-up steps bring the shader clock up from the layout build's idle, and 20 timed
             # steps average over its last ramp; rocprofv3 showed 5 timed steps still speeding up in round 5)
             legs["cfg3"] = cfg3_leg(device, max(20, a.leg_steps), 20, a.kernel)
         except Exception as exc:
             legs["cfg3"] = {"skipped": f"{type(exc).__name__}: {exc}"}
-    if ws == 1 and workload == "cfg2" and not a.no_saturating:
+    if a.full and ws == 1 and workload == "cfg2" and not a.no_saturating:
         try:
             legs["piece_saturated"] = resident_leg(dist, 1, 0, device, "suppl", False, a.leg_steps, 1, a.kernel, threads)
         except Exception as exc:
@@ -782,7 +818,7 @@ def main() -> int:
             + ("(each GPU verifies its own 16 GiB / 16,384-piece shard of an N x 16 GiB torrent, no collective), "
                if workload == "cfg2" and not strong else "")
             + "so the driver's per-N curve of value is one configuration; BASELINE configs[3] -- ONE 200 GiB torrent "
-              "of 51,200 x 4 MiB pieces sharded over the N GPUs -- is the cfg4 leg at every N: read the sharded "
+              "of 51,200 x 4 MiB pieces sharded over the N GPUs -- is the cfg4 leg (--full) at every N: read the sharded "
               "curve from cfg4.value against cfg4.aggregate_piece_ceiling (piece-bound past one GPU, "
               f"predicted {round(aggregate_piece_ceiling('cfg4', ws), 1)} GB/s at N = {ws})")
         if "cfg4" in legs and "value" in legs["cfg4"]:
@@ -793,7 +829,7 @@ def main() -> int:
                                      "predicted_aggregate_piece_ceiling":
                                          round(aggregate_piece_ceiling("cfg4", ws), 1)}
         out.update(legs)
-        if ws == 1 and not a.no_cpu_baseline:
+        if a.full and ws == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(share, a.cpu_seconds)
         out["placement"] = {"ranks": placement, "physical_gpus": physical, "visible_devices": ndev,
                             "rule": "device = LOCAL_RANK % (devices visible to the rank): LOCAL_RANK on a node "

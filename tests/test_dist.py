@@ -90,12 +90,13 @@ def test_device_placement_rule():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("scaling", ["strong", "weak"])
-def test_bench_two_ranks_on_the_hip_path(scaling):
+def test_bench_two_ranks_on_the_hip_path(scaling, tmp_path):
     """The N>1 path itself, on one GPU: `torch.distributed.run --nproc-per-node 2 bench.py` (gloo barriers,
     max-over-ranks time), each rank verifying its shard of one torrent through the HIP library against the
     oracle's digests -- strong-scaled (the torrent's pieces split over the ranks) and weak-scaled (each rank its
     own whole-size shard of an N-times larger torrent, the default `value`); rank 0 prints one valid JSON line
-    with an exact bitfield."""
+    with an exact bitfield, and --dump-outputs leaves each rank's last bitfield (float32, one value per piece:
+    0 on the 1 % of pieces whose digests the bench corrupts, 1 elsewhere)."""
     import json
     import subprocess
     import sys
@@ -103,7 +104,7 @@ def test_bench_two_ranks_on_the_hip_path(scaling):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
            "--workload", "tiny", "--" + scaling, "--steps", "3", "--warmup", "1", "--no-cfg4", "--e2e-steps", "0",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -115,6 +116,34 @@ def test_bench_two_ranks_on_the_hip_path(scaling):
         assert rec["config"]["total_pieces"] == 1000 and rec["config"]["pieces_per_gpu"] == 504
     else:
         assert rec["config"]["total_pieces"] == 2000 and rec["config"]["pieces_per_gpu"] == 1000
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+    import numpy as np
+    counts = [504, 496] if scaling == "strong" else [1000, 1000]
+    for rank, count in enumerate(counts):
+        bits = np.load(tmp_path / f"bitfield.rank{rank}.npy")
+        assert bits.dtype == np.float32 and bits.shape == (count,)
+        bad = set(range(9, count, 100)) | {count - 1}      # bench._corrupt with the tiny workload's seed 9
+        assert set(np.flatnonzero(bits == 0).tolist()) == bad and set(np.unique(bits).tolist()) == {0.0, 1.0}
+        raw = np.load(tmp_path / f"bitfield_bytes.rank{rank}.npy")
+        assert raw.dtype == np.float32 and raw.shape == ((count + 7) // 8,)
+        assert np.array_equal(np.unpackbits(raw.astype(np.uint8))[:count], bits.astype(np.uint8))
+
+
+def test_bench_dump_outputs_layout(tmp_path):
+    """bench.dump_outputs: the bitfield bytes of one verify become `bitfield.npy` (float32, one 0 / 1 value per piece,
+    most significant bit first, the padding bits of the last byte left out) and `bitfield_bytes.npy` (float32, one
+    value per byte); at N > 1 the names carry the rank.  Writing twice gives the same bytes."""
+    import bench
+    import numpy as np
+    bf = bytes([0b10110000, 0b01000000])
+    bench.dump_outputs(str(tmp_path / "a"), bf, 11, 0, 1)
+    bits = np.load(tmp_path / "a" / "bitfield.npy")
+    assert bits.dtype == np.float32 and bits.tolist() == [1, 0, 1, 1, 0, 0, 0, 0, 0, 1, 0]
+    raw = np.load(tmp_path / "a" / "bitfield_bytes.npy")
+    assert raw.dtype == np.float32 and raw.tolist() == [176.0, 64.0]
+    bench.dump_outputs(str(tmp_path / "b"), bf, 11, 1, 2)
+    assert sorted(os.listdir(tmp_path / "b")) == ["bitfield.rank1.npy", "bitfield_bytes.rank1.npy"]
+    assert (tmp_path / "b" / "bitfield.rank1.npy").read_bytes() == (tmp_path / "a" / "bitfield.npy").read_bytes()
 
 
 def test_aggregate_piece_ceiling_follows_the_shards():

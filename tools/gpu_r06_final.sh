@@ -10,9 +10,9 @@ out=gpurun_out/${CHECK_OUT:-r06_final}
 mkdir -p $out
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 240 --timeout-method thread > $out/pytest_gpu.log 2>&1 && echo TESTS_OK &&
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 && echo SMOKE_OK &&
-timeout -k 10 300 python3 bench.py > $out/bench_n1.json 2> $out/bench_n1.err && echo BENCH_OK &&
+timeout -k 10 300 python3 bench.py --full > $out/bench_n1.json 2> $out/bench_n1.err && echo BENCH_OK &&
 CHECK_OUT=${CHECK_OUT:-r06_final}/pmc bash tools/gpu_r05_pmc.sh > $out/pmc.log 2>&1 && echo PMC_OK &&
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/prof -o run -- python3 bench.py --steps 10 --warmup 3 \
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/prof -o run -- python3 bench.py --full --steps 10 --warmup 3 \
     > $out/bench_prof.json 2> $out/bench_prof.err && echo PROF_OK &&
 bash tools/rehearse_ranks.sh $out/rehearse ${REHEARSE_N:-2 8} && echo REHEARSE_OK
 rc=$?

@@ -11,7 +11,7 @@ for n in "$@"; do
     port=$((29500 + n))
     SECONDS=0
     timeout -k 10 600 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" \
-        --master-addr 127.0.0.1 --master-port "$port" bench.py --gpus "$n" --steps 10 --warmup 3 \
+        --master-addr 127.0.0.1 --master-port "$port" bench.py --gpus "$n" --full --steps 10 --warmup 3 \
         > "$out/bench_n${n}_ranks_one_gpu.json" 2> "$out/bench_n${n}_ranks_one_gpu.stderr.log"
     rc=$?
     echo "{\"n\": $n, \"rc\": $rc, \"wall_s\": $SECONDS}" | tee -a "$out/rehearsal_wall.jsonl"
