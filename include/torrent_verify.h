@@ -256,6 +256,46 @@ int tv_stream_file_table(tv_ctx *ctx, uint64_t n, const uint64_t *lengths, const
 int tv_hash(tv_ctx *ctx, uint8_t *digests_out);
 
 /*
+ * BitTorrent v2 (BEP 52) pieces: SHA-256 merkle roots over 16 KiB blocks.  The reference knows v1 torrents only
+ * (metainfo.ts:12-44 has no `file tree`); these calls verify and create the format current clients write by default.
+ *
+ * In a v2 torrent every file starts a new piece, so the layout set by tv_set_layout is the ALIGNED linear space:
+ * piece p at linear offset p * piece_length, pieces numbered in file-tree order as if pad files aligned every file
+ * (a zero-length file has no piece).  tv_stage*, tv_read and tv_fill_synthetic work on that space unchanged; the
+ * host stages each file at its aligned offset.  piece_length must be a power of two >= TV_V2_LEAF_BYTES.
+ *
+ * tv_v2_set_pieces gives the piece table of the layout: n == the layout's n_pieces entries, GLOBAL (the ctx takes
+ * its shard from them, as tv_set_digests does).
+ *   piece_bytes[p] : valid bytes of piece p, 1 .. piece_length (a file's last piece may be short; bytes past it are
+ *                    never read into a hash)
+ *   tree_leaves[p] : width of piece p's merkle tree in leaves: a power of two >= ceil(piece_bytes[p] / 16 KiB) and
+ *                    <= piece_length / 16 KiB.  A piece of a file longer than one piece has the full width
+ *                    (its `piece layers` entry is the root of a whole piece subtree, the missing leaves zero hashes);
+ *                    a file of <= piece_length bytes is one piece whose tree is only as wide as its leaves need, and
+ *                    whose root is the file's `pieces root`.  The width cannot be derived from the length: the host
+ *                    passes it.
+ *   hashes         : 32 * n bytes, the expected root of every piece (`piece layers` entries, or `pieces root` for a
+ *                    one-piece file); NULL = creation mode (tv_v2_hash only).
+ * A leaf (16 KiB block, the last of a file 1 .. 16,384 bytes, not padded) hashes to SHA-256 of its bytes; a leaf
+ * position past the piece's bytes is 32 zero bytes; an interior node is SHA-256(left || right).
+ * TV_ERR_ARG: piece_length not a power of two or < 16 KiB, n != n_pieces, a piece_bytes / tree_leaves entry outside
+ * the ranges above.  TV_ERR_STATE: before tv_set_layout, on a windowed layout or a slot pool (v2 needs the shard
+ * resident), during a stream; tv_v2_verify / tv_v2_hash without a piece table (tv_v2_verify: without hashes).
+ * tv_set_layout drops the table.
+ *
+ * tv_v2_verify: as tv_verify -- bit j = piece shard_first + j is readable (avail_bits, and not marked unreadable by
+ * tv_stage_file(s)) AND its merkle root equals hashes[32 j'..], j' its global index.  tv_v2_hash: the 32-byte root of
+ * every resident piece, in piece order (creation mode: a file's `piece layers` entry, or its `pieces root` when it
+ * is one piece; the host reduces a longer file's layer to its `pieces root`).  tv_last_timing, tv_last_kernel
+ * (kernel id 8) and TV_COUNTER_LAST_WORKGROUPS (the leaf kernel's grid) report on them.
+ */
+#define TV_V2_LEAF_BYTES 16384
+int tv_v2_set_pieces(tv_ctx *ctx, uint64_t n, const uint32_t *piece_bytes, const uint32_t *tree_leaves,
+                     const uint8_t *hashes);
+int tv_v2_verify(tv_ctx *ctx, const uint8_t *avail_bits, uint8_t *bitfield_out);
+int tv_v2_hash(tv_ctx *ctx, uint8_t *roots_out);
+
+/*
  * Streamed verify through a BOUNDED pinned ring (end-to-end resume check, SURVEY 8d cfg5: the
  * resume flow Client.add -> Storage -> bitfield -> sendBitfield, client.ts:53-67, torrent.ts:56-60,101).
  * No resident payload and no whole-shard host buffer are needed: the library hands out requests in the
@@ -366,7 +406,7 @@ int tv_get_option(tv_ctx *ctx, int key, int64_t *value);
  * library's compute stream: kernel_ms = the verify kernel(s) only; total_ms = whole call. */
 int tv_last_timing(tv_ctx *ctx, double *kernel_ms, double *total_ms);
 
-/* Kernel chosen for the last call (1 lane, 2 split, 4 twin) and launches it used. */
+/* Kernel chosen for the last call (1 lane, 2 split, 4 twin; 8 = the v2 SHA-256 merkle kernels) and launches it used. */
 int tv_last_kernel(tv_ctx *ctx, int *kernel, int *launches);
 
 /* Resource counters of a ctx (tv_get_counter keys): how often tv_set_layout and the calls after it had to

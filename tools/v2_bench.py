@@ -1,0 +1,152 @@
+"""BitTorrent v2 throughput on one GPU: tv_v2_verify (SHA-256 merkle piece roots) on the cfg2 shape (one 16 GiB file,
+1 MiB pieces) and on cfg4's piece geometry (4 MiB pieces, as many as fit), with three comparisons in the same run:
+tv_verify (SHA-1) on the same resident bytes, hashlib SHA-256 on this host's cores, and the A/B of the leaf kernel's
+lane mappings (TV_OPT_V2_MAP), alternated step by step.
+
+    python tools/v2_bench.py [--steps 10] [--warmup 3] [--out profiles/v2/v2_bench.json]
+
+Times are the library's HIP events around the kernels (tv_last_timing); the shader clock is the clock probe's
+(TV_OPT_CLOCK_PROBE).  The expected hashes come from tv_v2_hash, and a sample of pieces read back with tv_read is
+checked against hashlib, so the timed verify is an exact one.  The only pass condition: the GPU beats the CPU figure.
+"""
+import argparse
+import hashlib
+import json
+import os
+import statistics
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from torrent_amd import _native as N  # noqa: E402
+
+LEAF = 16384
+# 1,400 VALU per SHA-256 compression in the emitted ISA, 833 half-rate (~4 cycles per wave64
+# instruction: v_alignbit, v_add3, v_perm) and 567 full-rate (~2): 4,466 SIMD cycles per 64 lanes x 64 B
+CYCLES_PER_BLOCK = 833 * 4 + 567 * 2
+R_VALU_256 = 1024 * 64 * 64 * 2.4e9 / CYCLES_PER_BLOCK / 1e9      # GB/s at 2.4 GHz
+
+
+def merkle_root(data, width: int) -> bytes:
+    row = [hashlib.sha256(data[o:o + LEAF]).digest() for o in range(0, len(data), LEAF)]
+    row += [bytes(32)] * (width - len(row))
+    while len(row) > 1:
+        row = [hashlib.sha256(row[i] + row[i + 1]).digest() for i in range(0, len(row), 2)]
+    return row[0]
+
+
+def cpu_sha256(buf, threads: int) -> float:
+    """GB/s of hashlib SHA-256 over the 16 KiB leaves of `buf` on `threads` threads (hashlib releases the GIL)."""
+    mv = memoryview(buf)
+    n = len(mv)
+    part = -(-n // threads // LEAF) * LEAF
+
+    def run(t):
+        for o in range(t * part, min(n, (t + 1) * part), LEAF):
+            hashlib.sha256(mv[o:o + LEAF]).digest()
+
+    with ThreadPoolExecutor(threads) as ex:
+        list(ex.map(run, range(threads)))          # warm-up
+        t0 = time.perf_counter()
+        list(ex.map(run, range(threads)))
+        return n / (time.perf_counter() - t0) / 1e9
+
+
+def shape(ctx, name: str, total: int, L: int, steps: int, warmup: int, sample: int, sha1: bool) -> dict:
+    P = total // L
+    W = L // LEAF
+    ctx.set_layout(total, L, P)
+    ctx.fill_synthetic(5)
+    ctx.v2_set_pieces([L] * P, [W] * P, None)
+    roots = ctx.v2_hash()
+    # exactness on a sample of pieces read back from HBM
+    buf = bytearray(L)
+    for i in sorted({0, P - 1, *(P * k // sample for k in range(sample))}):
+        ctx.read(i * L, buf)
+        assert roots[32 * i:32 * i + 32] == merkle_root(bytes(buf), W), f"piece {i} differs from hashlib"
+    ctx.v2_set_pieces([L] * P, [W] * P, roots)
+    out = {"shape": name, "bytes": total, "piece_length": L, "pieces": P, "leaves": P * W, "mappings": {}}
+    ms = {1: [], 2: []}
+    khz = {1: [], 2: []}
+    for step in range(warmup + steps):
+        for m in (1, 2):                           # alternated: both see the same clock and neighbours
+            ctx.set_option(N.TV_OPT_V2_MAP, m)
+            bits = ctx.v2_verify()
+            assert bits == b"\xff" * (P // 8), "v2_verify: not all ones"
+            assert ctx.counter(N.TV_COUNTER_V2_MAP) == m
+            if step >= warmup:
+                ms[m].append(ctx.last_timing()[0])
+                khz[m].append(ctx.last_clock_khz())
+    ctx.set_option(N.TV_OPT_V2_MAP, 0)
+    for m, label in ((1, "leaf_linear"), (2, "piece_major")):
+        med = statistics.median(ms[m])
+        clock = statistics.median(khz[m])
+        gbs = total / med / 1e6
+        out["mappings"][label] = {
+            "kernel_ms_median": round(med, 4), "kernel_ms_min": round(min(ms[m]), 4), "kernel_ms_max": round(max(ms[m]), 4),
+            "GBps": round(gbs, 1), "clock_khz": clock,
+            "fraction_of_R_valu_2400": round(gbs / R_VALU_256, 4),
+            "fraction_of_R_valu_live_clock": round(gbs / (R_VALU_256 * clock / 2.4e6), 4) if clock else None}
+    ctx.v2_verify()
+    out["default_mapping"] = ctx.counter(N.TV_COUNTER_V2_MAP)
+    out["launches"] = ctx.last_kernel()[1]
+    if sha1:
+        ctx.set_digests(ctx.hash())
+        t = []
+        for step in range(warmup + steps):
+            assert ctx.verify() == b"\xff" * (P // 8)
+            if step >= warmup:
+                t.append(ctx.last_timing()[0])
+        med = statistics.median(t)
+        out["sha1_tv_verify"] = {"kernel_ms_median": round(med, 4), "GBps": round(total / med / 1e6, 1),
+                                 "kernel": ctx.last_kernel()[0]}
+    return out
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--cfg2-gib", type=int, default=16)
+    ap.add_argument("--cfg4-gib", type=int, default=200)
+    ap.add_argument("--cpu-gib", type=float, default=1.0)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if N.device_count() == 0:
+        raise SystemExit("no HIP device visible: this measures the GPU")
+    res = {"R_valu_sha256_GBps_2400": round(R_VALU_256, 1), "cycles_per_block": CYCLES_PER_BLOCK,
+           "build_id": N.build_id(), "steps": a.steps, "warmup": a.warmup, "shapes": []}
+    with N.Context(0) as ctx:
+        ctx.set_clock_probe(True)
+        res["shapes"].append(shape(ctx, "cfg2", a.cfg2_gib << 30, 1 << 20, a.steps, a.warmup, 8, True))
+        # the CPU figure: hashlib over bytes of the same payload, read back
+        threads = N.cpu_share()
+        host = bytearray(int(a.cpu_gib * (1 << 30)) // LEAF * LEAF)
+        ctx.read(0, host)
+        res["cpu_sha256"] = {"threads": threads, "bytes": len(host), "GBps": round(cpu_sha256(host, threads), 2)}
+        del host
+        gib = a.cfg4_gib
+        while gib >= 8:                            # cfg4's piece geometry at whatever fits resident
+            try:
+                ctx.set_layout(gib << 30, 4 << 20, (gib << 30) >> 22)
+                if ctx.counter(N.TV_COUNTER_WINDOW_PIECES) == 0:
+                    break
+            except N.NativeError as e:
+                if e.code != N.TV_ERR_NOMEM:
+                    raise
+            gib //= 2
+        res["shapes"].append(shape(ctx, f"cfg4_geometry_{gib}GiB", gib << 30, 4 << 20, a.steps, a.warmup, 4, True))
+    best = max(m["GBps"] for m in res["shapes"][0]["mappings"].values())
+    res["gpu_beats_cpu"] = best > res["cpu_sha256"]["GBps"]
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    return 0 if res["gpu_beats_cpu"] else 1
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

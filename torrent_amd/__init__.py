@@ -5,7 +5,7 @@ libtorrent_verify.so (hand-written HIP for gfx950, C ABI in include/torrent_veri
 This package is the host-side mirror of the reference's piece/storage/metainfo API
 (piece.ts, storage.ts, metainfo.ts) plus the new verify module.
 """
-from .bencode import bdecode, bencode  # noqa: F401
+from .bencode import bdecode, bdecode_raw, bencode  # noqa: F401
 from .metainfo import FileInfo, InfoDict, Metainfo, make_info, parse_metainfo, partition  # noqa: F401
 from .piece import BLOCK_SIZE, piece_length, validate_received_block, validate_requested_block  # noqa: F401
 from .storage import FsStorage, MemoryStorage, Storage, fs_storage  # noqa: F401
@@ -14,6 +14,9 @@ from .verify import (context_counters, hash_files, hash_pieces, release_contexts
                      verify_pieces_async, verify_stream)
 from .incremental import IncrementalVerifier  # noqa: F401
 from .make_torrent import make_torrent  # noqa: F401
+from .metainfo_v2 import FileV2, MetainfoV2, V2Layout, parse_metainfo_v2  # noqa: F401
+from .v2 import (hash_files_v2, make_torrent_v2, verify_files_v2, verify_payload_v2,  # noqa: F401
+                 verify_piece_v2)
 
 __all__ = [
     "bdecode", "bencode", "FileInfo", "InfoDict", "Metainfo", "make_info", "parse_metainfo", "partition",
@@ -22,4 +25,6 @@ __all__ = [
     "hash_pieces", "shard_ranges", "verify_files", "verify_payload", "verify_piece", "verify_piece_async",
     "verify_pieces", "verify_pieces_async", "verify_stream", "release_contexts", "context_counters", "hash_files",
     "IncrementalVerifier", "make_torrent",
+    "bdecode_raw", "FileV2", "MetainfoV2", "V2Layout", "parse_metainfo_v2", "hash_files_v2", "make_torrent_v2",
+    "verify_files_v2", "verify_payload_v2", "verify_piece_v2",
 ]

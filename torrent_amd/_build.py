@@ -16,7 +16,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libtorrent_verify.so")
 SOURCES = ["tv_kernels.hip", "tv_core.hip", "tv_context.hip", "tv_stage.hip", "tv_files.hip",
-           "tv_stream.hip", "tv_verify.hip"]
+           "tv_stream.hip", "tv_verify.hip", "tv_v2_kernels.hip", "tv_v2.hip"]
 HOST_SOURCES = ["tv_host.cpp"]          # host-only C++ (no device code): the host compiler
 EXPORTS = os.path.join(CSRC, "exports.map")   # the link exports tv_* only
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -84,7 +84,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     host_srcs = [os.path.join(CSRC, s) for s in HOST_SOURCES]
     deps = srcs + host_srcs + [header, os.path.join(CSRC, "tv_internal.h"), os.path.join(CSRC, "tv_host.h"),
                                os.path.join(CSRC, "tv_ctx.h"), os.path.join(CSRC, "tv_options_internal.h"), EXPORTS,
-                               os.path.join(CSRC, "tv_plan.h"),
+                               os.path.join(CSRC, "tv_plan.h"), os.path.join(CSRC, "tv_block.h"),
+                               os.path.join(CSRC, "tv_sha256.h"),
                                os.path.join(ROOT, "include", "torrent_verify.h")]
     if not (force or _newer(LIB, deps)):
         return LIB

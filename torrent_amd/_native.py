@@ -56,6 +56,9 @@ TV_OPT_STREAM_COLD_WINDOW = 26
 TV_OPT_STREAM_COLD_READERS = 27
 TV_OPT_STREAM_COLD_REQ = 28
 TV_COUNTER_WINDOW_BUFS = 122
+TV_OPT_V2_MAP = 29
+TV_COUNTER_V2_MAP = 124
+V2_MAP_LEAF, V2_MAP_PIECE = 1, 2   # tv_internal.h TV_V2_MAP_*
 TV_COUNTER_WINDOW_STREAMS = 123
 WIN_BUFS_DEFAULT = 3    # tv_plan.h kWinBufsDefault: window buffers of a windowed layout
 FILE_BOUNCE_DEFAULT = 2  # tv_ctx.h file_bounce: cold-read bounce readers per staging lane
@@ -77,9 +80,11 @@ TV_COUNTER_SLOTS_USED = 11
 TV_COUNTER_LAST_CLOCK_KHZ = 12
 
 TV_STREAM_RING_SLOTS = 3
+TV_V2_LEAF_BYTES = 16384
 TV_STREAM_SLOT_BYTES = 64 << 20
 
 KERNEL_AUTO, KERNEL_LANE, KERNEL_SPLIT, KERNEL_TWIN = 0, 1, 2, 4   # (3 was MIX, removed)
+KERNEL_V2 = 8   # tv_last_kernel after tv_v2_verify / tv_v2_hash
 
 _u64, _i64, _int, _p = ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
 
@@ -125,6 +130,9 @@ SYMBOLS = [
     ("tv_verify_host", _int, [_p, _p, _u64, _p, _p]),
     ("tv_verify_list", _int, [_p, _p, _u64, _p]),
     ("tv_hash", _int, [_p, _p]),
+    ("tv_v2_set_pieces", _int, [_p, _u64, _p, _p, _p]),
+    ("tv_v2_verify", _int, [_p, _p, _p]),
+    ("tv_v2_hash", _int, [_p, _p]),
     ("tv_stream_begin", _int, [_p, _p]),
     ("tv_stream_next", _int, [_p, _REQ]),
     ("tv_stream_commit", _int, [_p, _REQ]),
@@ -545,6 +553,38 @@ class Context:
         out = ctypes.create_string_buffer(max(1, 20 * self.shard_count))
         self._check(self._L.tv_hash(self._h, out))
         return out.raw[: 20 * self.shard_count]
+
+    # -- BitTorrent v2 (BEP 52): SHA-256 merkle piece roots ------------------------------------
+    def v2_set_pieces(self, piece_bytes, tree_leaves, hashes: Optional[bytes] = None) -> None:
+        """tv_v2_set_pieces: the v2 piece table of the layout (GLOBAL entries, one per piece of the aligned space):
+        valid bytes and merkle tree width of every piece, and the expected 32-byte roots (None: creation mode)."""
+        import numpy as np
+        pb = np.ascontiguousarray(piece_bytes, dtype=np.uint32)
+        tl = np.ascontiguousarray(tree_leaves, dtype=np.uint32)
+        if len(pb) != len(tl):
+            raise ValueError("v2_set_pieces: piece_bytes and tree_leaves differ in length")
+        if hashes is not None and len(hashes) != 32 * len(pb):
+            raise ValueError("v2_set_pieces: hashes must hold 32 bytes per piece")
+        a, keep = _addr(hashes)
+        if hashes is not None and a is None:   # (an empty table in verify mode: any non-NULL pointer)
+            keep = ctypes.create_string_buffer(1)
+            a = ctypes.addressof(keep)
+        self._check(self._L.tv_v2_set_pieces(self._h, len(pb), pb.ctypes.data, tl.ctypes.data, a))
+        del keep
+
+    def v2_verify(self, avail_bits=None) -> bytes:
+        """tv_v2_verify: the shard's have-bits (as verify), piece roots against the table's hashes."""
+        out = ctypes.create_string_buffer(max(1, self._nbits()))
+        a, keep = _addr(avail_bits)
+        self._check(self._L.tv_v2_verify(self._h, a, out))
+        del keep
+        return out.raw[: self._nbits()]
+
+    def v2_hash(self) -> bytes:
+        """tv_v2_hash: the 32-byte merkle root of every resident piece, in piece order."""
+        out = ctypes.create_string_buffer(max(1, 32 * self.shard_count))
+        self._check(self._L.tv_v2_hash(self._h, out))
+        return out.raw[: 32 * self.shard_count]
 
     def last_timing(self) -> tuple:
         k, t = ctypes.c_double(0), ctypes.c_double(0)

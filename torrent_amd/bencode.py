@@ -78,6 +78,50 @@ def bdecode(data) -> Any:
     return _decode(mv, 0)[1]
 
 
+def _decode_raw(data: memoryview, start: int, spans, depth: int):
+    """_decode with dictionary keys kept as bytes; `spans` (a dict, or None) receives the (start, end) byte span of
+    every value of the TOP-LEVEL dictionary, by key."""
+    if start >= len(data):
+        raise ValueError("Failed to bdecode. Unexpected end of input")
+    c = data[start]
+    if c == _DICT:
+        out = {}
+        n = start + 1
+        while n < len(data) and data[n] != _END:
+            n, key = _decode_str(data, n)
+            v0 = n
+            n, val = _decode_raw(data, n, spans, depth + 1)
+            out[bytes(key)] = val
+            if depth == 0 and spans is not None:
+                spans[bytes(key)] = (v0, n)
+        if n >= len(data):
+            raise ValueError("Failed to bdecode. Malformed dictionary")
+        return n + 1, out
+    if c == _LIST:
+        out = []
+        n = start + 1
+        while n < len(data) and data[n] != _END:
+            n, val = _decode_raw(data, n, spans, depth + 1)
+            out.append(val)
+        if n >= len(data):
+            raise ValueError("Failed to bdecode. Malformed list")
+        return n + 1, out
+    if c == _INT:
+        return _decode_int(data, start)
+    return _decode_str(data, start)
+
+
+def bdecode_raw(data, spans: bool = False) -> Any:
+    """Decode bencoded bytes with dictionary keys kept as `bytes` (bdecode turns keys into text, which destroys keys
+    that are raw hashes, such as those of a v2 torrent's `piece layers`).  spans=True returns (value, {key: (start,
+    end)}): the byte span in `data` of each value of the top-level dictionary (the raw `info` bytes an info-hash is
+    taken over)."""
+    mv = memoryview(data)
+    sp = {} if spans else None
+    val = _decode_raw(mv, 0, sp, 0)[1]
+    return (val, sp) if spans else val
+
+
 def _encode(out: bytearray, v: Any) -> None:
     if isinstance(v, str):
         b = v.encode()

@@ -291,6 +291,10 @@ int tv_set_option(tv_ctx* c, int key, int64_t value) {
                 return fail(c, TV_ERR_ARG, "TV_OPT_WIN_STREAMS must be 0 (default) .. %d", kWinHashStreams);
             c->win_streams_opt = (int)value;   // takes effect at the next tv_set_layout
             return TV_OK;
+        case TV_OPT_V2_MAP:
+            if (value < 0 || value > 2) return fail(c, TV_ERR_ARG, "TV_OPT_V2_MAP must be 0 (auto), 1 (leaf-linear) or 2 (piece-major)");
+            c->v2_map_opt = (int)value;
+            return TV_OK;
         case TV_OPT_STREAM_ROWS:
             if (value != 0 && value != 1) return fail(c, TV_ERR_ARG, "TV_OPT_STREAM_ROWS must be 0 or 1");
             if (c->st.active) return fail(c, TV_ERR_STATE, "TV_OPT_STREAM_ROWS cannot change during a stream");
@@ -332,6 +336,7 @@ int tv_get_option(tv_ctx* c, int key, int64_t* value) {
         case TV_OPT_STREAM_COLD_READERS: *value = c->stream_cold_readers; return TV_OK;
         case TV_OPT_STREAM_COLD_REQ: *value = (int64_t)c->stream_cold_req; return TV_OK;
         case TV_OPT_WIN_STREAMS: *value = c->win_streams_opt; return TV_OK;
+        case TV_OPT_V2_MAP: *value = c->v2_map_opt; return TV_OK;
     }
     return fail(c, TV_ERR_ARG, "unknown option %d", key);
 }
@@ -368,6 +373,7 @@ int tv_set_layout(tv_ctx* c, uint64_t total_length, uint64_t piece_length, uint6
     }
     c->has_layout = false;
     c->digests_set = false;
+    c->v2_set = c->v2_hashes = false;
     c->total = total_length;
     c->L = piece_length;
     c->P = n_pieces;
@@ -475,6 +481,7 @@ int tv_set_layout(tv_ctx* c, uint64_t total_length, uint64_t piece_length, uint6
     if (!reuse_fits(c->bit_words, c->cap_words)) free_words(c);
     if (c->chunk_bytes && (need_payload || !reuse_fits(stream_chunk_need(c), c->chunk_bytes))) free_chunks(c);
     if (c->list_cap > std::max<uint64_t>(1024, 2 * shard_count)) free_list(c);
+    v2_on_layout(c);
     if (shard_count && !c->d_digests) {
         TV_HIP(c, hipMalloc((void**)&c->d_digests, 5 * shard_count * sizeof(uint32_t)));
         TV_HIP(c, hipMalloc((void**)&c->d_state, 5 * shard_count * sizeof(uint32_t)));
@@ -587,7 +594,8 @@ int tv_get_counter(tv_ctx* c, int key, uint64_t* value) {
         case TV_COUNTER_PAYLOAD_BYTES: *value = c->cap_payload; return TV_OK;
         case TV_COUNTER_DEVICE_BYTES:
             *value = c->cap_payload + c->cap_count * 3 * 5 * sizeof(uint32_t) + c->cap_words * 8 * 3 +
-                     2 * c->chunk_bytes + c->list_cap * 9;
+                     2 * c->chunk_bytes + c->list_cap * 9 + c->cap_v2_count * 18 * sizeof(uint32_t) +
+                     c->cap_v2_nodes * sizeof(uint32_t);
             return TV_OK;
         case TV_COUNTER_LAST_WORKGROUPS: *value = c->last_workgroups; return TV_OK;
         case TV_COUNTER_NUMA_NODE: *value = c->numa_node < 0 ? UINT64_MAX : (uint64_t)c->numa_node; return TV_OK;
@@ -601,6 +609,7 @@ int tv_get_counter(tv_ctx* c, int key, uint64_t* value) {
         case TV_COUNTER_WINDOW_BUFS: *value = c->win ? (uint64_t)c->win_bufs : 0; return TV_OK;
         case TV_COUNTER_WINDOW_STREAMS: *value = c->win ? (uint64_t)c->win_nhs : 0; return TV_OK;
         case TV_COUNTER_BUDGET: *value = c->budget; return TV_OK;
+        case TV_COUNTER_V2_MAP: *value = (uint64_t)c->v2_last_map; return TV_OK;
         case TV_COUNTER_SLOTS_USED: *value = c->slot_of.size(); return TV_OK;
         case TV_COUNTER_FILE_CLOCK + TV_FILE_PHASE_OPEN ... TV_COUNTER_FILE_CLOCK + TV_FILE_CLOCK_N - 1:
             *value = c->file_ns[key - TV_COUNTER_FILE_CLOCK].load();

@@ -1,7 +1,8 @@
 // tv_ctx.h -- internal to libtorrent_verify.so: the context (struct tv_ctx, one per GPU) and the helpers its
 // translation units share.  tv_context.hip: lifecycle, options, layout, digests, counters; tv_core.hip: errors, NUMA,
 // staging rings, windows, slot pool, kernel choice, the host -> HBM copy path; tv_stage.hip: staging from memory;
-// tv_files.hip: staging from files; tv_stream.hip: the streamed engine; tv_verify.hip: verify / list / hash.
+// tv_files.hip: staging from files; tv_stream.hip: the streamed engine; tv_verify.hip: verify / list / hash;
+// tv_v2.hip: the BitTorrent v2 piece table, verify and hash.
 // Nothing here is exported (the link exports tv_* only: exports.map).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -311,6 +312,19 @@ struct tv_ctx {
     std::vector<uint32_t> slot_free;
     std::mutex slot_mu;                // piece_dst's slot path: tv_stage_files' lane-1 helper stages beside the caller
 
+    // BitTorrent v2 (tv_v2.hip): the shard's piece table and merkle node buffers.  tv_set_layout drops the table
+    // (v2_set) and keeps the allocations the new geometry fits (reuse_fits), as for the other per-layout memory.
+    bool v2_set = false;               // tv_v2_set_pieces has run for this layout
+    bool v2_hashes = false;            // ... with expected hashes (tv_v2_verify needs them)
+    uint32_t v2_logW = 0;              // log2(L / 16 KiB)
+    uint32_t v2_maxlog = 0;            // log2 of the widest tree in the shard (tree levels to run)
+    uint32_t* d_v2_tab = nullptr;      // [18][cap_v2_count]: piece bytes, tree leaves, expected [8], roots [8]
+    uint32_t* d_v2_nodes = nullptr;    // level buffers A [8][count x W] then B [8][count x max(W/2, 1)]
+    uint64_t cap_v2_count = 0;         // pieces of d_v2_tab
+    uint64_t cap_v2_nodes = 0;         // words of d_v2_nodes
+    int v2_map_opt = 0;                // TV_OPT_V2_MAP: 0 auto, else TV_V2_MAP_*
+    int v2_last_map = 0;               // the mapping the last v2 call's leaf kernel ran with
+
     bool open_rw = true;               // TV_OPT_OPEN_RW: files opened read + write (fsStorage.get) or read-only
     bool stream_rows = false;          // TV_OPT_STREAM_ROWS: stream requests carry whole pieces (windows of pieces)
     int lane_pairs = 0;                // TV_OPT_LANE_PAIRS: 0 auto (>= 256 x CUs pieces in the launch), 1 on, 2 off
@@ -372,6 +386,8 @@ void free_per_piece(tv_ctx* c);
 void free_words(tv_ctx* c);
 void free_chunks(tv_ctx* c);
 void free_list(tv_ctx* c);
+void free_v2(tv_ctx* c);
+void v2_on_layout(tv_ctx* c);   // tv_set_layout: drop the v2 piece table, free what the new geometry does not fit
 void free_device(tv_ctx* c);
 bool reuse_fits(uint64_t need, uint64_t cap);
 

@@ -54,6 +54,38 @@ struct TvPieces {
                              // 64-B blocks of a 128-B line loaded back to back; >= 1 wave per SIMD), 0 = 3-deep ring
 };
 
+// ---- BitTorrent v2 (BEP 52): SHA-256 merkle piece roots over 16 KiB leaves (tv_v2_kernels.hip, tv_v2.hip) ----------
+#define TV_KERNEL_V2 8      // tv_last_kernel id of tv_v2_verify / tv_v2_hash (leaf kernel + tree levels + finish)
+#define TV_V2_MAP_LEAF 1    // lanes of a wave = consecutive leaves of one piece (16 KiB apart)
+#define TV_V2_MAP_PIECE 2   // lanes of a wave = one leaf index of 64 consecutive pieces (`stride` apart)
+
+// One v2 launch set over the n resident pieces of a shard.  Piece j's leaf k is the bytes at data + j*stride +
+// k*16384; its hash goes to node slot j*W + k of level buffer A.  The tree levels ping-pong between A (row pitch W
+// nodes per piece) and B (row pitch max(W/2, 1)); both are SoA [8][rows] words (big-endian values).
+struct TvV2 {
+    const uint8_t* data;
+    uint64_t stride;
+    uint32_t n;                  // pieces
+    uint32_t logW;               // W = L / 16 KiB = 1 << logW leaves in a full piece
+    uint32_t map;                // TV_V2_MAP_*
+    const uint32_t* piece_bytes; // [n] valid bytes of piece j (1 .. L)
+    const uint32_t* tree_leaves; // [n] width of piece j's tree (a power of two, >= its leaves, <= W)
+    uint32_t* nodes_a;           // [8][n << logW]
+    uint32_t* nodes_b;           // [8][n * max(W/2, 1)]
+    const uint32_t* expect;      // verify: [8][n] expected root words
+    uint32_t* roots;             // hash: [8][n] root words out
+    const uint64_t* avail64;     // verify: MSB-first availability bytes in 64-bit words; may be null
+    uint64_t* out64;             // verify: MSB-first bitfield bytes in 64-bit words, whole 256-piece groups
+    uint64_t* clock;             // TV_OPT_CLOCK_PROBE (as TvPieces::clock); null = off
+};
+// Leaf hashes (every leaf inside a piece's valid bytes is hashed, the other positions of its tree get zero hashes).
+hipError_t tv_v2_launch_leaves(const TvV2& p, hipStream_t s, uint32_t* workgroups);
+// Tree level `level` (0 = leaves -> their parents) for every piece whose tree is wider than 1 << level; `maxlog` = the
+// widest tree of the launch (log2).
+hipError_t tv_v2_launch_level(const TvV2& p, uint32_t level, uint32_t maxlog, hipStream_t s);
+// Roots: compare with `expect` and the availability into out64 (hash = false), or copy them to `roots`.
+hipError_t tv_v2_launch_finish(const TvV2& p, bool hash, hipStream_t s);
+
 // workgroups (optional): set to the launch's grid size, companions included.
 hipError_t tv_launch_verify(const TvPieces& p, int kernel, bool hash, hipStream_t s, int split_pairs = 0,
                             uint32_t* workgroups = nullptr);

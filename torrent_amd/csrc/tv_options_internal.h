@@ -61,6 +61,11 @@
                                 back to back when the launch has >= 256 x CUs pieces (>= 1 wave per SIMD; HBM reads
                                 1.0004 instead of 1.023 x payload at 262,144 x 64 KiB), else a 3-deep ring of
                                 single blocks; 1 = pairs always; 2 = never */
+#define TV_OPT_V2_MAP 29 /* tv_v2_verify / tv_v2_hash: which lane of the leaf kernel hashes which 16 KiB leaf.  1 =
+                            leaf-linear (a wave's lanes are consecutive leaves of one piece, 16 KiB apart); 2 =
+                            piece-major (a wave's lanes are one leaf index of 64 consecutive pieces, `stride` apart as in
+                            the SHA-1 lane kernel; shards of fewer than 64 pieces run leaf-linear); 0 (default) = auto */
+#define TV_COUNTER_V2_MAP 124 /* the mapping the last tv_v2_verify / tv_v2_hash ran with (1 or 2; 0: none yet) */
 
 /* ---- file staging phase clock (tv_files.hip), for the stamped breakdown of tools/f2_stamps.py ---------------------
  * tv_get_counter(TV_COUNTER_FILE_CLOCK + phase): nanoseconds tv_stage_file(s) spent in that phase since the last

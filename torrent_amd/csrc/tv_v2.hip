@@ -1,0 +1,229 @@
+// tv_v2.hip -- BitTorrent v2 (BEP 52): the piece table of a layout (tv_v2_set_pieces) and the SHA-256 merkle verify
+// and hash calls over the resident shard (tv_v2_verify, tv_v2_hash): one leaf launch, one launch per tree level, one
+// finish launch (tv_v2_kernels.hip).
+#include <cstring>
+
+#include "tv_ctx.h"
+
+using namespace tvi;
+
+namespace tvi {
+
+void free_v2(tv_ctx* c) {
+    (void)hipFree(c->d_v2_tab); c->d_v2_tab = nullptr;
+    (void)hipFree(c->d_v2_nodes); c->d_v2_nodes = nullptr;
+    c->cap_v2_count = c->cap_v2_nodes = 0;
+    c->v2_set = c->v2_hashes = false;
+}
+
+static bool v2_piece_length_ok(uint64_t L) { return L >= TV_V2_LEAF_BYTES && (L & (L - 1)) == 0; }
+
+// Words of the two level buffers for `count` pieces of W leaves: A [8][count x W], B [8][count x max(W/2, 1)].
+static uint64_t v2_node_words(uint64_t count, uint64_t W) { return 8 * count * (W + (W > 1 ? W / 2 : 1)); }
+
+void v2_on_layout(tv_ctx* c) {
+    c->v2_set = c->v2_hashes = false;
+    if (!c->d_v2_tab && !c->d_v2_nodes) return;
+    // keep what a v2 table of the new geometry would reuse; anything else goes (a v1 layout holds no v2 memory)
+    const bool v2 = v2_piece_length_ok(c->L) && c->count && !c->win && !c->slots;
+    if (!v2 || !reuse_fits(c->count, c->cap_v2_count) ||
+        !reuse_fits(v2_node_words(c->count, c->L / TV_V2_LEAF_BYTES), c->cap_v2_nodes))
+        free_v2(c);
+}
+
+}  // namespace tvi
+
+namespace {
+
+// The calls' common state checks (in the order the header lists them).
+int v2_require(tv_ctx* c, const char* what) {
+    const int rc = require_layout(c, false, true);
+    if (rc) return rc;
+    if (c->win)
+        return fail(c, TV_ERR_STATE, "%s needs the shard resident; this layout is windowed (the shard exceeds the "
+                                     "device budget)", what);
+    if (c->slots) return fail(c, TV_ERR_STATE, "%s needs the shard resident; this layout is a slot pool (TV_OPT_LIST_SLOTS)", what);
+    return TV_OK;
+}
+
+// Availability of one v2 launch: the caller's bits less the pieces file staging could not read; null = all.
+int v2_avail(tv_ctx* c, const uint8_t* avail_bits, const uint64_t** out) {
+    *out = nullptr;
+    if (!avail_bits && !c->any_file_bad) return TV_OK;
+    TV_HIP(c, hipEventSynchronize(c->ev_avail));  // the previous copy out of h_avail is done
+    const size_t nbytes = c->bit_words * 8, used = (c->count + 7) / 8;
+    for (size_t k = 0; k < nbytes; k++) {
+        const uint8_t caller = k < used ? (avail_bits ? avail_bits[k] : 0xFF) : 0;
+        c->h_avail[k] = k < used ? (uint8_t)(caller & ~c->file_bad[k]) : 0;
+    }
+    TV_HIP(c, hipMemcpyAsync(c->d_avail, c->h_avail, nbytes, hipMemcpyHostToDevice, c->stream));
+    TV_HIP(c, hipEventRecord(c->ev_avail, c->stream));
+    *out = c->d_avail;
+    return TV_OK;
+}
+
+TvV2 v2_launch_args(tv_ctx* c) {
+    TvV2 p{};
+    const uint64_t W = 1ull << c->v2_logW;
+    p.data = c->d_payload;
+    p.stride = c->stride;
+    p.n = (uint32_t)c->count;
+    p.logW = c->v2_logW;
+    // piece-major needs a full wave of pieces; below that (and by default) leaf-linear
+    const int want = c->v2_map_opt ? c->v2_map_opt : TV_V2_MAP_LEAF;
+    p.map = (want == TV_V2_MAP_PIECE && c->count >= 64) ? TV_V2_MAP_PIECE : TV_V2_MAP_LEAF;
+    uint32_t* tab = c->d_v2_tab;
+    const uint64_t cap = c->cap_v2_count;
+    p.piece_bytes = tab;
+    p.tree_leaves = tab + cap;
+    p.expect = tab + 2 * cap;     // [8][count] packed at the row length `count` (<= cap)
+    p.roots = tab + 10 * cap;
+    p.nodes_a = c->d_v2_nodes;
+    p.nodes_b = c->d_v2_nodes + 8 * c->count * W;
+    p.out64 = c->d_out;
+    p.clock = c->clock_probe ? c->d_clock : nullptr;
+    return p;
+}
+
+// leaf kernel, tree levels, finish; ev_k0 .. ev_k1 bracket them
+int v2_run(tv_ctx* c, TvV2& p, bool hash) {
+    TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
+    TV_HIP(c, tv_v2_launch_leaves(p, c->stream, &c->last_workgroups));
+    for (uint32_t l = 0; l < c->v2_maxlog; l++) TV_HIP(c, tv_v2_launch_level(p, l, c->v2_maxlog, c->stream));
+    TV_HIP(c, tv_v2_launch_finish(p, hash, c->stream));
+    TV_HIP(c, hipEventRecord(c->ev_k1, c->stream));
+    c->v2_last_map = (int)p.map;
+    c->last_kernel = TV_KERNEL_V2;
+    c->last_launches = 2 + (int)c->v2_maxlog;
+    return TV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tv_v2_set_pieces(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const uint32_t* tree_leaves,
+                     const uint8_t* hashes) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = v2_require(c, "tv_v2_set_pieces");
+    if (rc) return rc;
+    c->v2_set = c->v2_hashes = false;
+    if (!v2_piece_length_ok(c->L))
+        return fail(c, TV_ERR_ARG, "a v2 piece length is a power of two >= %d (the layout has %llu)", TV_V2_LEAF_BYTES,
+                    (unsigned long long)c->L);
+    if (n != c->P)
+        return fail(c, TV_ERR_ARG, "the piece table has %llu entries, the layout %llu pieces", (unsigned long long)n,
+                    (unsigned long long)c->P);
+    if (n && (!piece_bytes || !tree_leaves)) return fail(c, TV_ERR_ARG, "NULL argument");
+    const uint64_t W = c->L / TV_V2_LEAF_BYTES;
+    for (uint64_t p = 0; p < n; p++) {
+        const uint64_t b = piece_bytes[p], w = tree_leaves[p];
+        if (b == 0 || b > c->L)
+            return fail(c, TV_ERR_ARG, "piece_bytes[%llu] = %llu is outside 1 .. %llu", (unsigned long long)p,
+                        (unsigned long long)b, (unsigned long long)c->L);
+        if (w == 0 || (w & (w - 1)) || w < (b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES || w > W)
+            return fail(c, TV_ERR_ARG, "tree_leaves[%llu] = %llu is not a power of two in %llu .. %llu",
+                        (unsigned long long)p, (unsigned long long)w,
+                        (unsigned long long)((b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES), (unsigned long long)W);
+    }
+    uint32_t logW = 0;
+    while ((1ull << logW) < W) logW++;
+    c->v2_logW = logW;
+    c->v2_maxlog = 0;
+    if (!c->count) {
+        c->v2_set = true;
+        c->v2_hashes = hashes != nullptr;
+        return TV_OK;
+    }
+    TV_HIP(c, hipSetDevice(c->device));
+    TV_HIP(c, hipStreamSynchronize(c->stream));   // (a v2 call of the last table may still read the buffers)
+    const uint64_t need_nodes = v2_node_words(c->count, W);
+    if (!c->d_v2_tab || !reuse_fits(c->count, c->cap_v2_count)) {
+        (void)hipFree(c->d_v2_tab);
+        c->d_v2_tab = nullptr;
+        c->cap_v2_count = 0;
+        TV_HIP(c, hipMalloc((void**)&c->d_v2_tab, 18 * c->count * sizeof(uint32_t)));
+        c->cap_v2_count = c->count;
+        c->n_device_allocs++;
+    }
+    if (!c->d_v2_nodes || !reuse_fits(need_nodes, c->cap_v2_nodes)) {
+        (void)hipFree(c->d_v2_nodes);
+        c->d_v2_nodes = nullptr;
+        c->cap_v2_nodes = 0;
+        TV_HIP(c, hipMalloc((void**)&c->d_v2_nodes, need_nodes * sizeof(uint32_t)));
+        c->cap_v2_nodes = need_nodes;
+        c->n_device_allocs++;
+    }
+    // the shard's rows: bytes, leaves, expected root words (big-endian values, SoA)
+    const uint64_t cap = c->cap_v2_count;
+    std::vector<uint32_t> tab(10 * cap, 0);
+    uint32_t maxw = 1;
+    for (uint64_t j = 0; j < c->count; j++) {
+        const uint64_t i = c->first + j;
+        tab[j] = piece_bytes[i];
+        tab[cap + j] = tree_leaves[i];
+        maxw = std::max(maxw, tree_leaves[i]);
+        if (!hashes) continue;
+        const uint8_t* d = hashes + 32 * i;
+        for (int k = 0; k < 8; k++)
+            tab[2 * cap + (uint64_t)k * c->count + j] = ((uint32_t)d[4 * k] << 24) | ((uint32_t)d[4 * k + 1] << 16) |
+                                                        ((uint32_t)d[4 * k + 2] << 8) | (uint32_t)d[4 * k + 3];
+    }
+    while ((1u << c->v2_maxlog) < maxw) c->v2_maxlog++;
+    TV_HIP(c, hipMemcpyAsync(c->d_v2_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    TV_HIP(c, hipStreamSynchronize(c->stream));
+    c->v2_set = true;
+    c->v2_hashes = hashes != nullptr;
+    return TV_OK;
+}
+
+int tv_v2_verify(tv_ctx* c, const uint8_t* avail_bits, uint8_t* bitfield_out) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = v2_require(c, "tv_v2_verify");
+    if (rc) return rc;
+    if (!c->v2_set) return fail(c, TV_ERR_STATE, "tv_v2_set_pieces has not been called for this layout");
+    if (!c->v2_hashes) return fail(c, TV_ERR_STATE, "tv_v2_verify: the piece table has no expected hashes (creation mode)");
+    if (!bitfield_out && c->count) return fail(c, TV_ERR_ARG, "bitfield_out is NULL");
+    if (!c->count) return TV_OK;
+    TV_HIP(c, hipSetDevice(c->device));
+    TV_HIP(c, hipEventRecord(c->ev_call0, c->stream));
+    TvV2 p = v2_launch_args(c);
+    rc = v2_avail(c, avail_bits, &p.avail64);
+    if (rc) return rc;
+    rc = v2_run(c, p, false);   // (the finish kernel writes every word of d_out)
+    if (rc) return rc;
+    rc = read_bits(c, bitfield_out);
+    if (rc) return rc;
+    return finish_timing(c);
+}
+
+int tv_v2_hash(tv_ctx* c, uint8_t* roots_out) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = v2_require(c, "tv_v2_hash");
+    if (rc) return rc;
+    if (!c->v2_set) return fail(c, TV_ERR_STATE, "tv_v2_set_pieces has not been called for this layout");
+    if (!roots_out && c->count) return fail(c, TV_ERR_ARG, "roots_out is NULL");
+    if (!c->count) return TV_OK;
+    TV_HIP(c, hipSetDevice(c->device));
+    TV_HIP(c, hipEventRecord(c->ev_call0, c->stream));
+    TvV2 p = v2_launch_args(c);
+    rc = v2_run(c, p, true);
+    if (rc) return rc;
+    std::vector<uint32_t> soa(8 * c->count);
+    DrainGuard drain(c);  // declared after soa: drains before soa is freed, also on error paths
+    TV_HIP(c, hipMemcpyAsync(soa.data(), p.roots, soa.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    TV_HIP(c, hipEventRecord(c->ev_call1, c->stream));
+    TV_HIP(c, hipEventSynchronize(c->ev_call1));
+    for (uint64_t j = 0; j < c->count; j++)
+        for (int k = 0; k < 8; k++) {
+            const uint32_t v = soa[(uint64_t)k * c->count + j];
+            uint8_t* d = roots_out + 32 * j + 4 * k;
+            d[0] = (uint8_t)(v >> 24); d[1] = (uint8_t)(v >> 16); d[2] = (uint8_t)(v >> 8); d[3] = (uint8_t)v;
+        }
+    return finish_timing(c);
+}
+
+}  // extern "C"

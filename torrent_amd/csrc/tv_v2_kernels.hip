@@ -1,0 +1,234 @@
+// tv_v2_kernels.hip -- gfx950 kernels of the BitTorrent v2 (BEP 52) path: SHA-256 merkle piece roots.
+//
+// A v2 piece hash is the root of a binary SHA-256 tree over the piece's 16 KiB blocks ("leaves"):
+//   leaf      = SHA-256 of the block at its real length (a file's last block is 1 .. 16,384 bytes, never padded);
+//   interior  = SHA-256(left || right), a 64-byte message: two compressions, the second over a constant block;
+//   a leaf position past the file's end is 32 zero bytes (not the hash of anything); the nodes above it are hashed
+//   like any other.
+// The serial unit is therefore 16 KiB, not a piece, so the parallelism is pieces x leaves:
+//   leaf kernel   : one lane per leaf; each lane loads its own 64-byte blocks (register prefetch, 3 blocks ahead, as
+//                   the SHA-1 lane kernel) and runs the compression in plain C++ (tv_sha256.h).  Leaf hashes go to the
+//                   node buffer A, SoA [8][pieces x W], W = L / 16 KiB.
+//   level kernel  : one launch per tree level, one lane per parent node; the levels ping-pong between A and B.
+//   finish kernel : one lane per piece: the root against the expected hash and the availability bit -> MSB-first
+//                   bitfield words (as tv_compare_kernel), or the root out (creation mode).
+// Which lane hashes which leaf (TvV2::map): consecutive leaves of a piece (addresses 16 KiB apart), or one leaf index
+// of 64 consecutive pieces (addresses `stride` apart, the layout the SHA-1 lane kernel reads).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "tv_block.h"
+#include "tv_internal.h"
+#include "tv_sha256.h"
+
+namespace {
+
+constexpr uint32_t kLeaf = 16384;
+constexpr int kDepth = 3;   // raw blocks in flight per lane (the SHA-1 lane kernel's TV_LANE_DEPTH)
+
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)v, m, 64);
+        v = o < v ? o : v;
+    }
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)v, m, 64);
+        v = o > v ? o : v;
+    }
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+__device__ __forceinline__ void bswap_block(const uint4 (&r)[4], uint32_t w[16]) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        w[4 * i + 0] = bswap32(r[i].x);
+        w[4 * i + 1] = bswap32(r[i].y);
+        w[4 * i + 2] = bswap32(r[i].z);
+        w[4 * i + 3] = bswap32(r[i].w);
+    }
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------
+// leaf kernel: lane t of the launch hashes leaf k of piece j (MAP decides which).
+// ------------------------------------------------------------------------------------------
+template <int MAP>
+__global__ __launch_bounds__(256) void tv_v2_leaf_kernel(TvV2 p) {
+    uint64_t t0 = 0, r0 = 0;
+    if (p.clock && blockIdx.x == 0) {   // clock probe, as the SHA-1 kernels' ClockStamp
+        t0 = __builtin_amdgcn_s_memtime();
+        r0 = __builtin_amdgcn_s_memrealtime();
+    }
+    const uint32_t logW = p.logW, W = 1u << logW;
+    const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    uint64_t j;
+    uint32_t k;
+    if (MAP == TV_V2_MAP_LEAF) {
+        j = t >> logW;
+        k = (uint32_t)t & (W - 1u);
+    } else {   // groups of 64 pieces; inside a group lane = piece, wave = leaf index
+        const uint32_t r = (uint32_t)t & ((64u << logW) - 1u);
+        j = (t >> (6u + logW)) * 64u + (r & 63u);
+        k = r >> 6;
+    }
+    const bool valid = j < p.n;
+    const uint64_t bytes = valid ? p.piece_bytes[j] : 0;
+    const uint32_t wj = valid ? p.tree_leaves[j] : 0;
+    const bool in_tree = k < wj;
+    const uint64_t lo = (uint64_t)k * kLeaf;
+    const bool active = in_tree && lo < bytes;            // the leaf holds >= 1 valid byte
+    const uint32_t len = active ? (uint32_t)(bytes - lo < kLeaf ? bytes - lo : kLeaf) : 0;
+    const uint64_t np = (uint64_t)p.n << logW;            // SoA row length of A
+    const uint64_t slot = (j << logW) + k;
+    if (in_tree && !active) {   // a padding leaf: a zero hash, and no memory read
+#pragma unroll
+        for (int q = 0; q < 8; q++) p.nodes_a[q * np + slot] = 0;
+    }
+    // wave-uniform block ranges over the wave's hashing lanes: [0, fast_end) are raw data for every one of them,
+    // [fast_end, end) go the padded-block way with the lanes past their last block masked
+    const uint32_t nb = active ? (uint32_t)nblocks(len) : 0;
+    const uint32_t fast_end = wave_min(active ? len >> 6 : 0xFFFFFFFFu);
+    const uint32_t end = wave_max(nb);
+    if (active) {
+        const uint8_t* leaf = p.data + j * p.stride + lo;
+        uint32_t h[8], w[16];
+        tv256::iv(h);
+        uint32_t b = 0;
+        if (b < fast_end) {
+            // loads are unconditional (the block index is clamped to the last raw block), so they are never
+            // predicated and stay in flight across a block
+            const uint32_t last = fast_end - 1;
+            uint4 R[kDepth][4];
+#pragma unroll
+            for (int d = 0; d < kDepth; d++) load_block(leaf, b + d < last ? b + d : last, R[d]);
+            for (;;) {
+#pragma unroll
+                for (int d = 0; d < kDepth; d++) {
+                    bswap_block(R[d], w);
+                    load_block(leaf, b + kDepth < last ? b + kDepth : last, R[d]);
+                    tv256::compress(h, w, h);
+                    if (++b >= fast_end) goto raw_done;
+                }
+            }
+        }
+    raw_done:
+        for (; b < end; b++) {
+            build_tail_block(leaf, len, b, w);
+            uint32_t r[8];
+            tv256::compress(h, w, r);
+            if (b < nb) {
+#pragma unroll
+                for (int i = 0; i < 8; i++) h[i] = r[i];
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 8; q++) p.nodes_a[q * np + slot] = h[q];
+    }
+    if (p.clock && blockIdx.x == 0 && threadIdx.x == 0) {
+        const uint64_t t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+        reinterpret_cast<ulonglong2*>(p.clock)[0] = make_ulonglong2(t0, r0);
+        reinterpret_cast<ulonglong2*>(p.clock)[1] = make_ulonglong2(t1, r1);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// level kernel: parent i of piece j at tree level `level` = SHA-256(child 2i || child 2i + 1).  log_half = log2 of the
+// lanes per piece in this launch (the widest tree's parents at this level); a piece with a narrower tree uses fewer.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void tv_v2_level_kernel(TvV2 p, uint32_t level, uint32_t log_half) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint64_t j = t >> log_half;
+    const uint32_t i = (uint32_t)t & ((1u << log_half) - 1u);
+    if (j >= p.n) return;
+    if (i >= (p.tree_leaves[j] >> (level + 1u))) return;
+    const uint64_t W = 1ull << p.logW, WB = W > 1 ? W / 2 : 1;
+    const bool from_a = (level & 1u) == 0;
+    const uint32_t* in = from_a ? p.nodes_a : p.nodes_b;
+    uint32_t* out = from_a ? p.nodes_b : p.nodes_a;
+    const uint64_t in_row = from_a ? W : WB, out_row = from_a ? WB : W;
+    const uint64_t in_np = p.n * in_row, out_np = p.n * out_row;
+    const uint64_t src = j * in_row + 2ull * i, dst = j * out_row + i;   // (in_row and src are even: 8-byte loads)
+    uint32_t w[16], h[8];
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        const uint2 v = *reinterpret_cast<const uint2*>(in + q * in_np + src);
+        w[q] = v.x;       // word q of the left child
+        w[8 + q] = v.y;   // word q of the right child
+    }
+    tv256::iv(h);
+    tv256::compress(h, w, h);
+    uint32_t pad[16] = {0x80000000u, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 512u};   // a 64-byte message's padding
+    tv256::compress(h, pad, h);
+#pragma unroll
+    for (int q = 0; q < 8; q++) out[q * out_np + dst] = h[q];
+}
+
+// ------------------------------------------------------------------------------------------
+// finish kernel: piece j's root (node 0 of its row in A after an even number of levels, in B after an odd one).
+// ------------------------------------------------------------------------------------------
+template <bool HASH>
+__global__ __launch_bounds__(256) void tv_v2_finish_kernel(TvV2 p) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    bool ok = j < p.n;
+    if (ok) {
+        const uint64_t W = 1ull << p.logW, WB = W > 1 ? W / 2 : 1;
+        const uint32_t lw = 31u - (uint32_t)__builtin_clz(p.tree_leaves[j]);
+        const bool in_a = (lw & 1u) == 0;
+        const uint32_t* src = in_a ? p.nodes_a : p.nodes_b;
+        const uint64_t row = in_a ? W : WB, np = p.n * row;
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const uint32_t v = src[q * np + j * row];
+            if (HASH) p.roots[(uint64_t)q * p.n + j] = v;
+            else ok &= v == p.expect[(uint64_t)q * p.n + j];
+        }
+    }
+    if (HASH) return;
+    const uint64_t mask = __ballot(ok);
+    if ((threadIdx.x & 63u) == 0) {   // lane 0 of the wave: pieces j .. j + 63, word j >> 6
+        uint64_t bits = __builtin_bswap64(__builtin_bitreverse64(mask));   // ballot bit l -> MSB-first bytes
+        if (p.avail64) bits &= p.avail64[j >> 6];
+        p.out64[j >> 6] = bits;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// host-side launchers (tv_v2.hip)
+// ------------------------------------------------------------------------------------------
+hipError_t tv_v2_launch_leaves(const TvV2& p, hipStream_t s, uint32_t* workgroups) {
+    if (workgroups) *workgroups = 0;
+    if (p.n == 0) return hipSuccess;
+    const uint64_t pieces = p.map == TV_V2_MAP_PIECE ? ((uint64_t)p.n + 63) / 64 * 64 : p.n;
+    const uint64_t grid = ((pieces << p.logW) + 255) / 256;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    if (workgroups) *workgroups = (uint32_t)grid;
+    if (p.map == TV_V2_MAP_PIECE)
+        hipLaunchKernelGGL((tv_v2_leaf_kernel<TV_V2_MAP_PIECE>), dim3((unsigned)grid), dim3(256), 0, s, p);
+    else
+        hipLaunchKernelGGL((tv_v2_leaf_kernel<TV_V2_MAP_LEAF>), dim3((unsigned)grid), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t tv_v2_launch_level(const TvV2& p, uint32_t level, uint32_t maxlog, hipStream_t s) {
+    if (p.n == 0 || level >= maxlog) return hipSuccess;
+    const uint32_t log_half = maxlog - level - 1;
+    const uint64_t grid = (((uint64_t)p.n << log_half) + 255) / 256;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(tv_v2_level_kernel, dim3((unsigned)grid), dim3(256), 0, s, p, level, log_half);
+    return hipGetLastError();
+}
+
+hipError_t tv_v2_launch_finish(const TvV2& p, bool hash, hipStream_t s) {
+    if (p.n == 0) return hipSuccess;
+    const dim3 grid((p.n + 255) / 256);
+    if (hash) hipLaunchKernelGGL((tv_v2_finish_kernel<true>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((tv_v2_finish_kernel<false>), grid, dim3(256), 0, s, p);
+    return hipGetLastError();
+}

@@ -54,6 +54,11 @@ const SYMBOLS = {
   },
   tv_verify_list: { parameters: ["pointer", "pointer", "u64", "pointer"], result: "i32", nonblocking: true },
   tv_hash: { parameters: ["pointer", "pointer"], result: "i32", nonblocking: true },
+  // BitTorrent v2 (SHA-256 merkle piece roots): bound so that the table covers the header; a TS host function for v2
+  // (the counterpart of torrent_amd/v2.py) is not part of this module yet.
+  tv_v2_set_pieces: { parameters: ["pointer", "u64", "pointer", "pointer", "pointer"], result: "i32" },
+  tv_v2_verify: { parameters: ["pointer", "pointer", "pointer"], result: "i32", nonblocking: true },
+  tv_v2_hash: { parameters: ["pointer", "pointer"], result: "i32", nonblocking: true },
   tv_stream_begin: { parameters: ["pointer", "pointer"], result: "i32" },
   tv_stream_next: { parameters: ["pointer", "pointer"], result: "i32", nonblocking: true },
   tv_stream_commit: { parameters: ["pointer", "pointer"], result: "i32", nonblocking: true },
