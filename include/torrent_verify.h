@@ -288,12 +288,31 @@ int tv_hash(tv_ctx *ctx, uint8_t *digests_out);
  * every resident piece, in piece order (creation mode: a file's `piece layers` entry, or its `pieces root` when it
  * is one piece; the host reduces a longer file's layer to its `pieces root`).  tv_last_timing, tv_last_kernel
  * (kernel id 8) and TV_COUNTER_LAST_WORKGROUPS (the leaf kernel's grid) report on them.
+ *
+ * tv_v2_verify_list: a LIST of v2 pieces in ONE launch (incremental verify on piece completion, as tv_verify_list
+ * for v1).  The entries describe themselves, so no tv_v2_set_pieces and no tv_set_digests is needed, and an
+ * incremental host hands over only what its pending pieces need: entry k is GLOBAL piece pieces[k] of this ctx's
+ * shard (any order, duplicates allowed) with piece_bytes[k] valid bytes, a tree of tree_leaves[k] leaves (the ranges
+ * of tv_v2_set_pieces) and the expected root hashes[32 k ..]; ok_out[k] = 1 iff the merkle root of the piece's
+ * resident bytes equals it.  On a whole-shard resident layout the piece's row is read; on a slot pool
+ * (TV_OPT_LIST_SLOTS) its slot, with tv_verify_list's rules: a listed piece without a slot (never staged) is 0, and
+ * every listed piece's slot is free again when the call returns.  Bytes past piece_bytes[k] in a row or slot (a
+ * previous occupant's) are never read into a hash.  Pieces marked unreadable by tv_stage_file(s) are 0.  n == 0 is
+ * TV_OK.  Each piece's tree is reduced inside one workgroup (leaf hashes and levels in on-chip memory), so the call
+ * holds no node buffers: device memory is 48 bytes per listed entry (at least 1,024 entries), reused by later calls
+ * of the same or a smaller n.  Piece lengths up to 1 GiB (65,536 leaves).
+ * TV_ERR_ARG: NULL arguments with n > 0, a piece outside the shard, piece_length not a power of two >= 16 KiB or
+ * > 1 GiB, a piece_bytes / tree_leaves entry outside the ranges above.  TV_ERR_STATE: before tv_set_layout, on a
+ * windowed layout, with TV_OPT_RESIDENT = 0, during a stream.  A refused call frees no slot.  tv_last_timing,
+ * tv_last_kernel (kernel id 16, one launch) and TV_COUNTER_LAST_WORKGROUPS report on it.
  */
 #define TV_V2_LEAF_BYTES 16384
 int tv_v2_set_pieces(tv_ctx *ctx, uint64_t n, const uint32_t *piece_bytes, const uint32_t *tree_leaves,
                      const uint8_t *hashes);
 int tv_v2_verify(tv_ctx *ctx, const uint8_t *avail_bits, uint8_t *bitfield_out);
 int tv_v2_hash(tv_ctx *ctx, uint8_t *roots_out);
+int tv_v2_verify_list(tv_ctx *ctx, uint64_t n, const uint64_t *pieces, const uint32_t *piece_bytes,
+                      const uint32_t *tree_leaves, const uint8_t *hashes /* 32*n */, uint8_t *ok_out);
 
 /*
  * Streamed verify through a BOUNDED pinned ring (end-to-end resume check, SURVEY 8d cfg5: the
@@ -406,7 +425,8 @@ int tv_get_option(tv_ctx *ctx, int key, int64_t *value);
  * library's compute stream: kernel_ms = the verify kernel(s) only; total_ms = whole call. */
 int tv_last_timing(tv_ctx *ctx, double *kernel_ms, double *total_ms);
 
-/* Kernel chosen for the last call (1 lane, 2 split, 4 twin; 8 = the v2 SHA-256 merkle kernels) and launches it used. */
+/* Kernel chosen for the last call (1 lane, 2 split, 4 twin; 8 = the v2 SHA-256 merkle kernels, 16 = the v2 list
+ * kernel) and launches it used. */
 int tv_last_kernel(tv_ctx *ctx, int *kernel, int *launches);
 
 /* Resource counters of a ctx (tv_get_counter keys): how often tv_set_layout and the calls after it had to

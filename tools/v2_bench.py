@@ -4,6 +4,15 @@ tv_verify (SHA-1) on the same resident bytes, hashlib SHA-256 on this host's cor
 lane mappings (TV_OPT_V2_MAP), alternated step by step.
 
     python tools/v2_bench.py [--steps 10] [--warmup 3] [--out profiles/v2/v2_bench.json]
+    python tools/v2_bench.py --list [--parent-json FILE] [--out profiles/v2/list_latency.json]
+    python tools/v2_bench.py --list-resident-only [--out FILE]
+
+--list is the incremental-verify leg: the flush time of tv_v2_verify_list (one launch, the trees in LDS) for 1 / 64 /
+4,096 pieces of 256 KiB and 1 / 64 / 1,024 pieces of 4 MiB, against (a) tv_verify_list (SHA-1) on the same bytes and
+(b) the resident tv_v2_verify over the same pieces (leaf launch + one launch per level + finish).  Medians of 10 after
+2 warm-ups.  --list-resident-only runs (b) alone and uses nothing newer than tv_v2_verify, so a copy of this tool
+beside an older build of the package measures that build; --parent-json takes its output as (b).  Acceptance: at the
+largest list of each size the fused kernel_ms is at most (b)'s times (b)'s own max / min spread (at least 1.05).
 
 Times are the library's HIP events around the kernels (tv_last_timing); the shader clock is the clock probe's
 (TV_OPT_CLOCK_PROBE).  The expected hashes come from tv_v2_hash, and a sample of pieces read back with tv_read is
@@ -104,8 +113,97 @@ def shape(ctx, name: str, total: int, L: int, steps: int, warmup: int, sample: i
     return out
 
 
+LIST_SHAPES = ((256 << 10, (1, 64, 4096)), (4 << 20, (1, 64, 1024)))
+LIST_STEPS, LIST_WARMUP = 10, 2
+
+
+def _stats(kernel, total) -> dict:
+    return {"kernel_ms": round(statistics.median(kernel), 4), "total_ms": round(statistics.median(total), 4),
+            "kernel_ms_min": round(min(kernel), 4), "kernel_ms_max": round(max(kernel), 4)}
+
+
+def _timed(ctx, call, check) -> dict:
+    kernel, total = [], []
+    for step in range(LIST_WARMUP + LIST_STEPS):
+        assert check(call()), "a timed call's result is wrong"
+        if step >= LIST_WARMUP:
+            k, t = ctx.last_timing()
+            kernel.append(k)
+            total.append(t)
+    return _stats(kernel, total)
+
+
+def list_legs(ctx, resident_only: bool) -> list:
+    """Per (piece length, list length): n resident pieces of the synthetic payload, their roots from tv_v2_hash (one
+    checked against hashlib), then the timed legs on those bytes."""
+    out = []
+    for L, counts in LIST_SHAPES:
+        W = L // LEAF
+        for n in counts:
+            ctx.set_layout(n * L, L, n)
+            ctx.fill_synthetic(5)
+            ctx.v2_set_pieces([L] * n, [W] * n, None)
+            roots = ctx.v2_hash()
+            buf = bytearray(L)
+            ctx.read((n - 1) * L, buf)
+            assert roots[-32:] == merkle_root(bytes(buf), W), "the last piece differs from hashlib"
+            ctx.v2_set_pieces([L] * n, [W] * n, roots)
+            row = {"piece_length": L, "pieces": n, "serial_compressions": 257 + 2 * (W.bit_length() - 1)}
+            all_ones = bytes([0xFF] * (n // 8)) + (bytes([0xFF00 >> (n % 8) & 0xFF]) if n % 8 else b"")
+            row["resident_v2_verify"] = dict(_timed(ctx, ctx.v2_verify, lambda b: b == all_ones),
+                                             launches=ctx.last_kernel()[1])
+            if not resident_only:
+                pieces = list(range(n))
+                row["v2_verify_list"] = dict(
+                    _timed(ctx, lambda: ctx.v2_verify_list(pieces, [L] * n, [W] * n, roots),
+                           lambda ok: ok == b"\x01" * n),
+                    launches=ctx.last_kernel()[1], workgroups=ctx.counter(N.TV_COUNTER_LAST_WORKGROUPS))
+                ctx.set_digests(ctx.hash())
+                row["sha1_verify_list"] = dict(_timed(ctx, lambda: ctx.verify_list(pieces), lambda ok: ok == b"\x01" * n),
+                                               kernel=ctx.last_kernel()[0])
+            out.append(row)
+    return out
+
+
+def list_main(a) -> int:
+    res = {"build_id": N.build_id(), "steps": LIST_STEPS, "warmup": LIST_WARMUP}
+    with N.Context(0) as ctx:
+        res["rows"] = list_legs(ctx, a.list_resident_only)
+    if a.list and a.parent_json:
+        with open(a.parent_json) as f:
+            parent = json.load(f)
+        res["parent_build_id"] = parent["build_id"]
+        by = {(r["piece_length"], r["pieces"]): r["resident_v2_verify"] for r in parent["rows"]}
+        for r in res["rows"]:
+            r["resident_v2_verify_parent_build"] = by[(r["piece_length"], r["pieces"])]
+    if a.list:
+        res["acceptance"] = []
+        for L, counts in LIST_SHAPES:
+            r = next(x for x in res["rows"] if x["piece_length"] == L and x["pieces"] == counts[-1])
+            b = r.get("resident_v2_verify_parent_build") or r["resident_v2_verify"]
+            spread = max(1.05, b["kernel_ms_max"] / b["kernel_ms_min"])
+            res["acceptance"].append({
+                "piece_length": L, "pieces": counts[-1], "fused_kernel_ms": r["v2_verify_list"]["kernel_ms"],
+                "resident_kernel_ms": b["kernel_ms"], "resident_spread": round(spread, 4),
+                "resident_from": "parent build" if "resident_v2_verify_parent_build" in r else "this build",
+                "bound_ms": round(b["kernel_ms"] * spread, 4),
+                "pass": r["v2_verify_list"]["kernel_ms"] <= b["kernel_ms"] * spread})
+        for r in res["rows"]:
+            if r["pieces"] == 1:   # reported, not gated
+                r["single_piece_sha1_over_v2"] = round(r["sha1_verify_list"]["kernel_ms"] / r["v2_verify_list"]["kernel_ms"], 2)
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--list", action="store_true", help="the incremental-verify leg (see the module docstring)")
+    ap.add_argument("--list-resident-only", action="store_true", help="leg (b) of --list alone")
+    ap.add_argument("--parent-json", default=None, help="--list: a --list-resident-only output to take (b) from")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cfg2-gib", type=int, default=16)
@@ -115,6 +213,8 @@ def main() -> int:
     a = ap.parse_args()
     if N.device_count() == 0:
         raise SystemExit("no HIP device visible: this measures the GPU")
+    if a.list or a.list_resident_only:
+        return list_main(a)
     res = {"R_valu_sha256_GBps_2400": round(R_VALU_256, 1), "cycles_per_block": CYCLES_PER_BLOCK,
            "build_id": N.build_id(), "steps": a.steps, "warmup": a.warmup, "shapes": []}
     with N.Context(0) as ctx:
@@ -126,7 +226,7 @@ def main() -> int:
         ctx.read(0, host)
         res["cpu_sha256"] = {"threads": threads, "bytes": len(host), "GBps": round(cpu_sha256(host, threads), 2)}
         del host
-        gib = a.cfg4_gib
+        gib = a.cfg4_gib                          # (0: cfg2 alone)
         while gib >= 8:                            # cfg4's piece geometry at whatever fits resident
             try:
                 ctx.set_layout(gib << 30, 4 << 20, (gib << 30) >> 22)
@@ -136,7 +236,8 @@ def main() -> int:
                 if e.code != N.TV_ERR_NOMEM:
                     raise
             gib //= 2
-        res["shapes"].append(shape(ctx, f"cfg4_geometry_{gib}GiB", gib << 30, 4 << 20, a.steps, a.warmup, 4, True))
+        if gib >= 8:
+            res["shapes"].append(shape(ctx, f"cfg4_geometry_{gib}GiB", gib << 30, 4 << 20, a.steps, a.warmup, 4, True))
     best = max(m["GBps"] for m in res["shapes"][0]["mappings"].values())
     res["gpu_beats_cpu"] = best > res["cpu_sha256"]["GBps"]
     line = json.dumps(res)

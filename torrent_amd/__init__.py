@@ -12,7 +12,8 @@ from .storage import FsStorage, MemoryStorage, Storage, fs_storage  # noqa: F401
 from .verify import (context_counters, hash_files, hash_pieces, release_contexts, shard_ranges,  # noqa: F401
                      verify_files, verify_payload, verify_piece, verify_piece_async, verify_pieces,
                      verify_pieces_async, verify_stream)
-from .incremental import IncrementalVerifier  # noqa: F401
+from .incremental import (IncrementalVerifier, IncrementalVerifierV2, flush_cost_ms_v2,  # noqa: F401
+                          validate_received_block_v2)
 from .make_torrent import make_torrent  # noqa: F401
 from .metainfo_v2 import FileV2, MetainfoV2, V2Layout, parse_metainfo_v2  # noqa: F401
 from .v2 import (hash_files_v2, make_torrent_v2, verify_files_v2, verify_payload_v2,  # noqa: F401
@@ -27,4 +28,5 @@ __all__ = [
     "IncrementalVerifier", "make_torrent",
     "bdecode_raw", "FileV2", "MetainfoV2", "V2Layout", "parse_metainfo_v2", "hash_files_v2", "make_torrent_v2",
     "verify_files_v2", "verify_payload_v2", "verify_piece_v2",
+    "IncrementalVerifierV2", "flush_cost_ms_v2", "validate_received_block_v2",
 ]

@@ -85,6 +85,7 @@ TV_STREAM_SLOT_BYTES = 64 << 20
 
 KERNEL_AUTO, KERNEL_LANE, KERNEL_SPLIT, KERNEL_TWIN = 0, 1, 2, 4   # (3 was MIX, removed)
 KERNEL_V2 = 8   # tv_last_kernel after tv_v2_verify / tv_v2_hash
+KERNEL_V2_LIST = 16   # tv_last_kernel after tv_v2_verify_list
 
 _u64, _i64, _int, _p = ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
 
@@ -133,6 +134,7 @@ SYMBOLS = [
     ("tv_v2_set_pieces", _int, [_p, _u64, _p, _p, _p]),
     ("tv_v2_verify", _int, [_p, _p, _p]),
     ("tv_v2_hash", _int, [_p, _p]),
+    ("tv_v2_verify_list", _int, [_p, _u64, _p, _p, _p, _p, _p]),
     ("tv_stream_begin", _int, [_p, _p]),
     ("tv_stream_next", _int, [_p, _REQ]),
     ("tv_stream_commit", _int, [_p, _REQ]),
@@ -585,6 +587,27 @@ class Context:
         out = ctypes.create_string_buffer(max(1, 32 * self.shard_count))
         self._check(self._L.tv_v2_hash(self._h, out))
         return out.raw[: 32 * self.shard_count]
+
+    def v2_verify_list(self, pieces, piece_bytes, tree_leaves, hashes) -> bytes:
+        """tv_v2_verify_list: one byte (0/1) per listed entry: GLOBAL piece pieces[k] with piece_bytes[k] valid
+        bytes, a merkle tree of tree_leaves[k] leaves and the expected root hashes[32 k : 32 k + 32]."""
+        import numpy as np
+        pc = np.ascontiguousarray(pieces, dtype=np.uint64)
+        pb = np.ascontiguousarray(piece_bytes, dtype=np.uint32)
+        tl = np.ascontiguousarray(tree_leaves, dtype=np.uint32)
+        n = len(pc)
+        if len(pb) != n or len(tl) != n:
+            raise ValueError("v2_verify_list: pieces, piece_bytes and tree_leaves differ in length")
+        if memoryview(hashes).nbytes != 32 * n:
+            raise ValueError("v2_verify_list: hashes must hold 32 bytes per entry")
+        if n == 0:
+            self._check(self._L.tv_v2_verify_list(self._h, 0, None, None, None, None, None))
+            return b""
+        a, keep = _addr(hashes)
+        out = ctypes.create_string_buffer(n)
+        self._check(self._L.tv_v2_verify_list(self._h, n, pc.ctypes.data, pb.ctypes.data, tl.ctypes.data, a, out))
+        del keep
+        return out.raw[:n]
 
     def last_timing(self) -> tuple:
         k, t = ctypes.c_double(0), ctypes.c_double(0)

@@ -2,7 +2,7 @@
 // translation units share.  tv_context.hip: lifecycle, options, layout, digests, counters; tv_core.hip: errors, NUMA,
 // staging rings, windows, slot pool, kernel choice, the host -> HBM copy path; tv_stage.hip: staging from memory;
 // tv_files.hip: staging from files; tv_stream.hip: the streamed engine; tv_verify.hip: verify / list / hash;
-// tv_v2.hip: the BitTorrent v2 piece table, verify and hash.
+// tv_v2.hip: the BitTorrent v2 piece table, verify, hash and list verify.
 // Nothing here is exported (the link exports tv_* only: exports.map).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -322,6 +322,8 @@ struct tv_ctx {
     uint32_t* d_v2_nodes = nullptr;    // level buffers A [8][count x W] then B [8][count x max(W/2, 1)]
     uint64_t cap_v2_count = 0;         // pieces of d_v2_tab
     uint64_t cap_v2_nodes = 0;         // words of d_v2_nodes
+    uint32_t* d_v2_list = nullptr;     // tv_v2_verify_list: [11][m] rows, bytes, widths, expected [8], then v2_list_cap out bytes
+    uint64_t v2_list_cap = 0;          // entries of d_v2_list (48 bytes each)
     int v2_map_opt = 0;                // TV_OPT_V2_MAP: 0 auto, else TV_V2_MAP_*
     int v2_last_map = 0;               // the mapping the last v2 call's leaf kernel ran with
 

@@ -86,6 +86,24 @@ hipError_t tv_v2_launch_level(const TvV2& p, uint32_t level, uint32_t maxlog, hi
 // Roots: compare with `expect` and the availability into out64 (hash = false), or copy them to `roots`.
 hipError_t tv_v2_launch_finish(const TvV2& p, bool hash, hipStream_t s);
 
+// ---- the v2 list launch (tv_v2_verify_list): m self-describing entries, one kernel, no node buffers ---------------
+#define TV_KERNEL_V2_LIST 16      // tv_last_kernel id of tv_v2_verify_list (tv_v2_list_kernel, one launch)
+#define TV_V2_LIST_MAX_LOGW 16    // W up to 65,536 leaves (1 GiB pieces): the tile roots of one piece fill one LDS row
+// Entry e's bytes are payload row rows[e] (data + rows[e] * stride): bytes[e] valid bytes, a tree of widths[e] leaves,
+// the expected root in expect[q * m + e] (q = 0 .. 7, big-endian values).  out_bytes[e] = 1 iff the root matches.
+struct TvV2List {
+    const uint8_t* data;
+    uint64_t stride;
+    uint32_t m;                  // entries
+    uint32_t logW;               // W = L / 16 KiB = 1 << logW: the widest tree an entry may have
+    const uint32_t* rows;        // [m]
+    const uint32_t* bytes;       // [m] 1 .. L
+    const uint32_t* widths;      // [m] a power of two, ceil(bytes / 16 KiB) .. W
+    const uint32_t* expect;      // [8][m]
+    uint8_t* out_bytes;          // [m]
+};
+hipError_t tv_v2_launch_list(const TvV2List& p, hipStream_t s, uint32_t* workgroups);
+
 // workgroups (optional): set to the launch's grid size, companions included.
 hipError_t tv_launch_verify(const TvPieces& p, int kernel, bool hash, hipStream_t s, int split_pairs = 0,
                             uint32_t* workgroups = nullptr);

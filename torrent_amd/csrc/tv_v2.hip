@@ -1,6 +1,7 @@
 // tv_v2.hip -- BitTorrent v2 (BEP 52): the piece table of a layout (tv_v2_set_pieces) and the SHA-256 merkle verify
 // and hash calls over the resident shard (tv_v2_verify, tv_v2_hash): one leaf launch, one launch per tree level, one
-// finish launch (tv_v2_kernels.hip).
+// finish launch (tv_v2_kernels.hip); and the list verify of self-describing entries over a resident shard or a slot
+// pool (tv_v2_verify_list): one launch, the trees in LDS.
 #include <cstring>
 
 #include "tv_ctx.h"
@@ -9,11 +10,21 @@ using namespace tvi;
 
 namespace tvi {
 
-void free_v2(tv_ctx* c) {
+static void free_v2_table(tv_ctx* c) {
     (void)hipFree(c->d_v2_tab); c->d_v2_tab = nullptr;
     (void)hipFree(c->d_v2_nodes); c->d_v2_nodes = nullptr;
     c->cap_v2_count = c->cap_v2_nodes = 0;
     c->v2_set = c->v2_hashes = false;
+}
+
+static void free_v2_list(tv_ctx* c) {
+    (void)hipFree(c->d_v2_list); c->d_v2_list = nullptr;
+    c->v2_list_cap = 0;
+}
+
+void free_v2(tv_ctx* c) {
+    free_v2_table(c);
+    free_v2_list(c);
 }
 
 static bool v2_piece_length_ok(uint64_t L) { return L >= TV_V2_LEAF_BYTES && (L & (L - 1)) == 0; }
@@ -23,12 +34,13 @@ static uint64_t v2_node_words(uint64_t count, uint64_t W) { return 8 * count * (
 
 void v2_on_layout(tv_ctx* c) {
     c->v2_set = c->v2_hashes = false;
+    if (c->v2_list_cap > std::max<uint64_t>(1024, 2 * c->count)) free_v2_list(c);   // (as tv_verify_list's buffers)
     if (!c->d_v2_tab && !c->d_v2_nodes) return;
     // keep what a v2 table of the new geometry would reuse; anything else goes (a v1 layout holds no v2 memory)
     const bool v2 = v2_piece_length_ok(c->L) && c->count && !c->win && !c->slots;
     if (!v2 || !reuse_fits(c->count, c->cap_v2_count) ||
         !reuse_fits(v2_node_words(c->count, c->L / TV_V2_LEAF_BYTES), c->cap_v2_nodes))
-        free_v2(c);
+        free_v2_table(c);
 }
 
 }  // namespace tvi
@@ -223,6 +235,115 @@ int tv_v2_hash(tv_ctx* c, uint8_t* roots_out) {
             uint8_t* d = roots_out + 32 * j + 4 * k;
             d[0] = (uint8_t)(v >> 24); d[1] = (uint8_t)(v >> 16); d[2] = (uint8_t)(v >> 8); d[3] = (uint8_t)v;
         }
+    return finish_timing(c);
+}
+
+int tv_v2_verify_list(tv_ctx* c, uint64_t n, const uint64_t* pieces, const uint32_t* piece_bytes,
+                      const uint32_t* tree_leaves, const uint8_t* hashes, uint8_t* ok_out) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = require_layout(c, false, true);
+    if (rc) return rc;
+    if (c->win)
+        return fail(c, TV_ERR_STATE, "tv_v2_verify_list needs the shard resident or a slot pool (TV_OPT_LIST_SLOTS); "
+                                     "this layout is windowed (the shard exceeds the device budget)");
+    if (n == 0) return TV_OK;
+    if (!pieces || !piece_bytes || !tree_leaves || !hashes || !ok_out) return fail(c, TV_ERR_ARG, "NULL argument");
+    if (n >= 0xFFFFFF00ull) return fail(c, TV_ERR_ARG, "list too long");
+    if (!v2_piece_length_ok(c->L))
+        return fail(c, TV_ERR_ARG, "a v2 piece length is a power of two >= %d (the layout has %llu)", TV_V2_LEAF_BYTES,
+                    (unsigned long long)c->L);
+    const uint64_t W = c->L / TV_V2_LEAF_BYTES;
+    if (W > (1ull << TV_V2_LIST_MAX_LOGW))
+        return fail(c, TV_ERR_ARG, "tv_v2_verify_list takes pieces of up to %llu bytes (the layout has %llu)",
+                    (unsigned long long)TV_V2_LEAF_BYTES << TV_V2_LIST_MAX_LOGW, (unsigned long long)c->L);
+    // every entry is checked before anything is launched or freed: a refused call changes nothing
+    for (uint64_t k = 0; k < n; k++) {
+        if (pieces[k] < c->first || pieces[k] >= c->first + c->count)
+            return fail(c, TV_ERR_ARG, "piece %llu is not in this context's shard [%llu, %llu)",
+                        (unsigned long long)pieces[k], (unsigned long long)c->first,
+                        (unsigned long long)(c->first + c->count));
+        const uint64_t b = piece_bytes[k], w = tree_leaves[k];
+        if (b == 0 || b > c->L)
+            return fail(c, TV_ERR_ARG, "piece_bytes[%llu] = %llu is outside 1 .. %llu", (unsigned long long)k,
+                        (unsigned long long)b, (unsigned long long)c->L);
+        if (w == 0 || (w & (w - 1)) || w < (b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES || w > W)
+            return fail(c, TV_ERR_ARG, "tree_leaves[%llu] = %llu is not a power of two in %llu .. %llu",
+                        (unsigned long long)k, (unsigned long long)w,
+                        (unsigned long long)((b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES), (unsigned long long)W);
+    }
+    // The entries launched: every listed piece, or, in a slot pool, the listed pieces that hold a slot (the others
+    // were never staged: 0).  origin[e] = the entry's index in the caller's arrays.
+    std::vector<uint64_t> origin;
+    origin.reserve(n);
+    for (uint64_t k = 0; k < n; k++) {
+        if (!c->slots || c->slot_of.count(pieces[k] - c->first)) origin.push_back(k);
+        else ok_out[k] = 0;
+    }
+    const uint64_t m = origin.size();
+    std::vector<uint32_t> tab(11 * m);   // rows, bytes, widths, expected root words [8][m] (big-endian values)
+    for (uint64_t e = 0; e < m; e++) {
+        const uint64_t k = origin[e], j = pieces[k] - c->first;
+        tab[e] = c->slots ? c->slot_of.find(j)->second : (uint32_t)j;
+        tab[m + e] = piece_bytes[k];
+        tab[2 * m + e] = tree_leaves[k];
+        const uint8_t* d = hashes + 32 * k;
+        for (int q = 0; q < 8; q++)
+            tab[(3 + (uint64_t)q) * m + e] = ((uint32_t)d[4 * q] << 24) | ((uint32_t)d[4 * q + 1] << 16) |
+                                             ((uint32_t)d[4 * q + 2] << 8) | (uint32_t)d[4 * q + 3];
+    }
+    std::vector<uint8_t> ok_launch(m);
+    TV_HIP(c, hipSetDevice(c->device));
+    if (m) {
+        DrainGuard drain(c);  // after the host vectors: their H2D / D2H copies end before they go
+        if (c->v2_list_cap < m) {
+            free_v2_list(c);
+            const uint64_t cap = std::max<uint64_t>(m, 1024);
+            TV_HIP(c, hipMalloc((void**)&c->d_v2_list, cap * 48));   // 11 table words and 4 out bytes per entry
+            c->v2_list_cap = cap;
+            c->n_device_allocs++;
+        }
+        uint8_t* d_ok = reinterpret_cast<uint8_t*>(c->d_v2_list + 11 * c->v2_list_cap);
+        TV_HIP(c, hipEventRecord(c->ev_call0, c->stream));
+        TV_HIP(c, hipMemcpyAsync(c->d_v2_list, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+        // fail closed: an entry the launch does not write reads as 0
+        TV_HIP(c, hipMemsetAsync(d_ok, 0, m, c->stream));
+        TvV2List p{};
+        p.data = c->d_payload;
+        p.stride = c->stride;
+        p.m = (uint32_t)m;
+        while ((1ull << p.logW) < W) p.logW++;
+        p.rows = c->d_v2_list;
+        p.bytes = c->d_v2_list + m;
+        p.widths = c->d_v2_list + 2 * m;
+        p.expect = c->d_v2_list + 3 * m;
+        p.out_bytes = d_ok;
+        TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
+        TV_HIP(c, tv_v2_launch_list(p, c->stream, &c->last_workgroups));
+        TV_HIP(c, hipEventRecord(c->ev_k1, c->stream));
+        TV_HIP(c, hipMemcpyAsync(ok_launch.data(), d_ok, m, hipMemcpyDeviceToHost, c->stream));
+        TV_HIP(c, hipEventRecord(c->ev_call1, c->stream));
+        TV_HIP(c, hipEventSynchronize(c->ev_call1));
+    } else {
+        c->last_workgroups = 0;
+    }
+    for (uint64_t e = 0; e < m; e++) ok_out[origin[e]] = ok_launch[e];
+    if (c->any_file_bad)  // pieces file staging could not read are 0 here too
+        for (uint64_t k = 0; k < n; k++)
+            if (get_bit(c->file_bad.data(), pieces[k] - c->first)) ok_out[k] = 0;
+    if (c->slots)  // a listed piece's slot is free again (a failed piece is staged anew when it is re-downloaded)
+        for (uint64_t k = 0; k < n; k++) {
+            auto it = c->slot_of.find(pieces[k] - c->first);
+            if (it == c->slot_of.end()) continue;
+            c->slot_free.push_back(it->second);
+            c->slot_of.erase(it);
+        }
+    c->last_kernel = TV_KERNEL_V2_LIST;
+    c->last_launches = m ? 1 : 0;
+    if (!m) {
+        c->kernel_ms = c->total_ms = 0.f;
+        return TV_OK;
+    }
     return finish_timing(c);
 }
 

@@ -12,6 +12,8 @@
 //   level kernel  : one launch per tree level, one lane per parent node; the levels ping-pong between A and B.
 //   finish kernel : one lane per piece: the root against the expected hash and the availability bit -> MSB-first
 //                   bitfield words (as tv_compare_kernel), or the root out (creation mode).
+//   list kernel   : tv_v2_verify_list's single launch: the leaf hashing above, then the piece's tree levels in LDS
+//                   inside the workgroup, root against the entry's expected hash -> one byte per entry.
 // Which lane hashes which leaf (TvV2::map): consecutive leaves of a piece (addresses 16 KiB apart), or one leaf index
 // of 64 consecutive pieces (addresses `stride` apart, the layout the SHA-1 lane kernel reads).
 #include <hip/hip_runtime.h>
@@ -54,6 +56,57 @@ __device__ __forceinline__ void bswap_block(const uint4 (&r)[4], uint32_t w[16])
     }
 }
 
+// SHA-256 of the `len` (1 .. 16,384) bytes at `leaf` into h, for the lanes with `active` set; the other lanes of the
+// wave hash nothing and get no h.  EVERY lane of the wave calls it (the block ranges below are wave reductions).
+// Raw blocks load kDepth ahead into registers (load_block); the padded tail goes through build_tail_block.
+__device__ __forceinline__ void hash_leaf(const uint8_t* leaf, uint32_t len, bool active, uint32_t h[8]) {
+    // wave-uniform block ranges over the wave's hashing lanes: [0, fast_end) are raw data for every one of them,
+    // [fast_end, end) go the padded-block way with the lanes past their last block masked
+    const uint32_t nb = active ? (uint32_t)nblocks(len) : 0;
+    const uint32_t fast_end = wave_min(active ? len >> 6 : 0xFFFFFFFFu);
+    const uint32_t end = wave_max(nb);
+    if (active) {
+        uint32_t w[16];
+        tv256::iv(h);
+        uint32_t b = 0;
+        if (b < fast_end) {
+            // loads are unconditional (the block index is clamped to the last raw block), so they are never
+            // predicated and stay in flight across a block
+            const uint32_t last = fast_end - 1;
+            uint4 R[kDepth][4];
+#pragma unroll
+            for (int d = 0; d < kDepth; d++) load_block(leaf, b + d < last ? b + d : last, R[d]);
+            for (;;) {
+#pragma unroll
+                for (int d = 0; d < kDepth; d++) {
+                    bswap_block(R[d], w);
+                    load_block(leaf, b + kDepth < last ? b + kDepth : last, R[d]);
+                    tv256::compress(h, w, h);
+                    if (++b >= fast_end) goto raw_done;
+                }
+            }
+        }
+    raw_done:
+        for (; b < end; b++) {
+            build_tail_block(leaf, len, b, w);
+            uint32_t r[8];
+            tv256::compress(h, w, r);
+            if (b < nb) {
+#pragma unroll
+                for (int i = 0; i < 8; i++) h[i] = r[i];
+            }
+        }
+    }
+}
+
+// An interior node: h = SHA-256(left || right), the 16 words of the two children in w (consumed).
+__device__ __forceinline__ void hash_pair(uint32_t w[16], uint32_t h[8]) {
+    tv256::iv(h);
+    tv256::compress(h, w, h);
+    uint32_t pad[16] = {0x80000000u, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 512u};   // a 64-byte message's padding
+    tv256::compress(h, pad, h);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -91,43 +144,9 @@ __global__ __launch_bounds__(256) void tv_v2_leaf_kernel(TvV2 p) {
 #pragma unroll
         for (int q = 0; q < 8; q++) p.nodes_a[q * np + slot] = 0;
     }
-    // wave-uniform block ranges over the wave's hashing lanes: [0, fast_end) are raw data for every one of them,
-    // [fast_end, end) go the padded-block way with the lanes past their last block masked
-    const uint32_t nb = active ? (uint32_t)nblocks(len) : 0;
-    const uint32_t fast_end = wave_min(active ? len >> 6 : 0xFFFFFFFFu);
-    const uint32_t end = wave_max(nb);
+    uint32_t h[8];
+    hash_leaf(p.data + j * p.stride + lo, len, active, h);
     if (active) {
-        const uint8_t* leaf = p.data + j * p.stride + lo;
-        uint32_t h[8], w[16];
-        tv256::iv(h);
-        uint32_t b = 0;
-        if (b < fast_end) {
-            // loads are unconditional (the block index is clamped to the last raw block), so they are never
-            // predicated and stay in flight across a block
-            const uint32_t last = fast_end - 1;
-            uint4 R[kDepth][4];
-#pragma unroll
-            for (int d = 0; d < kDepth; d++) load_block(leaf, b + d < last ? b + d : last, R[d]);
-            for (;;) {
-#pragma unroll
-                for (int d = 0; d < kDepth; d++) {
-                    bswap_block(R[d], w);
-                    load_block(leaf, b + kDepth < last ? b + kDepth : last, R[d]);
-                    tv256::compress(h, w, h);
-                    if (++b >= fast_end) goto raw_done;
-                }
-            }
-        }
-    raw_done:
-        for (; b < end; b++) {
-            build_tail_block(leaf, len, b, w);
-            uint32_t r[8];
-            tv256::compress(h, w, r);
-            if (b < nb) {
-#pragma unroll
-                for (int i = 0; i < 8; i++) h[i] = r[i];
-            }
-        }
 #pragma unroll
         for (int q = 0; q < 8; q++) p.nodes_a[q * np + slot] = h[q];
     }
@@ -200,6 +219,102 @@ __global__ __launch_bounds__(256) void tv_v2_finish_kernel(TvV2 p) {
 }
 
 // ------------------------------------------------------------------------------------------
+// list kernel (tv_v2_verify_list): a piece's whole tree in one workgroup, its nodes in LDS.
+//   W <= 256: a workgroup covers G = 256 / W consecutive list entries, one lane per leaf position (one tile).
+//   W  > 256: a workgroup owns one entry and walks it in W / 256 tiles of 256 leaves; each tile is reduced to its
+//             subtree root (8 levels), the roots collect in s_root, and that array is reduced at the end.
+// A level is compacted: parent t = SHA-256(node 2t || node 2t + 1) of the 256-node row, written back to position t, so
+// level l keeps 256 >> (l + 1) consecutive lanes (whole waves) busy.  An entry's root is node 0 of its segment after
+// log2(w) levels: the lane that computes it compares it with the expected words and writes out_bytes[e].
+// Every loop that holds a barrier runs on logW alone (workgroup-uniform); lanes with no leaf (a padding position, an
+// entry past m) skip the hashing, never a barrier, and no lane returns early.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+__device__ __forceinline__ void list_emit(const TvV2List& p, uint32_t e, const uint32_t h[8]) {
+    bool ok = true;
+#pragma unroll
+    for (int q = 0; q < 8; q++) ok &= h[q] == p.expect[(uint64_t)q * p.m + e];
+    p.out_bytes[e] = ok ? 1 : 0;
+}
+
+// One compacted level of the 256-node row `s`: lanes [0, parents) each hash one pair.  Returns true in those lanes,
+// with the parent in h.
+__device__ __forceinline__ bool list_level(uint32_t (&s)[8][256], uint32_t t, uint32_t parents, uint32_t h[8]) {
+    const bool par = t < parents;
+    uint32_t w[16];
+    if (par) {
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const uint2 v = *reinterpret_cast<const uint2*>(&s[q][2 * t]);
+            w[q] = v.x;       // word q of the left child
+            w[8 + q] = v.y;   // word q of the right child
+        }
+    }
+    __syncthreads();   // every pair is read before a parent overwrites a child of another lane's pair
+    if (par) {
+        hash_pair(w, h);
+#pragma unroll
+        for (int q = 0; q < 8; q++) s[q][t] = h[q];
+    }
+    __syncthreads();
+    return par;
+}
+
+}  // namespace
+
+// TILED = W > 256 (the launcher's choice), and only the tile loop depends on it: with the leaf hashing inside a loop the
+// compiler hoists the compression's constants out of it and the kernel takes 224 VGPRs (2 waves per SIMD); without
+// the loop it takes 126, the leaf kernel's 4 waves per SIMD.
+template <bool TILED>
+__global__ __launch_bounds__(256) void tv_v2_list_kernel(TvV2List p) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_node[8][256];   // the tile's current level, SoA
+    __shared__ __attribute__((aligned(16))) uint32_t s_root[8][256];   // W > 256: the tiles' subtree roots (W / 256 <= 256 of them)
+    __shared__ uint32_t s_lw[256];        // log2 of the tree width of the workgroup's entry g (0xFF: no entry)
+    const uint32_t t = threadIdx.x;
+    const uint32_t logW = p.logW, logT = logW < 8u ? logW : 8u;   // a tile holds 1 << logT leaves of an entry
+    const uint32_t tiles = 1u << (logW - logT);
+    const uint32_t e0 = blockIdx.x << (8u - logT);                // the workgroup's first entry
+    const uint32_t e = e0 + (t >> logT), kt = t & ((1u << logT) - 1u);
+    const bool valid = e < p.m;
+    const uint32_t bytes = valid ? p.bytes[e] : 0;
+    const uint32_t we = valid ? p.widths[e] : 0;
+    const uint8_t* row = p.data + (valid ? (uint64_t)p.rows[e] * p.stride : 0);
+    if (kt == 0) s_lw[t >> logT] = valid ? 31u - (uint32_t)__builtin_clz(we) : 0xFFu;
+    uint32_t h[8];
+    for (uint32_t T = 0; T < (TILED ? tiles : 1u); T++) {
+        const uint32_t k = (T << logT) + kt;
+        const uint32_t lo = k * kLeaf;                            // (k < 65,536: below 2^30)
+        const bool active = k < we && lo < bytes;                 // the leaf holds >= 1 valid byte
+        const uint32_t len = active ? (bytes - lo < kLeaf ? bytes - lo : kLeaf) : 0;
+        hash_leaf(row + lo, len, active, h);
+        if (!active) {   // a padding leaf (or no entry): a zero hash, and no memory read
+#pragma unroll
+            for (int q = 0; q < 8; q++) h[q] = 0;
+        }
+        if (T == 0 && kt == 0 && we == 1) list_emit(p, e, h);     // a one-leaf tree: the leaf is the root
+#pragma unroll
+        for (int q = 0; q < 8; q++) s_node[q][t] = h[q];
+        __syncthreads();
+        for (uint32_t l = 0; l < logT; l++) {
+            if (!list_level(s_node, t, 256u >> (l + 1u), h)) continue;
+            const uint32_t sh = logT - l - 1u, g = t >> sh;       // node t is node (t & mask) of entry g's level l + 1
+            if ((t & ((1u << sh) - 1u)) != 0) continue;
+            if (T == 0 && s_lw[g] == l + 1u) list_emit(p, e0 + g, h);
+            if (tiles > 1 && sh == 0) {                           // (lane 0) the tile's subtree root
+#pragma unroll
+                for (int q = 0; q < 8; q++) s_root[q][T] = h[q];
+            }
+        }
+    }
+    // W > 256: the tile roots' levels 8 .. logW - 1.  Lane 0 stored the last tile's root after that tile's last
+    // barrier, and with 256 tiles its reader (lane 127) is in another wave.
+    if (TILED) __syncthreads();
+    for (uint32_t l = 8; l < logW; l++)
+        if (list_level(s_root, t, tiles >> (l - 7u), h) && t == 0 && s_lw[0] == l + 1u) list_emit(p, e0, h);
+}
+
+// ------------------------------------------------------------------------------------------
 // host-side launchers (tv_v2.hip)
 // ------------------------------------------------------------------------------------------
 hipError_t tv_v2_launch_leaves(const TvV2& p, hipStream_t s, uint32_t* workgroups) {
@@ -222,6 +337,19 @@ hipError_t tv_v2_launch_level(const TvV2& p, uint32_t level, uint32_t maxlog, hi
     const uint64_t grid = (((uint64_t)p.n << log_half) + 255) / 256;
     if (grid > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
     hipLaunchKernelGGL(tv_v2_level_kernel, dim3((unsigned)grid), dim3(256), 0, s, p, level, log_half);
+    return hipGetLastError();
+}
+
+hipError_t tv_v2_launch_list(const TvV2List& p, hipStream_t s, uint32_t* workgroups) {
+    if (workgroups) *workgroups = 0;
+    if (p.m == 0) return hipSuccess;
+    if (p.logW > TV_V2_LIST_MAX_LOGW) return hipErrorInvalidValue;
+    const uint32_t logG = p.logW < 8u ? 8u - p.logW : 0u;   // entries per workgroup: max(1, 256 / W)
+    const uint64_t grid = (((uint64_t)p.m - 1) >> logG) + 1;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    if (workgroups) *workgroups = (uint32_t)grid;
+    if (p.logW > 8u) hipLaunchKernelGGL(tv_v2_list_kernel<true>, dim3((unsigned)grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(tv_v2_list_kernel<false>, dim3((unsigned)grid), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

@@ -59,6 +59,11 @@ const SYMBOLS = {
   tv_v2_set_pieces: { parameters: ["pointer", "u64", "pointer", "pointer", "pointer"], result: "i32" },
   tv_v2_verify: { parameters: ["pointer", "pointer", "pointer"], result: "i32", nonblocking: true },
   tv_v2_hash: { parameters: ["pointer", "pointer"], result: "i32", nonblocking: true },
+  tv_v2_verify_list: {
+    parameters: ["pointer", "u64", "pointer", "pointer", "pointer", "pointer", "pointer"],
+    result: "i32",
+    nonblocking: true,
+  },
   tv_stream_begin: { parameters: ["pointer", "pointer"], result: "i32" },
   tv_stream_next: { parameters: ["pointer", "pointer"], result: "i32", nonblocking: true },
   tv_stream_commit: { parameters: ["pointer", "pointer"], result: "i32", nonblocking: true },
