@@ -365,6 +365,49 @@ int tv_stream_abort(tv_ctx *ctx);
  * bytes tv_fill_synthetic writes), generated on the host by TV_OPT_FILE_THREADS threads. */
 int tv_stream_fill_synthetic(tv_ctx *ctx, const tv_stream_req *req, uint64_t seed);
 
+/*
+ * Streamed BitTorrent v2 verify through the same bounded ring: a v2 torrent larger than the device budget, or on a
+ * GPU shared with other work, checked without a resident shard.
+ *
+ * tv_v2_stream_begin starts a stream whose units are hashed as v2 pieces.  It carries the piece table itself (as
+ * tv_v2_verify_list's entries do): n == the layout's n_pieces GLOBAL entries with tv_v2_set_pieces' ranges and error
+ * texts, `hashes` required (32 * n bytes); the ctx copies its shard's part, so the arrays are the caller's again when
+ * the call returns.  It needs a layout (the ALIGNED linear space, as for the other v2 calls), but neither
+ * tv_set_digests nor tv_v2_set_pieces, works with TV_OPT_RESIDENT 0 or 1, and leaves a table set with
+ * tv_v2_set_pieces alone.  After it tv_stream_next / _commit / _commit_from / _unreadable / _fill_synthetic / _end /
+ * _abort work as after tv_stream_begin, with one difference in the requests: row q holds
+ * min(width, piece_bytes[piece + q] - offset) valid bytes, 0 when that piece ends before the column (every file ends
+ * a piece, so any row may be short; a row of 0 bytes is neither filled nor copied).
+ *
+ * Geometry: a column is C bytes of every piece of a window of wn pieces; C is a power of two, 16 KiB <= C <=
+ * min(piece_length, 64 MiB), wn a multiple of 64 or the whole shard.  TV_OPT_STREAM_CHUNK = X > 0: C = the largest
+ * power of two <= min(max(X, 16 KiB), min(piece_length, 64 MiB)), one window across the shard.  Otherwise, under
+ * TV_OPT_RESIDENT_BUDGET (1 GiB when unset) for the two chunk buffers: whole pieces (C = min(piece_length, 64 MiB))
+ * when 64 of them fit, else C halved until 64 rows fit; then as many pieces per window as fit.  TV_OPT_STREAM_ROWS has
+ * no effect.  A column of a piece is a whole aligned subtree of its merkle tree, so one kernel launch per column
+ * reduces it to one node per piece and nothing is carried from column to column; a window's last column is followed by
+ * log2(piece_length / C) level launches and one finish launch.  Device memory beyond the two chunk buffers: 44 bytes
+ * per shard piece and at most 48 bytes x wn x (piece_length / C) of nodes, reused by a later stream they fit
+ * (TV_COUNTER_DEVICE_BYTES / _ALLOCS count them).  tv_last_kernel reports kernel id 32 and the launches used;
+ * tv_last_timing and TV_COUNTER_LAST_WORKGROUPS report as for a v1 stream.
+ * TV_ERR_STATE: before tv_set_layout, while a stream is active.  TV_ERR_ARG: piece_length not a power of two >= 16 KiB,
+ * n != n_pieces, a piece_bytes / tree_leaves entry outside its range, NULL arrays with n > 0.
+ *
+ * tv_v2_stream_file_table is that stream with the library's own readers as the producer, as tv_stream_file_table:
+ * the piece table as above and the file table (n_files files of lengths[k] bytes, paths NUL-separated in `paths`, in
+ * file-tree order).  File k starts at its ALIGNED offset: start[k + 1] = round_up(start[k] + lengths[k],
+ * piece_length); a zero-length file takes no space.  TV_ERR_ARG when the files' piece count differs from n_pieces or
+ * a piece's bytes differ from what its file holds of it.  A v2 piece lies in exactly one file: it is unreadable
+ * (bit 0) exactly when that file is missing, unopenable under TV_OPT_OPEN_RW, or shorter than the piece's offset in
+ * it + piece_bytes (the zero-length-segment open rule of v1 does not apply).  status_out[k] (n_files entries) =
+ * TV_ERR_IO when a read or open of file k failed.  Nothing is created.
+ */
+int tv_v2_stream_begin(tv_ctx *ctx, uint64_t n, const uint32_t *piece_bytes, const uint32_t *tree_leaves,
+                       const uint8_t *hashes /* 32*n */, const uint8_t *avail_bits);
+int tv_v2_stream_file_table(tv_ctx *ctx, uint64_t n_pieces, const uint32_t *piece_bytes, const uint32_t *tree_leaves,
+                            const uint8_t *hashes, uint64_t n_files, const uint64_t *lengths, const char *paths,
+                            uint64_t paths_bytes, const uint8_t *avail_bits, uint8_t *bitfield_out, int32_t *status_out);
+
 /* Page-locked host memory for tv_verify_host / tv_stage sources.  A pinned source is read by
  * DMA directly (no staging memcpy); pageable memory goes through the library's pinned ring.
  * tv_host_register pins an existing range (e.g. a caller's buffer), tv_host_unregister undoes it. */
@@ -426,7 +469,7 @@ int tv_get_option(tv_ctx *ctx, int key, int64_t *value);
 int tv_last_timing(tv_ctx *ctx, double *kernel_ms, double *total_ms);
 
 /* Kernel chosen for the last call (1 lane, 2 split, 4 twin; 8 = the v2 SHA-256 merkle kernels, 16 = the v2 list
- * kernel) and launches it used. */
+ * kernel, 32 = a v2 stream's column kernel) and launches it used. */
 int tv_last_kernel(tv_ctx *ctx, int *kernel, int *launches);
 
 /* Resource counters of a ctx (tv_get_counter keys): how often tv_set_layout and the calls after it had to

@@ -6,6 +6,7 @@ lane mappings (TV_OPT_V2_MAP), alternated step by step.
     python tools/v2_bench.py [--steps 10] [--warmup 3] [--out profiles/v2/v2_bench.json]
     python tools/v2_bench.py --list [--parent-json FILE] [--out profiles/v2/list_latency.json]
     python tools/v2_bench.py --list-resident-only [--out FILE]
+    python tools/v2_bench.py --stream [--out profiles/v2/stream_bench.json]
 
 --list is the incremental-verify leg: the flush time of tv_v2_verify_list (one launch, the trees in LDS) for 1 / 64 /
 4,096 pieces of 256 KiB and 1 / 64 / 1,024 pieces of 4 MiB, against (a) tv_verify_list (SHA-1) on the same bytes and
@@ -13,6 +14,19 @@ lane mappings (TV_OPT_V2_MAP), alternated step by step.
 2 warm-ups.  --list-resident-only runs (b) alone and uses nothing newer than tv_v2_verify, so a copy of this tool
 beside an older build of the package measures that build; --parent-json takes its output as (b).  Acceptance: at the
 largest list of each size the fused kernel_ms is at most (b)'s times (b)'s own max / min spread (at least 1.05).
+
+--stream is the streamed leg: cfg2's bytes (16,384 x 1 MiB of the synthetic payload) through the bounded pinned ring
+as v2 pieces (tv_v2_stream_begin) and, in the same session over the same bytes and the same options (TV_OPT_STREAM_CHUNK
+0, TV_OPT_RESIDENT_BUDGET 1 GiB), as v1 pieces (tv_stream_begin: its automatic columns; and with TV_OPT_STREAM_ROWS, whose
+windows of whole pieces are the v2 stream's shape).  Two producers each: the host generator
+(tv_stream_fill_synthetic) and a 256 MiB page-locked pool of 256 pieces repeated, DMA'd in place
+(tv_stream_commit_from), as bench.py's cfg5 leg (not for v1's columns: a column request spans more pieces than the pool
+holds).  The expected roots and digests come from the resident calls on the
+same bytes (tv_fill_synthetic + tv_v2_hash / tv_hash).  Five timed runs after one warm-up.  Both paths are bound by
+the same PCIe copies, so the acceptance is: the v2 stream's median GB/s is no lower than the MINIMUM of the v1 stream's
+five runs (v1's own run-to-run spread as the margin), per producer, against the faster of the two v1 forms; the
+bitfields are all ones, and exact with 1 % of the expected hashes corrupted.  One point under a 0.25 GiB budget is
+recorded beside it (information, not a gate).
 
 Times are the library's HIP events around the kernels (tv_last_timing); the shader clock is the clock probe's
 (TV_OPT_CLOCK_PROBE).  The expected hashes come from tv_v2_hash, and a sample of pieces read back with tv_read is
@@ -199,8 +213,152 @@ def list_main(a) -> int:
     return 0
 
 
+STREAM_RUNS, STREAM_WARMUP = 5, 1
+POOL_PIECES = 256
+
+
+def _stream_pass(ctx, begin, produce) -> tuple:
+    """One streamed pass: (bitfield, seconds, requests, {phase: seconds}, kernel_ms, launches)."""
+    ph = {"next_s": 0.0, "produce_commit_s": 0.0, "end_s": 0.0}
+    t0 = time.perf_counter()
+    begin()
+    reqs = 0
+    while True:
+        ta = time.perf_counter()
+        req = ctx.stream_next()
+        tb = time.perf_counter()
+        ph["next_s"] += tb - ta
+        if not req.rows:
+            break
+        produce(req)
+        ph["produce_commit_s"] += time.perf_counter() - tb
+        reqs += 1
+    ta = time.perf_counter()
+    bits = ctx.stream_end()
+    t1 = time.perf_counter()
+    ph["end_s"] = t1 - ta
+    return bits, t1 - t0, reqs, {k: round(v, 4) for k, v in ph.items()}, ctx.last_timing()[0], ctx.last_kernel()
+
+
+def _stream_leg(ctx, total: int, begin, produce, want: bytes) -> dict:
+    gbs, kms, last = [], [], None
+    for run in range(STREAM_WARMUP + STREAM_RUNS):
+        bits, el, reqs, ph, k_ms, kern = _stream_pass(ctx, begin, produce)
+        assert bits == want, "a timed stream's bitfield is wrong"
+        if run >= STREAM_WARMUP:
+            gbs.append(total / el / 1e9)
+            kms.append(k_ms)
+            last = (reqs, ph, kern)
+    return {"GBps_runs": [round(g, 2) for g in gbs], "GBps_median": round(statistics.median(gbs), 2),
+            "GBps_min": round(min(gbs), 2), "GBps_max": round(max(gbs), 2),
+            "kernel_span_ms_median": round(statistics.median(kms), 2), "requests": last[0], "last_run_phases_s": last[1],
+            "kernel": last[2][0], "launches": last[2][1], "clock_khz": ctx.last_clock_khz()}
+
+
+def _corrupt_every(hashes: bytes, width: int, step: int = 100) -> tuple:
+    """Every `step`-th expected hash with one byte flipped -> (hashes, MSB-first bits with those pieces 0)."""
+    n = len(hashes) // width
+    h = bytearray(hashes)
+    bits = bytearray(b"\xff" * (n // 8))
+    for i in range(7, n, step):
+        h[width * i + 3] ^= 0x55
+        bits[i >> 3] &= ~(0x80 >> (i & 7)) & 0xFF
+    return bytes(h), bytes(bits)
+
+
+def stream_main(a) -> int:
+    from tests import synth
+    L, W, seed = 1 << 20, (1 << 20) // LEAF, 5
+    P = (a.cfg2_gib << 30) // L
+    total = P * L
+    ones = b"\xff" * (P // 8)
+    res = {"build_id": N.build_id(), "bytes": total, "piece_length": L, "pieces": P, "runs": STREAM_RUNS,
+           "warmup": STREAM_WARMUP, "threads": N.cpu_share(), "legs": {}}
+    with N.Context(0) as ctx:
+        ctx.set_clock_probe(True)
+        ctx.set_option(N.TV_OPT_FILE_THREADS, N.cpu_share())
+        # the expected values, from the resident calls: the generated torrent, then the pool's 256 pieces
+        ctx.set_layout(total, L, P)
+        ctx.fill_synthetic(seed)
+        ctx.v2_set_pieces([L] * P, [W] * P, None)
+        roots = ctx.v2_hash()
+        digests = ctx.hash()
+        buf = bytearray(L)
+        ctx.read((P - 1) * L, buf)
+        assert roots[-32:] == merkle_root(bytes(buf), W), "the last piece differs from hashlib"
+        pool = N.PinnedBuffer(POOL_PIECES * L)
+        synth.fill_into(pool.mv, seed + 100, 0, threads=N.cpu_share())
+        ctx.set_layout(POOL_PIECES * L, L, POOL_PIECES)
+        ctx.stage(0, pool.mv)
+        ctx.v2_set_pieces([L] * POOL_PIECES, [W] * POOL_PIECES, None)
+        pool_roots = ctx.v2_hash() * (P // POOL_PIECES)
+        pool_digests = ctx.hash() * (P // POOL_PIECES)
+        # streamed-only from here on
+        ctx.set_option(N.TV_OPT_RESIDENT, 0)
+        ctx.set_option(N.TV_OPT_STREAM_CHUNK, 0)
+        import numpy as np
+        table = (np.full(P, L, dtype=np.uint32), np.full(P, W, dtype=np.uint32))   # (no list conversion in the timed begin)
+
+        def gen(req):
+            ctx.stream_fill_synthetic(req, seed)
+            ctx.stream_commit(req)
+
+        def from_pool(req):
+            ctx.stream_commit_from(req, pool.mv, L, (req.piece % POOL_PIECES) * L + req.offset)
+
+        def legs(tag: str, budget: int, v1_forms) -> None:
+            ctx.set_option(N.TV_OPT_RESIDENT_BUDGET, budget)
+            ctx.set_option(N.TV_OPT_STREAM_ROWS, 0)
+            ctx.set_layout(total, L, P)
+            for name, prod, hs in (("generated", gen, roots), ("pinned_pool", from_pool, pool_roots)):
+                res["legs"][f"v2_{name}{tag}"] = _stream_leg(
+                    ctx, total, lambda: ctx.v2_stream_begin(table[0], table[1], hs), prod, ones)
+                bad, want = _corrupt_every(hs, 32)
+                bits = _stream_pass(ctx, lambda: ctx.v2_stream_begin(table[0], table[1], bad), prod)[0]
+                assert bits == want, "1 % corrupted: the bitfield is not exact"
+                res["legs"][f"v2_{name}{tag}"]["exact_with_1pct_corrupted"] = True
+            for form, rows in v1_forms:
+                ctx.set_option(N.TV_OPT_STREAM_ROWS, rows)
+                ctx.set_layout(total, L, P)
+                for name, prod, dg in (("generated", gen, digests), ("pinned_pool", from_pool, pool_digests)):
+                    if name == "pinned_pool" and not rows:
+                        continue      # (a column request spans 1,024 pieces: more than the pool holds in a row)
+                    ctx.set_digests(dg)
+                    res["legs"][f"v1_{form}_{name}{tag}"] = _stream_leg(ctx, total, ctx.stream_begin, prod, ones)
+                    bad, want = _corrupt_every(dg, 20)
+                    ctx.set_digests(bad)
+                    assert _stream_pass(ctx, ctx.stream_begin, prod)[0] == want
+            ctx.set_option(N.TV_OPT_STREAM_ROWS, 0)
+
+        legs("", 1 << 30, (("columns", 0), ("rows", 1)))
+        legs("_budget_quarter_GiB", 256 << 20, (("rows", 1),))
+        ctx.set_option(N.TV_OPT_RESIDENT, 1)
+        ctx.set_option(N.TV_OPT_RESIDENT_BUDGET, 0)
+        pool.close()
+    res["acceptance"] = []
+    ok = True
+    for name in ("generated", "pinned_pool"):
+        v2 = res["legs"][f"v2_{name}"]
+        forms = [f for f in ("columns", "rows") if f"v1_{f}_{name}" in res["legs"]]
+        best = max(forms, key=lambda f: res["legs"][f"v1_{f}_{name}"]["GBps_median"])
+        v1 = res["legs"][f"v1_{best}_{name}"]
+        row = {"producer": name, "v2_GBps_median": v2["GBps_median"], "v1_GBps_min_of_runs": v1["GBps_min"],
+               "v1_form": best,
+               "pass": v2["GBps_median"] >= v1["GBps_min"]}
+        ok = ok and row["pass"]
+        res["acceptance"].append(row)
+    res["pass"] = ok
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    return 0 if ok else 1
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--stream", action="store_true", help="the streamed leg (see the module docstring)")
     ap.add_argument("--list", action="store_true", help="the incremental-verify leg (see the module docstring)")
     ap.add_argument("--list-resident-only", action="store_true", help="leg (b) of --list alone")
     ap.add_argument("--parent-json", default=None, help="--list: a --list-resident-only output to take (b) from")
@@ -215,6 +373,8 @@ def main() -> int:
         raise SystemExit("no HIP device visible: this measures the GPU")
     if a.list or a.list_resident_only:
         return list_main(a)
+    if a.stream:
+        return stream_main(a)
     res = {"R_valu_sha256_GBps_2400": round(R_VALU_256, 1), "cycles_per_block": CYCLES_PER_BLOCK,
            "build_id": N.build_id(), "steps": a.steps, "warmup": a.warmup, "shapes": []}
     with N.Context(0) as ctx:

@@ -17,7 +17,7 @@ from .incremental import (IncrementalVerifier, IncrementalVerifierV2, flush_cost
 from .make_torrent import make_torrent  # noqa: F401
 from .metainfo_v2 import FileV2, MetainfoV2, V2Layout, parse_metainfo_v2  # noqa: F401
 from .v2 import (hash_files_v2, make_torrent_v2, verify_files_v2, verify_payload_v2,  # noqa: F401
-                 verify_piece_v2)
+                 verify_piece_v2, verify_stream_v2)
 
 __all__ = [
     "bdecode", "bencode", "FileInfo", "InfoDict", "Metainfo", "make_info", "parse_metainfo", "partition",
@@ -27,6 +27,6 @@ __all__ = [
     "verify_pieces", "verify_pieces_async", "verify_stream", "release_contexts", "context_counters", "hash_files",
     "IncrementalVerifier", "make_torrent",
     "bdecode_raw", "FileV2", "MetainfoV2", "V2Layout", "parse_metainfo_v2", "hash_files_v2", "make_torrent_v2",
-    "verify_files_v2", "verify_payload_v2", "verify_piece_v2",
+    "verify_files_v2", "verify_payload_v2", "verify_piece_v2", "verify_stream_v2",
     "IncrementalVerifierV2", "flush_cost_ms_v2", "validate_received_block_v2",
 ]

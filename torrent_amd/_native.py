@@ -86,6 +86,7 @@ TV_STREAM_SLOT_BYTES = 64 << 20
 KERNEL_AUTO, KERNEL_LANE, KERNEL_SPLIT, KERNEL_TWIN = 0, 1, 2, 4   # (3 was MIX, removed)
 KERNEL_V2 = 8   # tv_last_kernel after tv_v2_verify / tv_v2_hash
 KERNEL_V2_LIST = 16   # tv_last_kernel after tv_v2_verify_list
+KERNEL_V2_STREAM = 32   # tv_last_kernel after a v2 stream (tv_v2_stream_begin .. tv_stream_end)
 
 _u64, _i64, _int, _p = ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
 
@@ -135,6 +136,8 @@ SYMBOLS = [
     ("tv_v2_verify", _int, [_p, _p, _p]),
     ("tv_v2_hash", _int, [_p, _p]),
     ("tv_v2_verify_list", _int, [_p, _u64, _p, _p, _p, _p, _p]),
+    ("tv_v2_stream_begin", _int, [_p, _u64, _p, _p, _p, _p]),
+    ("tv_v2_stream_file_table", _int, [_p, _u64, _p, _p, _p, _u64, _p, _p, _u64, _p, _p, _p]),
     ("tv_stream_begin", _int, [_p, _p]),
     ("tv_stream_next", _int, [_p, _REQ]),
     ("tv_stream_commit", _int, [_p, _REQ]),
@@ -273,6 +276,7 @@ class Context:
         self.shard_first = 0
         self.shard_count = 0
         self.thread_budget = 16   # host threads this context's call may use (verify._run_shards sets its share)
+        self._v2_stream_bytes = None   # the piece bytes of an active v2 stream (row_bytes)
 
     # -- plumbing ----------------------------------------------------------------------
     def _err(self) -> str:
@@ -499,8 +503,58 @@ class Context:
     # -- streamed verify (tv_stream_*): bounded pinned ring, end-to-end resume check ----
     def stream_begin(self, avail_bits=None) -> None:
         a, keep = _addr(avail_bits)
+        self._v2_stream_bytes = None
         self._check(self._L.tv_stream_begin(self._h, a))
         del keep
+
+    def _v2_table(self, what: str, piece_bytes, tree_leaves, hashes):
+        import numpy as np
+        pb = np.ascontiguousarray(piece_bytes, dtype=np.uint32)
+        tl = np.ascontiguousarray(tree_leaves, dtype=np.uint32)
+        if len(pb) != len(tl):
+            raise ValueError(f"{what}: piece_bytes and tree_leaves differ in length")
+        if hashes is None or memoryview(hashes).nbytes != 32 * len(pb):
+            raise ValueError(f"{what}: hashes must hold 32 bytes per piece")
+        a, keep = _addr(hashes)
+        if a is None:   # (an empty table: any non-NULL pointer)
+            keep = ctypes.create_string_buffer(1)
+            a = ctypes.addressof(keep)
+        return pb, tl, a, keep
+
+    def v2_stream_begin(self, piece_bytes, tree_leaves, hashes, avail_bits=None) -> None:
+        """tv_v2_stream_begin: a stream whose units are hashed as BitTorrent v2 pieces.  The piece table is GLOBAL (one
+        entry per piece of the layout, as v2_set_pieces takes it) and `hashes` is required; then stream_next /
+        stream_commit / stream_end as after stream_begin.  row_bytes follows the table until the next stream_begin."""
+        pb, tl, a, keep = self._v2_table("v2_stream_begin", piece_bytes, tree_leaves, hashes)
+        b, keep2 = _addr(avail_bits)
+        self._check(self._L.tv_v2_stream_begin(self._h, len(pb), pb.ctypes.data, tl.ctypes.data, a, b))
+        self._v2_stream_bytes = pb
+        del keep, keep2
+
+    def v2_stream_file_table(self, piece_bytes, tree_leaves, hashes, lengths, paths, avail: Optional[bytes] = None) -> tuple:
+        """tv_v2_stream_file_table: the v2 resume check from the files through the bounded ring (the piece table as for
+        v2_stream_begin; file k: lengths[k] bytes at paths[k], file-tree order, each file at its aligned offset).
+        -> (bitfield, per-file statuses)."""
+        import numpy as np
+
+        pb, tl, h, keep = self._v2_table("v2_stream_file_table", piece_bytes, tree_leaves, hashes)
+        n = len(paths)
+        if len(lengths) != n:
+            raise ValueError("v2_stream_file_table: lengths and paths differ in length")
+        if n and all(type(x) is str for x in paths):
+            blob = ("\0".join(paths) + "\0").encode(sys.getfilesystemencoding(), "surrogateescape")
+        else:
+            blob = b"\0".join(os.fsencode(x) for x in paths) + b"\0" if n else b"\0"
+        if n and blob.count(b"\0") != n:
+            raise ValueError("v2_stream_file_table: a path contains a NUL byte")
+        ln = np.ascontiguousarray(lengths if n else [0], dtype=np.uint64)
+        st = np.zeros(max(1, n), dtype=np.int32)
+        out = ctypes.create_string_buffer(max(1, self._nbits()))
+        a, keep2 = _addr(avail)
+        self._check(self._L.tv_v2_stream_file_table(self._h, len(pb), pb.ctypes.data, tl.ctypes.data, h, n,
+                                                    ln.ctypes.data, blob, len(blob), a, out, st.ctypes.data))
+        del keep, keep2
+        return out.raw[: self._nbits()], st[:n].tolist()
 
     def stream_next(self) -> StreamReq:
         """The next request (req.rows == 0: every byte has been requested)."""
@@ -509,8 +563,11 @@ class Context:
         return req
 
     def row_bytes(self, req: StreamReq, q: int) -> int:
-        """Valid bytes of row q: min(width, piece_len - offset) (piece.ts:16-19)."""
+        """Valid bytes of row q: min(width, piece_len - offset) (piece.ts:16-19); in a v2 stream the piece's length is
+        its entry of the piece table."""
         i = req.piece + q
+        if self._v2_stream_bytes is not None:
+            return max(0, min(req.width, int(self._v2_stream_bytes[i]) - req.offset))
         L, P, total = self.piece_length, self.n_pieces, self.total_length
         plen = total % L if (i == P - 1 and total % L) else L
         return max(0, min(req.width, plen - req.offset))

@@ -2,7 +2,7 @@
 // translation units share.  tv_context.hip: lifecycle, options, layout, digests, counters; tv_core.hip: errors, NUMA,
 // staging rings, windows, slot pool, kernel choice, the host -> HBM copy path; tv_stage.hip: staging from memory;
 // tv_files.hip: staging from files; tv_stream.hip: the streamed engine; tv_verify.hip: verify / list / hash;
-// tv_v2.hip: the BitTorrent v2 piece table, verify, hash and list verify.
+// tv_v2.hip: the BitTorrent v2 piece table, verify, hash and list verify (the streamed v2 verify: tv_stream.hip).
 // Nothing here is exported (the link exports tv_* only: exports.map).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -138,6 +138,11 @@ struct StreamState {
     int kernel = 0;
     bool k0 = false;           // ev_k0 recorded (first launch queued)
     std::vector<uint8_t> av;   // shard-relative availability bits, applied to the bitfield at the end
+    // a BitTorrent v2 stream (tv_v2_stream_begin): the units are hashed as merkle pieces by tv_v2_column_kernel
+    bool v2 = false;
+    uint32_t v2_logc = 0, v2_logn = 0;   // log2 of the leaves per column (C / 16 KiB) and of the columns per piece (L / C)
+    int launches = 0;                    // kernel launches so far (column, level and finish kernels)
+    std::vector<uint32_t> v2_bytes;      // shard-relative valid bytes of every piece: the requests' row lengths
 };
 
 // A cold-read bounce buffer (TV_OPT_FILE_BOUNCE): kBounceBytes of page-locked memory and the event of the DMA that
@@ -324,6 +329,11 @@ struct tv_ctx {
     uint64_t cap_v2_nodes = 0;         // words of d_v2_nodes
     uint32_t* d_v2_list = nullptr;     // tv_v2_verify_list: [11][m] rows, bytes, widths, expected [8], then v2_list_cap out bytes
     uint64_t v2_list_cap = 0;          // entries of d_v2_list (48 bytes each)
+    // a v2 stream's device memory beyond the chunk buffers (tv_v2_stream_begin; kept for a later stream that fits)
+    uint32_t* d_v2s_tab = nullptr;     // [11][count]: piece bytes, tree leaves, top-tree widths, expected [8] per window
+    uint32_t* d_v2s_nodes = nullptr;   // a window's partial nodes: level buffers A [8][wn x ncol], B [8][wn x max(ncol/2, 1)]
+    uint64_t cap_v2s_tab = 0;          // words of d_v2s_tab
+    uint64_t cap_v2s_nodes = 0;        // words of d_v2s_nodes
     int v2_map_opt = 0;                // TV_OPT_V2_MAP: 0 auto, else TV_V2_MAP_*
     int v2_last_map = 0;               // the mapping the last v2 call's leaf kernel ran with
 
@@ -390,6 +400,10 @@ void free_chunks(tv_ctx* c);
 void free_list(tv_ctx* c);
 void free_v2(tv_ctx* c);
 void v2_on_layout(tv_ctx* c);   // tv_set_layout: drop the v2 piece table, free what the new geometry does not fit
+// tv_v2_set_pieces' checks of a GLOBAL piece table against the layout (TV_ERR_ARG and its texts), shared with
+// tv_v2_stream_begin
+int v2_check_table(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const uint32_t* tree_leaves);
+uint64_t v2_node_words(uint64_t count, uint64_t W);
 void free_device(tv_ctx* c);
 bool reuse_fits(uint64_t need, uint64_t cap);
 

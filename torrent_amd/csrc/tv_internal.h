@@ -77,6 +77,8 @@ struct TvV2 {
     const uint64_t* avail64;     // verify: MSB-first availability bytes in 64-bit words; may be null
     uint64_t* out64;             // verify: MSB-first bitfield bytes in 64-bit words, whole 256-piece groups
     uint64_t* clock;             // TV_OPT_CLOCK_PROBE (as TvPieces::clock); null = off
+    uint32_t out_words;          // verify: the finish launch writes out64[0 .. out_words) only (a window of a streamed
+                                 // shard: the words after it belong to the next window); 0 = every word of its grid
 };
 // Leaf hashes (every leaf inside a piece's valid bytes is hashed, the other positions of its tree get zero hashes).
 hipError_t tv_v2_launch_leaves(const TvV2& p, hipStream_t s, uint32_t* workgroups);
@@ -103,6 +105,30 @@ struct TvV2List {
     uint8_t* out_bytes;          // [m]
 };
 hipError_t tv_v2_launch_list(const TvV2List& p, hipStream_t s, uint32_t* workgroups);
+
+// ---- the v2 column launch of a streamed verify (tv_v2_stream_begin): one column of a window of n pieces -------------
+#define TV_KERNEL_V2_STREAM 32    // tv_last_kernel id of a v2 stream (tv_v2_column_kernel + the window's levels + finish)
+#define TV_V2_COL_MAX_LOGC 12     // a column is at most 64 MiB (one ring slot): 4,096 leaves, 16 tiles of 256
+// Row j of the chunk buffer (data + j * stride) holds bytes [col << (14 + logc), ...) of window piece j: the c = 1 << logc
+// leaves col * c .. col * c + c - 1 of its tree, an aligned subtree.  The kernel hashes the leaves (a position inside
+// the tree but past piece_bytes[j] is a zero hash and reads no memory) and reduces them in LDS to ONE node, the
+// subtree's root at level min(logc, log2 tree_leaves[j]), stored at node slot (j << logn) + col of `nodes`
+// (SoA [8][n << logn], big-endian values): level buffer A of the window's top tree, whose row of piece j is
+// max(1, tree_leaves[j] >> logc) nodes wide.  A piece whose tree does not reach the column (col * c >= tree_leaves[j])
+// writes nothing.
+struct TvV2Col {
+    const uint8_t* data;
+    uint64_t stride;
+    uint32_t n;                  // pieces in the window
+    uint32_t logc;               // leaves per column = 1 << logc (<= TV_V2_COL_MAX_LOGC)
+    uint32_t logn;               // columns per piece = 1 << logn
+    uint32_t col;                // this column
+    const uint32_t* piece_bytes; // [n]
+    const uint32_t* tree_leaves; // [n]
+    uint32_t* nodes;             // [8][n << logn]
+    uint64_t* clock;             // TV_OPT_CLOCK_PROBE (as TvPieces::clock); null = off
+};
+hipError_t tv_v2_launch_column(const TvV2Col& p, hipStream_t s, uint32_t* workgroups);
 
 // workgroups (optional): set to the launch's grid size, companions included.
 hipError_t tv_launch_verify(const TvPieces& p, int kernel, bool hash, hipStream_t s, int split_pairs = 0,

@@ -1,6 +1,7 @@
 // tv_plan.h -- the resident payload's shape under a device budget (tv_set_layout), a stream's windows x columns under
-// one (stream_geometry) and the file table's walk (walk_file_table), as plain host code with no HIP in it, so they are
-// unit-tested on the CPU (tests/c/plan_test.cpp, tests/c/walk_main.cpp, tests/test_plan.py).
+// one (stream_geometry; v2_stream_geometry for a BitTorrent v2 stream), the file table's walk (walk_file_table) and a
+// v2 torrent's aligned file offsets (v2_file_starts), as plain host code with no HIP in it, so they are unit-tested on
+// the CPU (tests/c/plan_test.cpp, tests/c/walk_main.cpp, tests/c/plan_v2_main.cpp; tests/test_plan.py, test_plan_v2.py).
 #pragma once
 #include <stdint.h>
 
@@ -132,6 +133,58 @@ inline void stream_geometry(uint64_t L, uint64_t count, uint64_t budget, uint64_
         w = std::min<uint64_t>(count, std::max<uint64_t>(w, (half - slack) / (C + 256) / 64 * 64));
     *col = C;
     *win = w;
+}
+
+// ---- a BitTorrent v2 stream's geometry (tv_stream.hip: tv_v2_stream_begin, tv_v2_stream_file_table) ----------------
+//
+// A column is C bytes of every piece of a window of wn pieces: C a power of two, 16 KiB (one leaf) <= C <= Cmax =
+// min(L, 64 MiB: one ring slot), so a column of a piece is a whole aligned subtree of c = C / 16 KiB leaves, which one
+// workgroup reduces to one node; wn a multiple of 64 (bitfield words of its own), or the whole shard.
+//   chunk > 0 (TV_OPT_STREAM_CHUNK): C = the largest power of two <= min(max(chunk, 16 KiB), Cmax), one window across
+//     the shard.
+//   chunk == 0: under `budget` bytes for the two chunk buffers (rows of pitch C + 256, `slack` after the last): start
+//     from C = Cmax (whole pieces: the longest rows, no partial nodes), halve C while 64 rows do not fit, then wn = the
+//     largest multiple of 64, at least 64 and at most the shard, whose two buffers fit.
+// The serial unit of a v2 piece is a 16 KiB leaf, so a narrow window costs no serial hashing time: there is no floor
+// of 2,048 pieces as in stream_geometry.  L must be a power of two >= 16 KiB (the callers check).
+constexpr uint64_t kV2Leaf = 16384;
+constexpr uint64_t kV2StreamColMax = 64ull << 20;
+inline void v2_stream_geometry(uint64_t L, uint64_t count, uint64_t budget, uint64_t chunk, uint64_t slack,
+                               uint64_t* col, uint64_t* win) {
+    const uint64_t cmax = std::min<uint64_t>(L, kV2StreamColMax);
+    if (chunk) {
+        const uint64_t lim = std::min<uint64_t>(std::max<uint64_t>(chunk, kV2Leaf), cmax);
+        uint64_t C = kV2Leaf;
+        while (C * 2 <= lim) C *= 2;
+        *col = C;
+        *win = count;
+        return;
+    }
+    const uint64_t half = budget / 2;
+    auto fits = [&](uint64_t C, uint64_t rows) { return half >= slack && rows <= (half - slack) / (C + 256); };
+    uint64_t C = cmax;
+    while (C > kV2Leaf && !fits(C, 64)) C /= 2;
+    uint64_t wn = half > slack ? (half - slack) / (C + 256) / 64 * 64 : 0;
+    wn = std::max<uint64_t>(64, wn);
+    *col = C;
+    *win = std::min<uint64_t>(wn, count);
+}
+
+// Where each file of a v2 torrent starts in the ALIGNED linear space: every file starts a new piece, so
+// start[k + 1] = round_up(start[k] + lengths[k], L) (a zero-length file takes no space).  start gets n + 1 entries;
+// start[n] / L is the files' piece count.  false (*bad = the file) when the offsets overflow 64 bits.
+inline bool v2_file_starts(uint64_t n, const uint64_t* lengths, uint64_t L, std::vector<uint64_t>* start,
+                           uint64_t* bad) {
+    start->assign(n + 1, 0);
+    for (uint64_t k = 0; k < n; k++) {
+        const uint64_t s = (*start)[k];
+        if (lengths[k] > UINT64_MAX - s || s + lengths[k] > UINT64_MAX - (L - 1)) {
+            *bad = k;
+            return false;
+        }
+        (*start)[k + 1] = (s + lengths[k] + L - 1) / L * L;
+    }
+    return true;
 }
 
 }  // namespace tvi

@@ -1,5 +1,7 @@
 // tv_stream.hip -- the streamed verify engine (tv_stream_*; tv_verify_host runs on it): a bounded pinned ring
 // between the caller's bytes and two device chunk buffers, one kernel launch per column / window of pieces.
+// tv_v2_stream_begin / tv_v2_stream_file_table run BitTorrent v2 pieces through the same engine: one column-kernel
+// launch per unit and the window's top tree after its last column.
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -24,6 +26,17 @@ uint64_t row_bytes(const tv_ctx* c, uint64_t piece, uint64_t offset, uint64_t wi
     const uint64_t plen = piece_len(c, piece);
     return plen > offset ? std::min(width, plen - offset) : 0;
 }
+
+// A v2 stream's row: the piece's valid bytes inside the column (0 when the piece ends before it).  Any row may be
+// short, not only the torrent's last piece's: every file ends a piece.
+uint64_t v2_row_bytes(const tv_ctx* c, uint64_t piece, uint64_t offset, uint64_t width) {
+    const uint64_t plen = c->st.v2_bytes[piece - c->first];
+    return plen > offset ? std::min(width, plen - offset) : 0;
+}
+
+// The row length rule of the active stream.
+using RowBytes = uint64_t (*)(const tv_ctx*, uint64_t, uint64_t, uint64_t);
+RowBytes stream_row_rule(const tv_ctx* c) { return c->st.v2 ? v2_row_bytes : row_bytes; }
 
 // Drop an active stream: give its lent slot back and let the queued copies and kernels drain.
 void stream_abort_locked(tv_ctx* c) {
@@ -113,6 +126,130 @@ int stream_begin_locked(tv_ctx* c, const uint8_t* avail_bits, uint64_t col_overr
     return TV_OK;
 }
 
+// A BitTorrent v2 stream (tv_v2_stream_begin): the same ring, requests and chunk buffers, the units hashed as merkle
+// pieces.  A column of C = c x 16 KiB bytes of a piece is a whole aligned subtree of its tree, so the column kernel
+// reduces it to one node in the window's partial-node buffer and NOTHING is carried between columns (the v1 columns
+// carry each piece's SHA-1 chaining value in d_state); the window's last column is followed by the top tree over the
+// L / C nodes of each piece: log2(L / C) level launches and the finish launch, on a table derived for the window.
+// The geometry: tv_plan.h v2_stream_geometry.  The caller has checked the state and the table (v2_check_table).
+int v2_stream_begin_locked(tv_ctx* c, const uint32_t* piece_bytes, const uint32_t* tree_leaves, const uint8_t* hashes,
+                           const uint8_t* avail_bits, uint64_t req_bytes = 0) {
+    StreamState& st = c->st;
+    st = StreamState{};
+    st.v2 = true;
+    st.kernel = TV_KERNEL_V2_STREAM;
+    st.av.assign((c->count + 7) / 8, 0xFF);
+    if (avail_bits) memcpy(st.av.data(), avail_bits, st.av.size());
+    if (c->count == 0) {  // nothing to hash: the first tv_stream_next reports completion
+        st.active = true;
+        return TV_OK;
+    }
+    uint64_t C = 0, wn = 0;
+    v2_stream_geometry(c->L, c->count, c->budget_opt ? c->budget_opt : (1ull << 30), c->stream_chunk, kSlack, &C, &wn);
+    st.C = C;
+    st.wn = wn;
+    st.row_pitch = C + 256;
+    st.ncol = c->L / C;
+    st.nwin = (c->count + wn - 1) / wn;
+    st.nunits = st.nwin * st.ncol;
+    while ((kV2Leaf << st.v2_logc) < C) st.v2_logc++;
+    while ((1ull << st.v2_logn) < st.ncol) st.v2_logn++;
+    st.rows_per_req = std::max<uint64_t>(1, (req_bytes ? std::min<uint64_t>(req_bytes, kRingSlotBytes) : kRingSlotBytes) / C);
+    TV_HIP(c, hipStreamSynchronize(c->stream));   // (nothing queued still reads the buffers replaced below)
+    const uint64_t need = st.row_pitch * wn + kSlack;
+    if (!reuse_fits(need, c->chunk_bytes)) {
+        free_chunks(c);
+        for (auto& p : c->d_chunk) {
+            TV_HIP(c, hipMalloc((void**)&p, need));
+            c->n_device_allocs++;
+        }
+        c->chunk_bytes = need;
+    }
+    // (whole-piece columns run no level: the finish launch reads the column nodes themselves, level buffer A alone)
+    const uint64_t need_tab = 11 * c->count, need_nodes = st.ncol > 1 ? v2_node_words(wn, st.ncol) : 8 * wn;
+    if (!c->d_v2s_tab || !reuse_fits(need_tab, c->cap_v2s_tab)) {
+        (void)hipFree(c->d_v2s_tab);
+        c->d_v2s_tab = nullptr;
+        c->cap_v2s_tab = 0;
+        TV_HIP(c, hipMalloc((void**)&c->d_v2s_tab, need_tab * sizeof(uint32_t)));
+        c->cap_v2s_tab = need_tab;
+        c->n_device_allocs++;
+    }
+    if (!c->d_v2s_nodes || !reuse_fits(need_nodes, c->cap_v2s_nodes)) {
+        (void)hipFree(c->d_v2s_nodes);
+        c->d_v2s_nodes = nullptr;
+        c->cap_v2s_nodes = 0;
+        TV_HIP(c, hipMalloc((void**)&c->d_v2s_nodes, need_nodes * sizeof(uint32_t)));
+        c->cap_v2s_nodes = need_nodes;
+        c->n_device_allocs++;
+    }
+    // the shard's rows: bytes, leaves, the width of each piece's top tree over its column nodes, and the expected root
+    // words (big-endian values), SoA [8][pieces of the window] window after window: a window's launches see a table
+    // of their own at piece j0 (expected words at 8 * j0)
+    std::vector<uint32_t> tab(need_tab, 0);
+    st.v2_bytes.resize(c->count);
+    for (uint64_t j = 0; j < c->count; j++) {
+        const uint64_t i = c->first + j, j0 = j / wn * wn, wcount = std::min(wn, c->count - j0);
+        st.v2_bytes[j] = tab[j] = piece_bytes[i];
+        tab[c->count + j] = tree_leaves[i];
+        tab[2 * c->count + j] = std::max<uint32_t>(1, tree_leaves[i] >> st.v2_logc);
+        const uint8_t* d = hashes + 32 * i;
+        for (int k = 0; k < 8; k++)
+            tab[3 * c->count + 8 * j0 + (uint64_t)k * wcount + (j - j0)] =
+                ((uint32_t)d[4 * k] << 24) | ((uint32_t)d[4 * k + 1] << 16) | ((uint32_t)d[4 * k + 2] << 8) |
+                (uint32_t)d[4 * k + 3];
+    }
+    TV_HIP(c, hipMemcpyAsync(c->d_v2s_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    TV_HIP(c, hipStreamSynchronize(c->stream));   // (tab is the call's own)
+    TV_HIP(c, hipEventRecord(c->ev_call0, c->stream));
+    TV_HIP(c, hipMemsetAsync(c->d_out, 0, c->bit_words * 8, c->stream));  // fail closed, as tv_verify
+    TV_HIP(c, hipEventRecord(c->done_ev[0], c->stream));
+    TV_HIP(c, hipEventRecord(c->done_ev[1], c->stream));
+    st.active = true;
+    return TV_OK;
+}
+
+// A completed unit of a v2 stream: the column kernel on the chunk buffer, and after a window's last column its top
+// tree (one level launch per doubling of the columns, none when a column is a whole piece) and the finish launch into
+// the window's bitfield words.  done_ev[buf] follows the column kernel, the only launch that reads the buffer.
+int v2_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount) {
+    StreamState& st = c->st;
+    const uint64_t col = st.unit % st.ncol;
+    uint32_t* tab = c->d_v2s_tab;
+    TvV2Col k{};
+    k.data = c->d_chunk[buf];
+    k.stride = st.row_pitch;
+    k.n = (uint32_t)wcount;
+    k.logc = st.v2_logc;
+    k.logn = st.v2_logn;
+    k.col = (uint32_t)col;
+    k.piece_bytes = tab + j0;
+    k.tree_leaves = tab + c->count + j0;
+    k.nodes = c->d_v2s_nodes;
+    k.clock = c->clock_probe ? c->d_clock : nullptr;
+    TV_HIP(c, tv_v2_launch_column(k, c->stream, &c->last_workgroups));
+    st.launches++;
+    TV_HIP(c, hipEventRecord(c->done_ev[buf], c->stream));
+    if (col + 1 < st.ncol) return TV_OK;
+    TvV2 p{};
+    p.n = (uint32_t)wcount;
+    p.logW = st.v2_logn;
+    p.piece_bytes = tab + j0;
+    p.tree_leaves = tab + 2 * c->count + j0;
+    p.nodes_a = c->d_v2s_nodes;
+    p.nodes_b = c->d_v2s_nodes + 8 * wcount * st.ncol;
+    p.expect = tab + 3 * c->count + 8 * j0;
+    p.out64 = c->d_out + j0 / 64;   // (availability: st.av, applied at the end with the unreadable pieces)
+    p.out_words = (uint32_t)((wcount + 63) / 64);
+    for (uint32_t l = 0; l < st.v2_logn; l++) {
+        TV_HIP(c, tv_v2_launch_level(p, l, st.v2_logn, c->stream));
+        st.launches++;
+    }
+    TV_HIP(c, tv_v2_launch_finish(p, false, c->stream));
+    st.launches++;
+    return TV_OK;
+}
+
 int stream_next_locked(tv_ctx* c, tv_stream_req* req) {
     StreamState& st = c->st;
     if (!st.active) return fail(c, TV_ERR_STATE, "tv_stream_begin has not been called");
@@ -153,6 +290,55 @@ int stream_commit_locked(tv_ctx* c, const tv_stream_req* req, const uint8_t* src
     uint8_t* dst = c->d_chunk[buf] + st.row * st.row_pitch;
     uint8_t* slot = c->ring[st.slot];
     const uint64_t n = std::min(rows_copy, r.rows);
+    if (st.v2) {
+        // any row may be short or empty (every file ends a piece): runs of whole rows go as one 2D copy each, a short
+        // row as a copy of its own, an empty row (the piece ends before the column) is neither gathered nor copied
+        const uint8_t* from = slot;
+        uint64_t from_pitch = r.width;
+        if (src && pinned) {
+            from = src;
+            from_pitch = pitch;
+        } else if (src) {
+            const uint64_t per = std::max<uint64_t>(1, (4ull << 20) / r.width);  // rows per task, as gather_rows
+            c->pool[0].run(c->file_threads, (n + per - 1) / per, [&](uint64_t q) {
+                for (uint64_t k = q * per; k < std::min(n, (q + 1) * per); k++) {
+                    const uint64_t nb = v2_row_bytes(c, r.piece + k, r.offset, r.width);
+                    if (nb) tv_copy_host(slot + k * r.width, src + k * pitch, nb);
+                }
+            });
+        }
+        for (uint64_t q = 0; q < n;) {
+            const uint64_t nb = v2_row_bytes(c, r.piece + q, r.offset, r.width);
+            uint64_t e = q + 1;
+            if (nb == r.width) {
+                while (e < n && v2_row_bytes(c, r.piece + e, r.offset, r.width) == r.width) e++;
+                TV_HIP(c, hipMemcpy2DAsync(dst + q * st.row_pitch, st.row_pitch, from + q * from_pitch, from_pitch,
+                                           r.width, e - q, hipMemcpyHostToDevice, c->copy_stream));
+            } else if (nb) {
+                TV_HIP(c, hipMemcpyAsync(dst + q * st.row_pitch, from + q * from_pitch, nb, hipMemcpyHostToDevice,
+                                         c->copy_stream));
+            }
+            q = e;
+        }
+        st.outstanding = false;
+        const int s = st.slot;
+        st.slot = -1;
+        int rc = release_slot(c, s, 0);  // its event follows the copies just queued
+        if (rc) return rc;
+        st.row += r.rows;
+        if (st.row < wcount) return TV_OK;
+        TV_HIP(c, hipEventRecord(c->col_ev[buf], c->copy_stream));
+        TV_HIP(c, hipStreamWaitEvent(c->stream, c->col_ev[buf], 0));
+        if (!st.k0) {
+            TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
+            st.k0 = true;
+        }
+        rc = v2_unit_launch(c, buf, j0, wcount);
+        if (rc) return rc;
+        st.unit++;
+        st.row = 0;
+        return TV_OK;
+    }
     uint64_t full = n;  // rows [0, full) carry `width` bytes; only the torrent's short last piece has fewer
     if (full && row_bytes(c, r.piece + full - 1, r.offset, r.width) < r.width) full--;
     const uint64_t tail = full < n ? row_bytes(c, r.piece + full, r.offset, r.width) : 0;
@@ -228,7 +414,7 @@ int stream_end_locked(tv_ctx* c, uint8_t* bitfield_out) {
         }
         for (size_t k = 0; k < st.av.size(); k++) bitfield_out[k] &= st.av[k];  // unreadable pieces: bit 0
         c->last_kernel = st.kernel;
-        c->last_launches = (int)st.nunits;
+        c->last_launches = st.v2 ? st.launches : (int)st.nunits;
         rc = finish_timing(c);
         st = StreamState{};
         return rc;
@@ -245,94 +431,16 @@ int stream_result(tv_ctx* c, int rc) {
 }
 
 
-}  // namespace tvi
-
-using namespace tvi;
-
-extern "C" {
-
-// End-to-end verification from a host buffer holding the whole shard (tv_verify_host): the stream engine
-// with the caller's buffer as the producer.  Each request's rows are one 2D DMA straight from a page-locked
-// source (src pitch L) or are gathered into the request's ring slot first.  Rows past src_len are not
-// copied; their pieces are unreadable.
-int tv_verify_host(tv_ctx* c, const uint8_t* src, uint64_t src_len, const uint8_t* avail_bits,
-                   uint8_t* bitfield_out) {
-    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
-    std::lock_guard<std::mutex> g(c->mu);
-    int rc = require_layout(c, true);
-    if (rc) return rc;
-    if (!bitfield_out && c->count) return fail(c, TV_ERR_ARG, "bitfield_out is NULL");
-    if (!src && src_len) return fail(c, TV_ERR_ARG, "src is NULL");
-    if (!c->count) return TV_OK;
-    TV_HIP(c, hipSetDevice(c->device));
-    // pieces whose bytes extend past src_len are unreadable
-    std::vector<uint8_t> av((c->count + 7) / 8, 0);
-    for (uint64_t j = 0; j < c->count; j++) {
-        const uint64_t end = j * c->L + piece_len(c, c->first + j);
-        if (end <= src_len && (!avail_bits || get_bit(avail_bits, j))) set_bit(av.data(), j);
-    }
-    const bool pinned = is_pinned(src);
-    uint64_t col = 0, win = 0;   // windows x columns within the device budget (or 1 GiB), unless a width is set
-    if (!c->stream_chunk && !stream_rows(c))
-        budget_geometry(c, c->budget_opt ? c->budget_opt : (1ull << 30), 2048, &col, &win);
-    DrainGuard drain(c);  // no DMA reads the caller's buffer after the call returns, also on error paths
-    rc = stream_begin_locked(c, av.data(), col, win);
-    if (rc) {
-        stream_abort_locked(c);
-        return rc;
-    }
-    for (;;) {
-        tv_stream_req req;
-        rc = stream_next_locked(c, &req);
-        if (rc || !req.rows) break;
-        // rows wholly inside src: a prefix of the request (its rows ascend in linear offset)
-        const uint64_t base = (req.piece - c->first) * c->L + req.offset;
-        uint64_t k = 0;
-        while (k < req.rows && base + k * c->L + row_bytes(c, req.piece + k, req.offset, req.width) <= src_len) k++;
-        rc = stream_commit_locked(c, &req, k ? src + base : nullptr, c->L, pinned, k);
-        if (rc) break;
-    }
-    if (rc) {
-        stream_abort_locked(c);
-        return rc;
-    }
-    return stream_end_locked(c, bitfield_out);
-}
-
-// The resume check from FILES through the bounded ring (tv_stream_file_table): the stream engine with the library's
-// own readers as the producer.  Each request's rows (bytes [offset, offset + width) of consecutive pieces: a column
-// across the shard) are read by the lane-0 pool straight from the files into the request's ring slot, each row's
-// linear range walked over the file table as Storage.get walks it (storage.ts:98-137); the kernels hash one column
-// while the next is read.  Device memory: two columns (TV_OPT_STREAM_CHUNK bytes of every shard piece), so a shard
-// verifies under a small device budget with every piece's SHA-1 advancing at once, where windows of whole pieces
-// pay one piece's serial SHA-1 per window.  A piece is unreadable exactly when fsStorage.get would return null
-// for it: a byte of it in a missing, unopenable or too-short file, a zero-length segment of its walk whose open
-// fails (storage.ts:109-110,158), or bytes past the files' end.  Files are opened as fsStorage.get opens them
-// (TV_OPT_OPEN_RW), kept open for the call, never created.
-int tv_stream_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const char* paths, uint64_t paths_bytes,
-                         const uint8_t* avail_bits, uint8_t* bitfield_out, int32_t* status_out) {
-    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
-    std::lock_guard<std::mutex> g(c->mu);
-    int rc = require_layout(c, true);
-    if (rc) return rc;
-    if (!bitfield_out && c->count) return fail(c, TV_ERR_ARG, "bitfield_out is NULL");
-    if (n && (!lengths || !paths || !status_out)) return fail(c, TV_ERR_ARG, "NULL argument");
-    std::vector<const char*> path(n);
-    std::vector<uint64_t> start(n + 1, 0);   // file k's linear bytes: [start[k], start[k + 1])
-    for (uint64_t k = 0, o = 0; k < n; k++) {
-        const void* z = o < paths_bytes ? memchr(paths + o, 0, paths_bytes - o) : nullptr;
-        if (!z)
-            return fail(c, TV_ERR_ARG, "paths holds %llu NUL-terminated paths in %llu bytes, the table %llu files",
-                        (unsigned long long)k, (unsigned long long)paths_bytes, (unsigned long long)n);
-        path[k] = paths + o;
-        o = (uint64_t)((const char*)z - paths) + 1;
-        if (lengths[k] > UINT64_MAX - start[k])
-            return fail(c, TV_ERR_ARG, "file %llu: the lengths overflow 64-bit offsets", (unsigned long long)k);
-        start[k + 1] = start[k] + lengths[k];
-        status_out[k] = TV_OK;
-    }
-    if (!c->count) return TV_OK;
-    TV_HIP(c, hipSetDevice(c->device));
+// The reader loop of tv_stream_file_table and tv_v2_stream_file_table: the stream engine with the library's own
+// readers as the producer.  File k's bytes are the LINEAR bytes [start[k], start[k] + lengths[k]) (v1: the files back
+// to back; v2: every file at the next piece boundary, tv_plan.h v2_file_starts); `rule` gives a request row's valid
+// bytes; begin(cold) starts the stream (its geometry and availability are the caller's) once the shard's files are
+// known to be mostly in the page cache or not.  Each row's range is walked over the files and read into the request's
+// ring slot by the lane-0 pool; a row that a missing, unopenable or short file cannot fill makes its piece unreadable
+// and the file's status TV_ERR_IO.
+int stream_files_locked(tv_ctx* c, uint64_t n, const uint64_t* lengths, const std::vector<const char*>& path,
+                        const std::vector<uint64_t>& start, RowBytes rule, const std::function<int(bool)>& begin,
+                        uint8_t* bitfield_out, int32_t* status_out) {
     const uint64_t last = c->first + c->count - 1;
     const uint64_t lo = c->first * c->L, hi = std::min(c->total, last * c->L + piece_len(c, last));
     // Whether the shard's files are mostly not in the page cache (TV_OPT_FILE_ODIRECT): up to 16 of the files holding
@@ -343,14 +451,14 @@ int tv_stream_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const c
     if (c->file_odirect) {
         std::vector<uint64_t> big;
         for (uint64_t k = 0; k < n; k++) {
-            const uint64_t a = std::max(lo, start[k]), b = std::min(hi, start[k + 1]);
+            const uint64_t a = std::max(lo, start[k]), b = std::min(hi, start[k] + lengths[k]);
             if (b > a && b - a >= (1u << 20) && path[k][0]) big.push_back(k);
         }
         double hit = 0, all = 0;
         const size_t m = std::min<size_t>(16, big.size());
         for (size_t q = 0; q < m; q++) {
             const uint64_t k = big[q * big.size() / m];
-            const uint64_t a = std::max(lo, start[k]), b = std::min(hi, start[k + 1]);
+            const uint64_t a = std::max(lo, start[k]), b = std::min(hi, start[k] + lengths[k]);
             // (nonblocking: a FIFO in the table must not hang the sample; only regular files are sampled)
             const int fd = open(path[k], O_RDONLY | O_NONBLOCK | O_CLOEXEC);
             if (fd < 0) continue;
@@ -362,35 +470,6 @@ int tv_stream_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const c
             all += (double)(b - a);
         }
         cold = all > 0 && hit < 0.5 * all;
-    }
-    // Geometry: windows x columns within the budget (TV_OPT_RESIDENT_BUDGET, or 1 GiB); a cold shard's windows are
-    // 512 pieces (rows 4 x longer; ~44 GB/s of hashing, above what the disk gives).  An explicit TV_OPT_STREAM_CHUNK
-    // keeps the engine's columns across the whole shard.
-    uint64_t col = 0, win = 0;
-    if (!c->stream_chunk) {
-        const uint64_t min_win = cold ? (c->stream_cold_window ? c->stream_cold_window : 512) : 2048;
-        budget_geometry(c, c->budget_opt ? c->budget_opt : (1ull << 30), min_win, &col, &win);
-    }
-    // availability before any read: the caller's bits, pieces past the files' end, and the pieces whose walk has a
-    // zero-length segment whose open fails (the same segments tv_stage_file_table checks)
-    std::vector<uint8_t> av((c->count + 7) / 8, 0);
-    for (uint64_t j = 0; j < c->count; j++) {
-        const uint64_t i = c->first + j, end = i * c->L + piece_len(c, i);
-        if (end <= std::min(c->total, start[n]) && (!avail_bits || get_bit(avail_bits, j))) set_bit(av.data(), j);
-    }
-    {
-        std::vector<TableSeg> segs;
-        uint64_t bad = 0, reached = 0;
-        if (!walk_file_table(n, lengths, lo, hi, c->L, &segs, &bad, &reached))
-            return fail(c, TV_ERR_ARG, "file %llu: the lengths overflow 64-bit offsets", (unsigned long long)bad);
-        for (const TableSeg& sg : segs) {
-            if (sg.len || sg.linear < lo || sg.linear >= hi) continue;
-            if (fs_openable(path[sg.file], c->open_rw)) {
-                status_out[sg.file] = TV_ERR_IO;
-                const uint64_t j = sg.linear / c->L - c->first;
-                av[j >> 3] &= (uint8_t)~(0x80u >> (j & 7));
-            }
-        }
     }
     // the call's open files: the first kCachedFds opened stay open until the end (a one- or few-file torrent opens
     // each once); past that a reader opens and closes the file around its read (as fsStorage.get does per call), so
@@ -502,7 +581,7 @@ int tv_stream_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const c
     };
     const int readers = cold ? (c->stream_cold_readers ? c->stream_cold_readers : 2 * c->file_threads) : c->file_threads;
     DrainGuard drain(c);  // (the ring's copies and the column kernels are done when the call returns)
-    rc = stream_begin_locked(c, av.data(), col, win, cold ? c->stream_cold_req : 0);
+    int rc = begin(cold);
     if (rc) {
         stream_abort_locked(c);
         return rc;
@@ -517,15 +596,19 @@ int tv_stream_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const c
         std::vector<uint8_t> row_bad(req.rows, 0);
         c->pool[0].run(readers, req.rows, [&](uint64_t q) {
             const uint64_t i = req.piece + q, j = i - c->first;
-            const uint64_t nb = row_bytes(c, i, req.offset, req.width);
+            const uint64_t nb = rule(c, i, req.offset, req.width);
             if (!nb || !get_bit(c->st.av.data(), j)) return;
             const uint64_t a = i * c->L + req.offset, b = a + nb;   // the row's linear bytes
             uint8_t* out = slot + q * req.width;
             // the file holding byte a: the last k with start[k] <= a < start[k + 1] (zero-length files skipped)
             uint64_t k = (uint64_t)(std::upper_bound(start.begin(), start.end(), a) - start.begin()) - 1;
             for (uint64_t pos = a; pos < b && k < n; k++) {
-                if (start[k + 1] <= pos) continue;
-                const uint64_t e = std::min(b, start[k + 1]);
+                if (start[k] + lengths[k] <= pos) continue;
+                if (pos < start[k]) {   // (a row reaching into the gap after a file: its table and files disagree)
+                    row_bad[q] = 1;
+                    return;
+                }
+                const uint64_t e = std::min(b, start[k] + lengths[k]);
                 bool own = false;
                 int dfd = -1;
                 const int fd = fd_of(k, &own, &dfd);
@@ -577,6 +660,130 @@ int tv_stream_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const c
     return stream_end_locked(c, bitfield_out);
 }
 
+}  // namespace tvi
+
+using namespace tvi;
+
+extern "C" {
+
+// End-to-end verification from a host buffer holding the whole shard (tv_verify_host): the stream engine
+// with the caller's buffer as the producer.  Each request's rows are one 2D DMA straight from a page-locked
+// source (src pitch L) or are gathered into the request's ring slot first.  Rows past src_len are not
+// copied; their pieces are unreadable.
+int tv_verify_host(tv_ctx* c, const uint8_t* src, uint64_t src_len, const uint8_t* avail_bits,
+                   uint8_t* bitfield_out) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = require_layout(c, true);
+    if (rc) return rc;
+    if (!bitfield_out && c->count) return fail(c, TV_ERR_ARG, "bitfield_out is NULL");
+    if (!src && src_len) return fail(c, TV_ERR_ARG, "src is NULL");
+    if (!c->count) return TV_OK;
+    TV_HIP(c, hipSetDevice(c->device));
+    // pieces whose bytes extend past src_len are unreadable
+    std::vector<uint8_t> av((c->count + 7) / 8, 0);
+    for (uint64_t j = 0; j < c->count; j++) {
+        const uint64_t end = j * c->L + piece_len(c, c->first + j);
+        if (end <= src_len && (!avail_bits || get_bit(avail_bits, j))) set_bit(av.data(), j);
+    }
+    const bool pinned = is_pinned(src);
+    uint64_t col = 0, win = 0;   // windows x columns within the device budget (or 1 GiB), unless a width is set
+    if (!c->stream_chunk && !stream_rows(c))
+        budget_geometry(c, c->budget_opt ? c->budget_opt : (1ull << 30), 2048, &col, &win);
+    DrainGuard drain(c);  // no DMA reads the caller's buffer after the call returns, also on error paths
+    rc = stream_begin_locked(c, av.data(), col, win);
+    if (rc) {
+        stream_abort_locked(c);
+        return rc;
+    }
+    for (;;) {
+        tv_stream_req req;
+        rc = stream_next_locked(c, &req);
+        if (rc || !req.rows) break;
+        // rows wholly inside src: a prefix of the request (its rows ascend in linear offset)
+        const uint64_t base = (req.piece - c->first) * c->L + req.offset;
+        uint64_t k = 0;
+        while (k < req.rows && base + k * c->L + row_bytes(c, req.piece + k, req.offset, req.width) <= src_len) k++;
+        rc = stream_commit_locked(c, &req, k ? src + base : nullptr, c->L, pinned, k);
+        if (rc) break;
+    }
+    if (rc) {
+        stream_abort_locked(c);
+        return rc;
+    }
+    return stream_end_locked(c, bitfield_out);
+}
+
+// The resume check from FILES through the bounded ring (tv_stream_file_table): the stream engine with the library's
+// own readers as the producer.  Each request's rows (bytes [offset, offset + width) of consecutive pieces: a column
+// across the shard) are read by the lane-0 pool straight from the files into the request's ring slot, each row's
+// linear range walked over the file table as Storage.get walks it (storage.ts:98-137); the kernels hash one column
+// while the next is read.  Device memory: two columns (TV_OPT_STREAM_CHUNK bytes of every shard piece), so a shard
+// verifies under a small device budget with every piece's SHA-1 advancing at once, where windows of whole pieces
+// pay one piece's serial SHA-1 per window.  A piece is unreadable exactly when fsStorage.get would return null
+// for it: a byte of it in a missing, unopenable or too-short file, a zero-length segment of its walk whose open
+// fails (storage.ts:109-110,158), or bytes past the files' end.  Files are opened as fsStorage.get opens them
+// (TV_OPT_OPEN_RW), kept open for the call, never created.
+int tv_stream_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const char* paths, uint64_t paths_bytes,
+                         const uint8_t* avail_bits, uint8_t* bitfield_out, int32_t* status_out) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = require_layout(c, true);
+    if (rc) return rc;
+    if (!bitfield_out && c->count) return fail(c, TV_ERR_ARG, "bitfield_out is NULL");
+    if (n && (!lengths || !paths || !status_out)) return fail(c, TV_ERR_ARG, "NULL argument");
+    std::vector<const char*> path(n);
+    std::vector<uint64_t> start(n + 1, 0);   // file k's linear bytes: [start[k], start[k + 1])
+    for (uint64_t k = 0, o = 0; k < n; k++) {
+        const void* z = o < paths_bytes ? memchr(paths + o, 0, paths_bytes - o) : nullptr;
+        if (!z)
+            return fail(c, TV_ERR_ARG, "paths holds %llu NUL-terminated paths in %llu bytes, the table %llu files",
+                        (unsigned long long)k, (unsigned long long)paths_bytes, (unsigned long long)n);
+        path[k] = paths + o;
+        o = (uint64_t)((const char*)z - paths) + 1;
+        if (lengths[k] > UINT64_MAX - start[k])
+            return fail(c, TV_ERR_ARG, "file %llu: the lengths overflow 64-bit offsets", (unsigned long long)k);
+        start[k + 1] = start[k] + lengths[k];
+        status_out[k] = TV_OK;
+    }
+    if (!c->count) return TV_OK;
+    TV_HIP(c, hipSetDevice(c->device));
+    const uint64_t last = c->first + c->count - 1;
+    const uint64_t lo = c->first * c->L, hi = std::min(c->total, last * c->L + piece_len(c, last));
+    // availability before any read: the caller's bits, pieces past the files' end, and the pieces whose walk has a
+    // zero-length segment whose open fails (the same segments tv_stage_file_table checks)
+    std::vector<uint8_t> av((c->count + 7) / 8, 0);
+    for (uint64_t j = 0; j < c->count; j++) {
+        const uint64_t i = c->first + j, end = i * c->L + piece_len(c, i);
+        if (end <= std::min(c->total, start[n]) && (!avail_bits || get_bit(avail_bits, j))) set_bit(av.data(), j);
+    }
+    {
+        std::vector<TableSeg> segs;
+        uint64_t bad = 0, reached = 0;
+        if (!walk_file_table(n, lengths, lo, hi, c->L, &segs, &bad, &reached))
+            return fail(c, TV_ERR_ARG, "file %llu: the lengths overflow 64-bit offsets", (unsigned long long)bad);
+        for (const TableSeg& sg : segs) {
+            if (sg.len || sg.linear < lo || sg.linear >= hi) continue;
+            if (fs_openable(path[sg.file], c->open_rw)) {
+                status_out[sg.file] = TV_ERR_IO;
+                const uint64_t j = sg.linear / c->L - c->first;
+                av[j >> 3] &= (uint8_t)~(0x80u >> (j & 7));
+            }
+        }
+    }
+    // Geometry: windows x columns within the budget (TV_OPT_RESIDENT_BUDGET, or 1 GiB); a cold shard's windows are
+    // 512 pieces (rows 4 x longer; ~44 GB/s of hashing, above what the disk gives).  An explicit TV_OPT_STREAM_CHUNK
+    // keeps the engine's columns across the whole shard.
+    return stream_files_locked(c, n, lengths, path, start, row_bytes, [&](bool cold) {
+        uint64_t col = 0, win = 0;
+        if (!c->stream_chunk) {
+            const uint64_t min_win = cold ? (c->stream_cold_window ? c->stream_cold_window : 512) : 2048;
+            budget_geometry(c, c->budget_opt ? c->budget_opt : (1ull << 30), min_win, &col, &win);
+        }
+        return stream_begin_locked(c, av.data(), col, win, cold ? c->stream_cold_req : 0);
+    }, bitfield_out, status_out);
+}
+
 int tv_stream_begin(tv_ctx* c, const uint8_t* avail_bits) {
     if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
     std::lock_guard<std::mutex> g(c->mu);
@@ -584,6 +791,70 @@ int tv_stream_begin(tv_ctx* c, const uint8_t* avail_bits) {
     if (rc) return rc;
     TV_HIP(c, hipSetDevice(c->device));
     return stream_result(c, stream_begin_locked(c, avail_bits));
+}
+
+int tv_v2_stream_begin(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const uint32_t* tree_leaves,
+                       const uint8_t* hashes, const uint8_t* avail_bits) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = require_layout(c, false);
+    if (rc) return rc;
+    rc = v2_check_table(c, n, piece_bytes, tree_leaves);
+    if (rc) return rc;
+    if (n && !hashes) return fail(c, TV_ERR_ARG, "NULL argument");
+    TV_HIP(c, hipSetDevice(c->device));
+    rc = v2_stream_begin_locked(c, piece_bytes, tree_leaves, hashes, avail_bits);
+    if (rc) c->st = StreamState{};   // (a failed begin leaves no stream, v2 or other)
+    return rc;
+}
+
+// The v2 resume check from FILES through the bounded ring: tv_stream_file_table's reader loop over the ALIGNED file
+// table (every file starts a piece), the rows ending with their piece's bytes.  A v2 piece lies in one file, so it is
+// unreadable exactly when that file cannot supply its bytes; there are no zero-length segments to open.
+int tv_v2_stream_file_table(tv_ctx* c, uint64_t n_pieces, const uint32_t* piece_bytes, const uint32_t* tree_leaves,
+                            const uint8_t* hashes, uint64_t n, const uint64_t* lengths, const char* paths,
+                            uint64_t paths_bytes, const uint8_t* avail_bits, uint8_t* bitfield_out,
+                            int32_t* status_out) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = require_layout(c, false);
+    if (rc) return rc;
+    rc = v2_check_table(c, n_pieces, piece_bytes, tree_leaves);
+    if (rc) return rc;
+    if (n_pieces && !hashes) return fail(c, TV_ERR_ARG, "NULL argument");
+    if (!bitfield_out && c->count) return fail(c, TV_ERR_ARG, "bitfield_out is NULL");
+    if (n && (!lengths || !paths || !status_out)) return fail(c, TV_ERR_ARG, "NULL argument");
+    std::vector<const char*> path(n);
+    for (uint64_t k = 0, o = 0; k < n; k++) {
+        const void* z = o < paths_bytes ? memchr(paths + o, 0, paths_bytes - o) : nullptr;
+        if (!z)
+            return fail(c, TV_ERR_ARG, "paths holds %llu NUL-terminated paths in %llu bytes, the table %llu files",
+                        (unsigned long long)k, (unsigned long long)paths_bytes, (unsigned long long)n);
+        path[k] = paths + o;
+        o = (uint64_t)((const char*)z - paths) + 1;
+    }
+    std::vector<uint64_t> start;   // file k's linear bytes: [start[k], start[k] + lengths[k])
+    uint64_t bad = 0;
+    if (!v2_file_starts(n, lengths, c->L, &start, &bad))
+        return fail(c, TV_ERR_ARG, "file %llu: the lengths overflow 64-bit offsets", (unsigned long long)bad);
+    if (start[n] / c->L != n_pieces)
+        return fail(c, TV_ERR_ARG, "the files hold %llu pieces, the piece table %llu", (unsigned long long)(start[n] / c->L),
+                    (unsigned long long)n_pieces);
+    // every piece's bytes are its file's (so a row never reaches past its file into the gap before the next one)
+    for (uint64_t k = 0; k < n; k++)
+        for (uint64_t p = start[k] / c->L, o = 0; o < lengths[k]; p++, o += c->L)
+            if (piece_bytes[p] != std::min<uint64_t>(c->L, lengths[k] - o))
+                return fail(c, TV_ERR_ARG, "piece_bytes[%llu] = %llu, but file %llu holds %llu bytes of that piece",
+                            (unsigned long long)p, (unsigned long long)piece_bytes[p], (unsigned long long)k,
+                            (unsigned long long)std::min<uint64_t>(c->L, lengths[k] - o));
+    for (uint64_t k = 0; k < n; k++) status_out[k] = TV_OK;
+    if (!c->count) return TV_OK;
+    TV_HIP(c, hipSetDevice(c->device));
+    rc = stream_files_locked(c, n, lengths, path, start, v2_row_bytes, [&](bool cold) {
+        return v2_stream_begin_locked(c, piece_bytes, tree_leaves, hashes, avail_bits, cold ? c->stream_cold_req : 0);
+    }, bitfield_out, status_out);
+    if (rc && !c->st.active) c->st = StreamState{};
+    return rc;
 }
 
 int tv_stream_next(tv_ctx* c, tv_stream_req* req) {
@@ -646,9 +917,10 @@ int tv_stream_fill_synthetic(tv_ctx* c, const tv_stream_req* req, uint64_t seed)
     if (!req || req->seq != st.req.seq) return fail(c, TV_ERR_ARG, "the request does not match the outstanding one");
     const tv_stream_req r = st.req;
     uint8_t* slot = c->ring[st.slot];
+    const RowBytes rule = stream_row_rule(c);   // (a v2 stream's rows end with their piece's bytes)
     c->pool[0].run(c->file_threads, r.rows, [&](uint64_t q) {
         const uint64_t i = r.piece + q;
-        tv_synth_fill_host(seed, i * c->L + r.offset, row_bytes(c, i, r.offset, r.width), slot + q * r.width);
+        tv_synth_fill_host(seed, i * c->L + r.offset, rule(c, i, r.offset, r.width), slot + q * r.width);
     });
     return TV_OK;
 }

@@ -22,25 +22,58 @@ static void free_v2_list(tv_ctx* c) {
     c->v2_list_cap = 0;
 }
 
+static void free_v2_stream(tv_ctx* c) {
+    (void)hipFree(c->d_v2s_tab); c->d_v2s_tab = nullptr;
+    (void)hipFree(c->d_v2s_nodes); c->d_v2s_nodes = nullptr;
+    c->cap_v2s_tab = c->cap_v2s_nodes = 0;
+}
+
 void free_v2(tv_ctx* c) {
     free_v2_table(c);
     free_v2_list(c);
+    free_v2_stream(c);
 }
 
 static bool v2_piece_length_ok(uint64_t L) { return L >= TV_V2_LEAF_BYTES && (L & (L - 1)) == 0; }
 
 // Words of the two level buffers for `count` pieces of W leaves: A [8][count x W], B [8][count x max(W/2, 1)].
-static uint64_t v2_node_words(uint64_t count, uint64_t W) { return 8 * count * (W + (W > 1 ? W / 2 : 1)); }
+uint64_t v2_node_words(uint64_t count, uint64_t W) { return 8 * count * (W + (W > 1 ? W / 2 : 1)); }
 
 void v2_on_layout(tv_ctx* c) {
     c->v2_set = c->v2_hashes = false;
     if (c->v2_list_cap > std::max<uint64_t>(1024, 2 * c->count)) free_v2_list(c);   // (as tv_verify_list's buffers)
+    // a v2 stream's table and nodes: kept for a layout a v2 stream could run on and whose table they fit
+    if ((c->d_v2s_tab || c->d_v2s_nodes) &&
+        !(v2_piece_length_ok(c->L) && c->count && reuse_fits(11 * c->count, c->cap_v2s_tab)))
+        free_v2_stream(c);
     if (!c->d_v2_tab && !c->d_v2_nodes) return;
     // keep what a v2 table of the new geometry would reuse; anything else goes (a v1 layout holds no v2 memory)
     const bool v2 = v2_piece_length_ok(c->L) && c->count && !c->win && !c->slots;
     if (!v2 || !reuse_fits(c->count, c->cap_v2_count) ||
         !reuse_fits(v2_node_words(c->count, c->L / TV_V2_LEAF_BYTES), c->cap_v2_nodes))
         free_v2_table(c);
+}
+
+int v2_check_table(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const uint32_t* tree_leaves) {
+    if (!v2_piece_length_ok(c->L))
+        return fail(c, TV_ERR_ARG, "a v2 piece length is a power of two >= %d (the layout has %llu)", TV_V2_LEAF_BYTES,
+                    (unsigned long long)c->L);
+    if (n != c->P)
+        return fail(c, TV_ERR_ARG, "the piece table has %llu entries, the layout %llu pieces", (unsigned long long)n,
+                    (unsigned long long)c->P);
+    if (n && (!piece_bytes || !tree_leaves)) return fail(c, TV_ERR_ARG, "NULL argument");
+    const uint64_t W = c->L / TV_V2_LEAF_BYTES;
+    for (uint64_t p = 0; p < n; p++) {
+        const uint64_t b = piece_bytes[p], w = tree_leaves[p];
+        if (b == 0 || b > c->L)
+            return fail(c, TV_ERR_ARG, "piece_bytes[%llu] = %llu is outside 1 .. %llu", (unsigned long long)p,
+                        (unsigned long long)b, (unsigned long long)c->L);
+        if (w == 0 || (w & (w - 1)) || w < (b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES || w > W)
+            return fail(c, TV_ERR_ARG, "tree_leaves[%llu] = %llu is not a power of two in %llu .. %llu",
+                        (unsigned long long)p, (unsigned long long)w,
+                        (unsigned long long)((b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES), (unsigned long long)W);
+    }
+    return TV_OK;
 }
 
 }  // namespace tvi
@@ -121,24 +154,9 @@ int tv_v2_set_pieces(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const u
     int rc = v2_require(c, "tv_v2_set_pieces");
     if (rc) return rc;
     c->v2_set = c->v2_hashes = false;
-    if (!v2_piece_length_ok(c->L))
-        return fail(c, TV_ERR_ARG, "a v2 piece length is a power of two >= %d (the layout has %llu)", TV_V2_LEAF_BYTES,
-                    (unsigned long long)c->L);
-    if (n != c->P)
-        return fail(c, TV_ERR_ARG, "the piece table has %llu entries, the layout %llu pieces", (unsigned long long)n,
-                    (unsigned long long)c->P);
-    if (n && (!piece_bytes || !tree_leaves)) return fail(c, TV_ERR_ARG, "NULL argument");
+    rc = v2_check_table(c, n, piece_bytes, tree_leaves);
+    if (rc) return rc;
     const uint64_t W = c->L / TV_V2_LEAF_BYTES;
-    for (uint64_t p = 0; p < n; p++) {
-        const uint64_t b = piece_bytes[p], w = tree_leaves[p];
-        if (b == 0 || b > c->L)
-            return fail(c, TV_ERR_ARG, "piece_bytes[%llu] = %llu is outside 1 .. %llu", (unsigned long long)p,
-                        (unsigned long long)b, (unsigned long long)c->L);
-        if (w == 0 || (w & (w - 1)) || w < (b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES || w > W)
-            return fail(c, TV_ERR_ARG, "tree_leaves[%llu] = %llu is not a power of two in %llu .. %llu",
-                        (unsigned long long)p, (unsigned long long)w,
-                        (unsigned long long)((b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES), (unsigned long long)W);
-    }
     uint32_t logW = 0;
     while ((1ull << logW) < W) logW++;
     c->v2_logW = logW;

@@ -14,6 +14,9 @@
 //                   bitfield words (as tv_compare_kernel), or the root out (creation mode).
 //   list kernel   : tv_v2_verify_list's single launch: the leaf hashing above, then the piece's tree levels in LDS
 //                   inside the workgroup, root against the entry's expected hash -> one byte per entry.
+//   column kernel : a streamed verify's unit (tv_v2_stream_begin): a column of every piece of a window is a whole aligned
+//                   subtree of each piece, hashed and reduced in LDS to one node per piece; the level and finish
+//                   kernels then run over those nodes.
 // Which lane hashes which leaf (TvV2::map): consecutive leaves of a piece (addresses 16 KiB apart), or one leaf index
 // of 64 consecutive pieces (addresses `stride` apart, the layout the SHA-1 lane kernel reads).
 #include <hip/hip_runtime.h>
@@ -211,7 +214,8 @@ __global__ __launch_bounds__(256) void tv_v2_finish_kernel(TvV2 p) {
     }
     if (HASH) return;
     const uint64_t mask = __ballot(ok);
-    if ((threadIdx.x & 63u) == 0) {   // lane 0 of the wave: pieces j .. j + 63, word j >> 6
+    // lane 0 of the wave: pieces j .. j + 63, word j >> 6 (a streamed window's launch stops at its own words)
+    if ((threadIdx.x & 63u) == 0 && (p.out_words == 0 || (j >> 6) < p.out_words)) {
         uint64_t bits = __builtin_bswap64(__builtin_bitreverse64(mask));   // ballot bit l -> MSB-first bytes
         if (p.avail64) bits &= p.avail64[j >> 6];
         p.out64[j >> 6] = bits;
@@ -315,8 +319,106 @@ __global__ __launch_bounds__(256) void tv_v2_list_kernel(TvV2List p) {
 }
 
 // ------------------------------------------------------------------------------------------
+// column kernel (a streamed verify, tv_v2_stream_begin): one column of a window of pieces.  A column of a piece is c
+// = 1 << logc consecutive leaves starting at a multiple of c: a whole aligned subtree, so nothing is carried from one
+// column to the next -- the workgroup that hashes the leaves reduces them in LDS to the subtree's root (level
+// min(logc, log2 w) of a piece whose tree is w leaves wide) and stores that ONE node; the window's top tree over the
+// L / C nodes of each piece runs in the level and finish kernels after the last column.
+//   c <= 256: a workgroup covers G = 256 / c consecutive rows of the chunk buffer, one lane per leaf (one tile).
+//   c  > 256: a workgroup owns one row and walks it in c / 256 tiles, as the list kernel walks a piece.
+// A leaf position inside the tree but past the piece's bytes is a zero hash and reads no memory (its row of the chunk
+// buffer may hold an earlier window's bytes there, or nothing); a column wholly past the bytes therefore reduces zero
+// hashes to the true all-zero subtree root.  A piece whose tree ends before the column stores nothing.
+// As in the list kernel, every loop that holds a barrier runs on logc alone and no lane returns early; TILED keeps
+// the tile loop out of the one-tile instantiation (its register count: see tv_v2_list_kernel).
+// ------------------------------------------------------------------------------------------
+namespace {
+
+__device__ __forceinline__ void column_store(const TvV2Col& p, uint32_t j, const uint32_t h[8]) {
+    const uint64_t np = (uint64_t)p.n << p.logn, slot = ((uint64_t)j << p.logn) + p.col;
+#pragma unroll
+    for (int q = 0; q < 8; q++) p.nodes[q * np + slot] = h[q];
+}
+
+}  // namespace
+
+template <bool TILED>
+__global__ __launch_bounds__(256) void tv_v2_column_kernel(TvV2Col p) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_node[8][256];   // the tile's current level, SoA
+    __shared__ __attribute__((aligned(16))) uint32_t s_root[8][256];   // c > 256: the tiles' subtree roots (<= 16 of them)
+    __shared__ uint32_t s_tg[256];        // the level at which row g's node is complete (0xFF: no row, or out of reach)
+    uint64_t t0 = 0, r0 = 0;
+    if (p.clock && blockIdx.x == 0) {   // clock probe, as the leaf kernel's
+        t0 = __builtin_amdgcn_s_memtime();
+        r0 = __builtin_amdgcn_s_memrealtime();
+    }
+    const uint32_t t = threadIdx.x;
+    const uint32_t logc = p.logc, logT = logc < 8u ? logc : 8u;   // a tile holds 1 << logT leaves of a row
+    const uint32_t tiles = 1u << (logc - logT);
+    const uint32_t j0 = blockIdx.x << (8u - logT);                // the workgroup's first row
+    const uint32_t j = j0 + (t >> logT), kt = t & ((1u << logT) - 1u);
+    const bool valid = j < p.n;
+    const uint32_t bytes = valid ? p.piece_bytes[j] : 0;
+    const uint32_t wj = valid ? p.tree_leaves[j] : 0;
+    const uint64_t k0 = (uint64_t)p.col << logc;                  // the column's first leaf
+    const bool reach = k0 < wj;                                   // the piece's tree reaches this column
+    const uint32_t lw = wj ? 31u - (uint32_t)__builtin_clz(wj) : 0u;
+    const uint32_t target = lw < logc ? lw : logc;
+    const uint8_t* row = p.data + (valid ? (uint64_t)j * p.stride : 0);
+    if (kt == 0) s_tg[t >> logT] = reach ? target : 0xFFu;
+    uint32_t h[8];
+    for (uint32_t T = 0; T < (TILED ? tiles : 1u); T++) {
+        const uint32_t kr = (T << logT) + kt;                     // leaf of the column (its 16 KiB of the row)
+        const uint64_t lo = (k0 + kr) * kLeaf;                    // ... and its first byte in the piece
+        const bool active = k0 + kr < wj && lo < bytes;           // the leaf holds >= 1 valid byte
+        const uint32_t len = active ? (uint32_t)(bytes - lo < kLeaf ? bytes - lo : kLeaf) : 0;
+        hash_leaf(row + (uint64_t)kr * kLeaf, len, active, h);
+        if (!active) {   // a padding leaf (or no row): a zero hash, and no memory read
+#pragma unroll
+            for (int q = 0; q < 8; q++) h[q] = 0;
+        }
+        if (T == 0 && kt == 0 && reach && target == 0) column_store(p, j, h);   // c == 1 or a one-leaf tree
+#pragma unroll
+        for (int q = 0; q < 8; q++) s_node[q][t] = h[q];
+        __syncthreads();
+        for (uint32_t l = 0; l < logT; l++) {
+            if (!list_level(s_node, t, 256u >> (l + 1u), h)) continue;
+            const uint32_t sh = logT - l - 1u, g = t >> sh;       // node t is node (t & mask) of row g's level l + 1
+            if ((t & ((1u << sh) - 1u)) != 0) continue;
+            if (T == 0 && s_tg[g] == l + 1u) column_store(p, j0 + g, h);
+            if (tiles > 1 && sh == 0) {                           // (lane 0) the tile's subtree root
+#pragma unroll
+                for (int q = 0; q < 8; q++) s_root[q][T] = h[q];
+            }
+        }
+    }
+    // c > 256: the tile roots' levels 8 .. logc - 1 (lane 0 stored the last tile's root after that tile's last barrier)
+    if (TILED) __syncthreads();
+    for (uint32_t l = 8; l < logc; l++)
+        if (list_level(s_root, t, tiles >> (l - 7u), h) && t == 0 && s_tg[0] == l + 1u) column_store(p, j0, h);
+    if (p.clock && blockIdx.x == 0 && threadIdx.x == 0) {
+        const uint64_t t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+        reinterpret_cast<ulonglong2*>(p.clock)[0] = make_ulonglong2(t0, r0);
+        reinterpret_cast<ulonglong2*>(p.clock)[1] = make_ulonglong2(t1, r1);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // host-side launchers (tv_v2.hip)
 // ------------------------------------------------------------------------------------------
+hipError_t tv_v2_launch_column(const TvV2Col& p, hipStream_t s, uint32_t* workgroups) {
+    if (workgroups) *workgroups = 0;
+    if (p.n == 0) return hipSuccess;
+    if (p.logc > TV_V2_COL_MAX_LOGC || (p.col >> p.logn) != 0) return hipErrorInvalidValue;
+    const uint32_t logG = p.logc < 8u ? 8u - p.logc : 0u;   // rows per workgroup: max(1, 256 / c)
+    const uint64_t grid = (((uint64_t)p.n - 1) >> logG) + 1;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    if (workgroups) *workgroups = (uint32_t)grid;
+    if (p.logc > 8u) hipLaunchKernelGGL(tv_v2_column_kernel<true>, dim3((unsigned)grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(tv_v2_column_kernel<false>, dim3((unsigned)grid), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
 hipError_t tv_v2_launch_leaves(const TvV2& p, hipStream_t s, uint32_t* workgroups) {
     if (workgroups) *workgroups = 0;
     if (p.n == 0) return hipSuccess;

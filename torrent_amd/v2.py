@@ -5,27 +5,33 @@ a piece: the leaf kernel hashes every block of the resident shard side by side a
 piece roots (torrent_amd/csrc/tv_v2_kernels.hip).  The host's part is the piece table (metainfo_v2.V2Layout) and the
 staging: every file starts a new piece, so file k is staged at its ALIGNED linear offset (first piece x piece length).
 
-    verify_payload_v2(meta, files_bytes, devices=None) -> bytearray    one buffer per file
-    verify_files_v2(meta, dir_path, devices=None, threads=None) -> bytearray
+    verify_payload_v2(meta, files_bytes, devices=None, stream=False) -> bytearray    one buffer per file
+    verify_files_v2(meta, dir_path, devices=None, threads=None, stream=False) -> bytearray
+    verify_stream_v2(meta, read, devices=None, avail=None, chunk=0, ...) -> bytearray    read(file, offset, length)
     verify_piece_v2(meta, index, data) -> bool
     hash_files_v2(dir_path, piece_length, files=None, ...) -> per-file pieces roots and layers (creation mode)
     make_torrent_v2(path, tracker, ...) -> bytes of a v2-only .torrent
 
 All of them shard over `devices` with shard_ranges, as the v1 calls do.  There is no CPU fallback for piece hashing
-(only a file's P - 1 layer hashes and the info-hash are host work), and a shard must fit the device's resident budget:
-v2 through windows or the streamed ring is not built yet, so a larger shard raises.
+(only a file's P - 1 layer hashes and the info-hash are host work).  By default a shard must fit the device's resident
+budget and a larger one raises; stream=True (and verify_stream_v2) verify through the library's bounded pinned ring
+instead (tv_v2_stream_begin / tv_v2_stream_file_table): two chunk buffers within the budget, whatever the shard's
+size.  Creation (hash_files_v2) is resident only; windowed resident v2 layouts are not built.
 """
 from __future__ import annotations
 
 import hashlib
 import os
 import time
+from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional, Sequence
 
 from . import _native
 from .bencode import bencode
 from .metainfo_v2 import LEAF_BYTES, MetainfoV2, V2Layout, layer_root, make_layout, valid_piece_length
-from .verify import _PIECE_SLOT, _concat, _context, _devices, _run_shards, _set_bit
+from .storage import copy_bytes
+from .verify import (_PIECE_SLOT, _chunked_map, _concat, _context, _devices, _run_shards, _set_bit, _shard_avail,
+                     _storage_threads)
 
 CREATED_BY = "torrent_amd make_torrent_v2"
 
@@ -37,7 +43,8 @@ def _v2_layout(ctx, lay: V2Layout, first: int, count: int, hashes: Optional[byte
     if ctx.counter(_native.TV_COUNTER_WINDOW_PIECES):
         held = ctx.counter(_native.TV_COUNTER_BUDGET)
         raise MemoryError(f"v2 verify needs its shard resident: {count} pieces of {lay.piece_length} bytes exceed the "
-                          f"device budget of {held} bytes (use more devices; streamed v2 is not built yet)")
+                          f"device budget of {held} bytes (use more devices, or stream=True to verify through the "
+                          f"bounded ring)")
     ctx.v2_set_pieces(lay.piece_bytes, lay.tree_leaves, hashes)
 
 
@@ -49,14 +56,89 @@ def _file_paths(meta_name: str, files: Sequence, dir_path: str) -> List[str]:
     return [os.path.join(dir_path, *f.path) for f in files]
 
 
-def verify_payload_v2(meta: MetainfoV2, files_bytes: Sequence, devices=None, budget: Optional[int] = None) -> bytearray:
+def _v2_stream_layout(ctx, lay: V2Layout, first: int, count: int, budget: Optional[int], chunk: int) -> None:
+    """The layout of a streamed v2 check: no resident payload; the geometry comes from the budget or the chunk."""
+    ctx.set_option(_native.TV_OPT_RESIDENT, 0)
+    try:
+        ctx.set_option(_native.TV_OPT_RESIDENT_BUDGET, int(budget or 0))
+        ctx.set_option(_native.TV_OPT_STREAM_CHUNK, int(chunk or 0))
+        ctx.set_layout(lay.total_length, lay.piece_length, lay.n_pieces, first, count)
+    finally:
+        ctx.set_option(_native.TV_OPT_RESIDENT, 1)
+
+
+def verify_stream_v2(meta: MetainfoV2, read, devices=None, avail: Optional[bytes] = None, chunk: int = 0,
+                     threads: Optional[int] = None, budget: Optional[int] = None) -> bytearray:
+    """Resume check of a v2 torrent through the library's BOUNDED pinned ring (tv_v2_stream_begin, tv_stream_*): no
+    resident shard and no whole-shard host buffer, so a torrent of any size verifies within `budget` bytes of device
+    memory (default 1 GiB) and 3 x 64 MiB of host memory per device.  read(file_index, offset, length) -> bytes | None
+    supplies one row of a request: `length` bytes of file `file_index` (file-tree order) from `offset` -- a v2 piece
+    never spans files, so a row is one call; None or a short result makes that piece unreadable (bit 0).  By default
+    the rows are whole pieces (or the widest power-of-two part of one that the budget holds 64 of); chunk=C > 0 asks
+    for columns of C bytes (a power of two >= 16 KiB) across the whole shard.  The reads of a request are in flight
+    together on `threads` threads, each writing its own row of the slot (as verify_stream)."""
+    lay = meta.layout
+    P = lay.n_pieces
+
+    def shard(ctx, first: int, count: int) -> bytes:
+        _v2_stream_layout(ctx, lay, first, count, budget, chunk)
+        nthr = _storage_threads(ctx, threads)
+        pool = ThreadPoolExecutor(nthr) if nthr > 1 else None
+        try:
+            ctx.v2_stream_begin(lay.piece_bytes, lay.tree_leaves, lay.hashes, _shard_avail(avail, first, count))
+            while True:
+                req = ctx.stream_next()
+                if not req.rows:
+                    break
+
+                def fill(q: int, req=req):
+                    """Row q into the slot; returns the piece index when it is unreadable."""
+                    n = ctx.row_bytes(req, q)
+                    if n == 0:
+                        return None
+                    i = req.piece + q
+                    data = read(lay.piece_file[i], lay.piece_offset[i] + req.offset, n)
+                    if data is None or len(data) != n:
+                        return i
+                    copy_bytes(req.slot + q * req.width, data, n)
+                    return None
+
+                for i in _chunked_map(pool, fill, req.rows, nthr):
+                    if i is not None:
+                        ctx.stream_unreadable(i)
+                ctx.stream_commit(req)
+            return ctx.stream_end()
+        except BaseException:
+            ctx.stream_abort()
+            raise
+        finally:
+            if pool is not None:
+                pool.shutdown()
+            ctx.set_option(_native.TV_OPT_STREAM_CHUNK, 0)
+
+    if P == 0:
+        return bytearray()
+    ranges, slices = _run_shards(_devices(devices), P, shard)
+    return _concat(slices, ranges, P)
+
+
+def verify_payload_v2(meta: MetainfoV2, files_bytes: Sequence, devices=None, budget: Optional[int] = None,
+                      stream: bool = False) -> bytearray:
     """Have-bitfield of a v2 torrent whose files are in host memory: files_bytes[k] is file k's bytes (file-tree
-    order).  None, or a buffer shorter than the file, makes exactly the pieces it cannot supply unreadable (bit 0)."""
+    order).  None, or a buffer shorter than the file, makes exactly the pieces it cannot supply unreadable (bit 0).
+    stream=True verifies through the bounded ring (verify_stream_v2 reading the buffers) and never raises for size;
+    the default needs every shard resident within the budget."""
     lay = meta.layout
     P, L = lay.n_pieces, lay.piece_length
     if len(files_bytes) != len(meta.files):
         raise ValueError("verify_payload_v2: one buffer per file")
     views = [None if b is None else memoryview(b).cast("B") for b in files_bytes]
+    if stream:
+        def read(k: int, offset: int, n: int):
+            mv = views[k]
+            return None if mv is None or mv.nbytes < offset + n else mv[offset:offset + n]
+
+        return verify_stream_v2(meta, read, devices=devices, budget=budget)
 
     def shard(ctx, first: int, count: int) -> bytes:
         _v2_layout(ctx, lay, first, count, lay.hashes, budget)
@@ -105,15 +187,29 @@ def _stage_files_v2(ctx, lay: V2Layout, lengths: Sequence[int], paths: Sequence[
 
 
 def verify_files_v2(meta: MetainfoV2, dir_path: str, devices=None, threads: Optional[int] = None,
-                    budget: Optional[int] = None) -> bytearray:
+                    budget: Optional[int] = None, stream: bool = False) -> bytearray:
     """Resume check of a v2 torrent from disk: the have-bitfield of the files under dir_path.  A missing or short file
-    gives 0 bits for exactly the pieces it cannot supply (the library's per-piece marking); nothing is created."""
+    gives 0 bits for exactly the pieces it cannot supply (the library's per-piece marking); nothing is created.
+    stream=True reads the files through the bounded ring in the library's own threads (tv_v2_stream_file_table, files
+    opened read-only) and never raises for size; the default needs every shard resident within the budget."""
     lay = meta.layout
     P = lay.n_pieces
     paths = _file_paths(meta.name, meta.files, dir_path)
     lengths = [f.length for f in meta.files]
 
+    def stream_shard(ctx, first: int, count: int) -> bytes:
+        _v2_stream_layout(ctx, lay, first, count, budget, 0)
+        ctx.set_option(_native.TV_OPT_FILE_THREADS, max(1, threads or ctx.thread_budget))
+        ctx.set_option(_native.TV_OPT_OPEN_RW, 0)          # a verify writes nothing: read-only
+        try:
+            safe = [p if "\0" not in p else "" for p in paths]
+            return ctx.v2_stream_file_table(lay.piece_bytes, lay.tree_leaves, lay.hashes, lengths, safe)[0]
+        finally:
+            ctx.set_option(_native.TV_OPT_OPEN_RW, 1)
+
     def shard(ctx, first: int, count: int) -> bytes:
+        if stream:
+            return stream_shard(ctx, first, count)
         _v2_layout(ctx, lay, first, count, lay.hashes, budget)
         _stage_files_v2(ctx, lay, lengths, paths, first, count, threads or ctx.thread_budget)
         return ctx.v2_verify()

@@ -64,6 +64,17 @@ const SYMBOLS = {
     result: "i32",
     nonblocking: true,
   },
+  tv_v2_stream_begin: {
+    parameters: ["pointer", "u64", "pointer", "pointer", "pointer", "pointer"],
+    result: "i32",
+    nonblocking: true,
+  },
+  tv_v2_stream_file_table: {
+    parameters: ["pointer", "u64", "pointer", "pointer", "pointer", "u64", "pointer", "pointer", "u64", "pointer",
+                 "pointer", "pointer"],
+    result: "i32",
+    nonblocking: true,
+  },
   tv_stream_begin: { parameters: ["pointer", "pointer"], result: "i32" },
   tv_stream_next: { parameters: ["pointer", "pointer"], result: "i32", nonblocking: true },
   tv_stream_commit: { parameters: ["pointer", "pointer"], result: "i32", nonblocking: true },
