@@ -315,6 +315,51 @@ int tv_v2_verify_list(tv_ctx *ctx, uint64_t n, const uint64_t *pieces, const uin
                       const uint32_t *tree_leaves, const uint8_t *hashes /* 32*n */, uint8_t *ok_out);
 
 /*
+ * Below the piece: the leaf layer of a v2 piece, and single 16 KiB blocks against it.  A v2 piece hash is the root of
+ * a merkle tree so that a block can be checked on its own: a downloader that has a piece's leaf layer (obtained from
+ * a peer and proven against the piece's hash, a `hashes` message) can name the bad blocks of a failed piece and fetch
+ * only those again, and check a block before its piece is complete; a seeder answers a hash request from the leaf
+ * layer of a piece it holds.  The tree above the leaves (proofs, uncle hashes) is a few hundred small hashes: host
+ * work, not in this library.
+ *
+ * Both calls take entries that describe themselves exactly as tv_v2_verify_list's do: entry k is GLOBAL piece
+ * pieces[k] of this ctx's shard (any order, duplicates allowed) with piece_bytes[k] valid bytes and a tree of
+ * tree_leaves[k] leaves (the ranges and error texts of tv_v2_set_pieces); no piece table and no digests are needed; on
+ * a whole-shard resident layout the piece's row is read, on a slot pool (TV_OPT_LIST_SLOTS) its slot.  With
+ * W = piece_length / 16 KiB, block i of a piece is its bytes [16384 i, min(16384 (i + 1), piece_bytes[k])): it holds
+ * bytes when 16384 i < piece_bytes[k], and its hash is SHA-256 of those bytes (the last one 1 .. 16,384, not padded).
+ * Any valid v2 piece length is accepted (no tree is held in on-chip memory, so tv_v2_verify_list's 1 GiB limit does
+ * not apply).
+ *
+ * tv_v2_leaf_hashes: leaves_out gets 32 * n * W bytes: entry k's block i at leaves_out + (k * W + i) * 32; the
+ * positions at or past ceil(piece_bytes[k] / 16 KiB), out to W, are 32 zero bytes (BEP 52's zero hashes of the padding
+ * leaves inside the tree, and the positions beyond a narrower tree alike).  A listed piece that holds no slot, or that
+ * tv_stage_file(s) marked unreadable, is TV_ERR_STATE naming the piece (there is nothing to hand out).
+ *
+ * tv_v2_check_blocks: leaf_hashes has the layout of leaves_out (32 * n * W bytes; only wanted positions are read).
+ * want_bits: n rows of ceil(W / 8) bytes, MSB-first, bit i of row k = block i of entry k is wanted; NULL = every block
+ * that holds bytes.  ok_bits_out has the same shape: bit i of row k is 1 iff block i is wanted, holds at least one
+ * valid byte, and SHA-256 of its valid bytes equals leaf_hashes[(k * W + i) * 32 ..]; spare bits are 0.  A block that
+ * is not wanted is neither read nor hashed, so a partly received piece can sit in a slot with stale bytes around its
+ * staged blocks.  A piece without a slot, or marked unreadable, gives all 0 bits (tv_verify_list's rule).
+ *
+ * release != 0 frees the listed pieces' slots when the call returns, as tv_v2_verify_list does; release == 0 keeps
+ * them (the piece may still be assembling).  A refused call changes nothing and frees no slot.  n == 0 is TV_OK.
+ * TV_ERR_ARG: NULL arrays with n > 0 (want_bits may be NULL), a piece outside the shard, piece_length not a power of
+ * two >= 16 KiB, a piece_bytes / tree_leaves entry outside its range, more than TV_V2_BLOCKS_MAX blocks to hash, and
+ * for tv_v2_leaf_hashes also n * W > TV_V2_BLOCKS_MAX.  TV_ERR_STATE: before tv_set_layout, on a windowed layout, with
+ * TV_OPT_RESIDENT = 0, during a stream.  Each call is ONE launch, one lane per block to hash; device memory is at most
+ * 48 bytes per such block (at least 1,024 of them), reused by later calls that fit.  tv_last_timing, tv_last_kernel
+ * (kernel id 64, one launch) and TV_COUNTER_LAST_WORKGROUPS (ceil(blocks / 256)) report on it.
+ */
+#define TV_V2_BLOCKS_MAX (1ull << 22)
+int tv_v2_leaf_hashes(tv_ctx *ctx, uint64_t n, const uint64_t *pieces, const uint32_t *piece_bytes,
+                      const uint32_t *tree_leaves, uint8_t *leaves_out, int release);
+int tv_v2_check_blocks(tv_ctx *ctx, uint64_t n, const uint64_t *pieces, const uint32_t *piece_bytes,
+                       const uint32_t *tree_leaves, const uint8_t *leaf_hashes, const uint8_t *want_bits,
+                       uint8_t *ok_bits_out, int release);
+
+/*
  * Streamed verify through a BOUNDED pinned ring (end-to-end resume check, SURVEY 8d cfg5: the
  * resume flow Client.add -> Storage -> bitfield -> sendBitfield, client.ts:53-67, torrent.ts:56-60,101).
  * No resident payload and no whole-shard host buffer are needed: the library hands out requests in the
@@ -469,7 +514,7 @@ int tv_get_option(tv_ctx *ctx, int key, int64_t *value);
 int tv_last_timing(tv_ctx *ctx, double *kernel_ms, double *total_ms);
 
 /* Kernel chosen for the last call (1 lane, 2 split, 4 twin; 8 = the v2 SHA-256 merkle kernels, 16 = the v2 list
- * kernel, 32 = a v2 stream's column kernel) and launches it used. */
+ * kernel, 32 = a v2 stream's column kernel, 64 = the v2 block kernel) and launches it used. */
 int tv_last_kernel(tv_ctx *ctx, int *kernel, int *launches);
 
 /* Resource counters of a ctx (tv_get_counter keys): how often tv_set_layout and the calls after it had to

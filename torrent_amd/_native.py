@@ -81,12 +81,14 @@ TV_COUNTER_LAST_CLOCK_KHZ = 12
 
 TV_STREAM_RING_SLOTS = 3
 TV_V2_LEAF_BYTES = 16384
+TV_V2_BLOCKS_MAX = 1 << 22   # blocks one tv_v2_leaf_hashes / tv_v2_check_blocks call hashes, at most
 TV_STREAM_SLOT_BYTES = 64 << 20
 
 KERNEL_AUTO, KERNEL_LANE, KERNEL_SPLIT, KERNEL_TWIN = 0, 1, 2, 4   # (3 was MIX, removed)
 KERNEL_V2 = 8   # tv_last_kernel after tv_v2_verify / tv_v2_hash
 KERNEL_V2_LIST = 16   # tv_last_kernel after tv_v2_verify_list
 KERNEL_V2_STREAM = 32   # tv_last_kernel after a v2 stream (tv_v2_stream_begin .. tv_stream_end)
+KERNEL_V2_BLOCKS = 64   # tv_last_kernel after tv_v2_leaf_hashes / tv_v2_check_blocks
 
 _u64, _i64, _int, _p = ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
 
@@ -136,6 +138,8 @@ SYMBOLS = [
     ("tv_v2_verify", _int, [_p, _p, _p]),
     ("tv_v2_hash", _int, [_p, _p]),
     ("tv_v2_verify_list", _int, [_p, _u64, _p, _p, _p, _p, _p]),
+    ("tv_v2_leaf_hashes", _int, [_p, _u64, _p, _p, _p, _p, _int]),
+    ("tv_v2_check_blocks", _int, [_p, _u64, _p, _p, _p, _p, _p, _p, _int]),
     ("tv_v2_stream_begin", _int, [_p, _u64, _p, _p, _p, _p]),
     ("tv_v2_stream_file_table", _int, [_p, _u64, _p, _p, _p, _u64, _p, _p, _u64, _p, _p, _p]),
     ("tv_stream_begin", _int, [_p, _p]),
@@ -665,6 +669,52 @@ class Context:
         self._check(self._L.tv_v2_verify_list(self._h, n, pc.ctypes.data, pb.ctypes.data, tl.ctypes.data, a, out))
         del keep
         return out.raw[:n]
+
+    def _v2_entries(self, what: str, pieces, piece_bytes, tree_leaves):
+        import numpy as np
+        pc = np.ascontiguousarray(pieces, dtype=np.uint64)
+        pb = np.ascontiguousarray(piece_bytes, dtype=np.uint32)
+        tl = np.ascontiguousarray(tree_leaves, dtype=np.uint32)
+        if len(pb) != len(pc) or len(tl) != len(pc):
+            raise ValueError(f"{what}: pieces, piece_bytes and tree_leaves differ in length")
+        return pc, pb, tl, max(1, getattr(self, "piece_length", 0) // TV_V2_LEAF_BYTES)
+
+    def v2_leaf_hashes(self, pieces, piece_bytes, tree_leaves, release: bool = False) -> bytes:
+        """tv_v2_leaf_hashes: the leaf layer of every listed entry (as v2_verify_list's), 32 x W bytes each, W =
+        piece_length / 16 KiB: SHA-256 of each 16 KiB block that holds bytes, zero hashes after them out to W."""
+        pc, pb, tl, W = self._v2_entries("v2_leaf_hashes", pieces, piece_bytes, tree_leaves)
+        n = len(pc)
+        if n == 0:
+            self._check(self._L.tv_v2_leaf_hashes(self._h, 0, None, None, None, None, int(bool(release))))
+            return b""
+        if n * W > TV_V2_BLOCKS_MAX:       # (the library refuses it too; the output buffer would be n x W x 32 bytes)
+            raise ValueError(f"v2_leaf_hashes: {n} entries of {W} leaf positions exceed TV_V2_BLOCKS_MAX")
+        out = ctypes.create_string_buffer(32 * n * W)
+        self._check(self._L.tv_v2_leaf_hashes(self._h, n, pc.ctypes.data, pb.ctypes.data, tl.ctypes.data, out,
+                                              int(bool(release))))
+        return out.raw[:32 * n * W]
+
+    def v2_check_blocks(self, pieces, piece_bytes, tree_leaves, leaf_hashes, want_bits=None,
+                        release: bool = False) -> bytes:
+        """tv_v2_check_blocks: the listed entries' 16 KiB blocks against `leaf_hashes` (32 x W bytes per entry, the
+        layout v2_leaf_hashes returns).  want_bits: ceil(W / 8) bytes per entry, MSB-first (None: every block that
+        holds bytes).  Returns bits of the same shape: 1 = the block was wanted, holds bytes and matches."""
+        pc, pb, tl, W = self._v2_entries("v2_check_blocks", pieces, piece_bytes, tree_leaves)
+        n, pitch = len(pc), (W + 7) // 8
+        if memoryview(leaf_hashes).nbytes != 32 * n * W:
+            raise ValueError("v2_check_blocks: leaf_hashes must hold 32 x W bytes per entry")
+        if want_bits is not None and memoryview(want_bits).nbytes != n * pitch:
+            raise ValueError("v2_check_blocks: want_bits must hold ceil(W / 8) bytes per entry")
+        if n == 0:
+            self._check(self._L.tv_v2_check_blocks(self._h, 0, None, None, None, None, None, None, int(bool(release))))
+            return b""
+        a, keep = _addr(leaf_hashes)
+        w, keep_w = _addr(want_bits)
+        out = ctypes.create_string_buffer(n * pitch)
+        self._check(self._L.tv_v2_check_blocks(self._h, n, pc.ctypes.data, pb.ctypes.data, tl.ctypes.data, a, w, out,
+                                               int(bool(release))))
+        del keep, keep_w
+        return out.raw[:n * pitch]
 
     def last_timing(self) -> tuple:
         k, t = ctypes.c_double(0), ctypes.c_double(0)

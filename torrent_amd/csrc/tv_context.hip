@@ -595,7 +595,7 @@ int tv_get_counter(tv_ctx* c, int key, uint64_t* value) {
         case TV_COUNTER_DEVICE_BYTES:
             *value = c->cap_payload + c->cap_count * 3 * 5 * sizeof(uint32_t) + c->cap_words * 8 * 3 +
                      2 * c->chunk_bytes + c->list_cap * 9 + c->cap_v2_count * 18 * sizeof(uint32_t) +
-                     c->cap_v2_nodes * sizeof(uint32_t) + c->v2_list_cap * 48 +
+                     c->cap_v2_nodes * sizeof(uint32_t) + (c->v2_list_cap + c->v2_blk_cap) * 48 +
                      (c->cap_v2s_tab + c->cap_v2s_nodes) * sizeof(uint32_t);
             return TV_OK;
         case TV_COUNTER_LAST_WORKGROUPS: *value = c->last_workgroups; return TV_OK;

@@ -329,6 +329,10 @@ struct tv_ctx {
     uint64_t cap_v2_nodes = 0;         // words of d_v2_nodes
     uint32_t* d_v2_list = nullptr;     // tv_v2_verify_list: [11][m] rows, bytes, widths, expected [8], then v2_list_cap out bytes
     uint64_t v2_list_cap = 0;          // entries of d_v2_list (48 bytes each)
+    // tv_v2_leaf_hashes / tv_v2_check_blocks: ceil(m / 64) ballot words of a check, then [11][m] rows, leaves, lens,
+    // hash words [8] (expected or out)
+    uint32_t* d_v2_blk = nullptr;
+    uint64_t v2_blk_cap = 0;           // items of d_v2_blk (48 bytes each)
     // a v2 stream's device memory beyond the chunk buffers (tv_v2_stream_begin; kept for a later stream that fits)
     uint32_t* d_v2s_tab = nullptr;     // [11][count]: piece bytes, tree leaves, top-tree widths, expected [8] per window
     uint32_t* d_v2s_nodes = nullptr;   // a window's partial nodes: level buffers A [8][wn x ncol], B [8][wn x max(ncol/2, 1)]

@@ -130,6 +130,27 @@ struct TvV2Col {
 };
 hipError_t tv_v2_launch_column(const TvV2Col& p, hipStream_t s, uint32_t* workgroups);
 
+// ---- the v2 block launch (tv_v2_leaf_hashes, tv_v2_check_blocks): m 16 KiB blocks, one lane each, no tree ----------
+#define TV_KERNEL_V2_BLOCKS 64    // tv_last_kernel id of tv_v2_leaf_hashes / tv_v2_check_blocks (tv_v2_block_kernel, one launch)
+#define TV_V2_BLOCKS_MAX_ITEMS (1u << 22)   // = TV_V2_BLOCKS_MAX of the public header: item indices stay 32-bit
+// Item t is the lens[t] (1 .. 16,384) bytes at data + rows[t] * stride + leaves[t] * 16384: block leaves[t] of the
+// piece in payload row (or slot) rows[t].  Consecutive items are consecutive blocks of a piece, so a wave reads
+// addresses 16 KiB apart (the TV_V2_MAP_LEAF pattern).  check = false: item t's hash words to hashes[q * m + t]
+// (q = 0 .. 7, big-endian values).  check = true: they are compared with expect[q * m + t], and bit (t & 63) of
+// out64[t >> 6] is set iff all eight match; out64 (ceil(m / 64) words) must be zero before the launch.
+struct TvV2Blocks {
+    const uint8_t* data;
+    uint64_t stride;
+    uint32_t m;                  // items (<= TV_V2_BLOCKS_MAX_ITEMS)
+    const uint32_t* rows;        // [m]
+    const uint32_t* leaves;      // [m]
+    const uint32_t* lens;        // [m]
+    const uint32_t* expect;      // check: [8][m]
+    uint32_t* hashes;            // !check: [8][m]
+    uint64_t* out64;             // check: [ceil(m / 64)]
+};
+hipError_t tv_v2_launch_blocks(const TvV2Blocks& p, bool check, hipStream_t s, uint32_t* workgroups);
+
 // workgroups (optional): set to the launch's grid size, companions included.
 hipError_t tv_launch_verify(const TvPieces& p, int kernel, bool hash, hipStream_t s, int split_pairs = 0,
                             uint32_t* workgroups = nullptr);

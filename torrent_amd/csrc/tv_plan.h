@@ -1,7 +1,9 @@
 // tv_plan.h -- the resident payload's shape under a device budget (tv_set_layout), a stream's windows x columns under
 // one (stream_geometry; v2_stream_geometry for a BitTorrent v2 stream), the file table's walk (walk_file_table) and a
-// v2 torrent's aligned file offsets (v2_file_starts), as plain host code with no HIP in it, so they are unit-tested on
-// the CPU (tests/c/plan_test.cpp, tests/c/walk_main.cpp, tests/c/plan_v2_main.cpp; tests/test_plan.py, test_plan_v2.py).
+// v2 torrent's aligned file offsets (v2_file_starts) and the item list of a v2 block launch (v2_block_items,
+// v2_block_scatter), as plain host code with no HIP in it, so they are unit-tested on the CPU (tests/c/plan_test.cpp,
+// tests/c/walk_main.cpp, tests/c/plan_v2_main.cpp, tests/c/plan_v2_blocks_main.cpp; tests/test_plan.py,
+// test_plan_v2.py, test_plan_v2_blocks.py).
 #pragma once
 #include <stdint.h>
 
@@ -185,6 +187,51 @@ inline bool v2_file_starts(uint64_t n, const uint64_t* lengths, uint64_t L, std:
         (*start)[k + 1] = (s + lengths[k] + L - 1) / L * L;
     }
     return true;
+}
+
+// ---- the item list of a v2 block launch (tv_v2.hip: tv_v2_leaf_hashes, tv_v2_check_blocks) --------------------------
+//
+// Entry k is a piece of piece_bytes[k] valid bytes in a torrent whose full piece holds W blocks of 16 KiB.  Its block
+// i holds bytes when i * 16 KiB < piece_bytes[k]; the last such block may be short.  An item is one block the launch
+// hashes: (entry, block, bytes).  want_bits (optional): n rows of ceil(W / 8) bytes, MSB-first, bit i of row k = block
+// i of entry k is wanted; NULL = every block that holds bytes.  A wanted position that holds no byte gives no item.
+// skip (optional): skip[k] != 0 = entry k gives no item (a piece with no slot, an unreadable piece).  Items come in
+// entry order, blocks ascending, so the lanes of a wave read addresses 16 KiB apart.
+struct V2BlockItem {
+    uint32_t entry, leaf, len;
+};
+
+inline uint64_t v2_block_pitch(uint64_t W) { return (W + 7) / 8; }
+
+// false: more than `cap` items (*items is then unspecified).
+inline bool v2_block_items(uint64_t n, const uint32_t* piece_bytes, uint64_t W, const uint8_t* want_bits,
+                           const uint8_t* skip, uint64_t cap, std::vector<V2BlockItem>* items) {
+    items->clear();
+    const uint64_t pitch = v2_block_pitch(W);
+    for (uint64_t k = 0; k < n; k++) {
+        if (skip && skip[k]) continue;
+        const uint64_t bytes = piece_bytes[k];
+        const uint64_t held = std::min<uint64_t>((bytes + kV2Leaf - 1) / kV2Leaf, W);   // blocks that hold bytes
+        const uint8_t* row = want_bits ? want_bits + k * pitch : nullptr;
+        for (uint64_t i = 0; i < held; i++) {
+            if (row && !((row[i >> 3] >> (7 - (i & 7))) & 1)) continue;
+            if (items->size() >= cap) return false;
+            const uint64_t lo = i * kV2Leaf;
+            items->push_back({(uint32_t)k, (uint32_t)i, (uint32_t)std::min<uint64_t>(kV2Leaf, bytes - lo)});
+        }
+    }
+    return true;
+}
+
+// The launch's results back to per-entry bit rows: ballots[t >> 6] bit (t & 63) = item t matched.  ok_bits gets n
+// rows of ceil(W / 8) bytes, MSB-first; a bit with no item, and every spare bit, is 0.
+inline void v2_block_scatter(uint64_t n, uint64_t W, const std::vector<V2BlockItem>& items, const uint64_t* ballots,
+                             uint8_t* ok_bits) {
+    const uint64_t pitch = v2_block_pitch(W);
+    std::fill(ok_bits, ok_bits + n * pitch, (uint8_t)0);
+    for (uint64_t t = 0; t < items.size(); t++)
+        if ((ballots[t >> 6] >> (t & 63)) & 1)
+            ok_bits[items[t].entry * pitch + (items[t].leaf >> 3)] |= (uint8_t)(0x80u >> (items[t].leaf & 7));
 }
 
 }  // namespace tvi

@@ -1,7 +1,8 @@
 // tv_v2.hip -- BitTorrent v2 (BEP 52): the piece table of a layout (tv_v2_set_pieces) and the SHA-256 merkle verify
 // and hash calls over the resident shard (tv_v2_verify, tv_v2_hash): one leaf launch, one launch per tree level, one
 // finish launch (tv_v2_kernels.hip); and the list verify of self-describing entries over a resident shard or a slot
-// pool (tv_v2_verify_list): one launch, the trees in LDS.
+// pool (tv_v2_verify_list): one launch, the trees in LDS; and the calls below the piece (tv_v2_leaf_hashes,
+// tv_v2_check_blocks): the listed entries' 16 KiB blocks, one lane each, in one launch.
 #include <cstring>
 
 #include "tv_ctx.h"
@@ -22,6 +23,11 @@ static void free_v2_list(tv_ctx* c) {
     c->v2_list_cap = 0;
 }
 
+static void free_v2_blocks(tv_ctx* c) {
+    (void)hipFree(c->d_v2_blk); c->d_v2_blk = nullptr;
+    c->v2_blk_cap = 0;
+}
+
 static void free_v2_stream(tv_ctx* c) {
     (void)hipFree(c->d_v2s_tab); c->d_v2s_tab = nullptr;
     (void)hipFree(c->d_v2s_nodes); c->d_v2s_nodes = nullptr;
@@ -31,6 +37,7 @@ static void free_v2_stream(tv_ctx* c) {
 void free_v2(tv_ctx* c) {
     free_v2_table(c);
     free_v2_list(c);
+    free_v2_blocks(c);
     free_v2_stream(c);
 }
 
@@ -42,6 +49,9 @@ uint64_t v2_node_words(uint64_t count, uint64_t W) { return 8 * count * (W + (W 
 void v2_on_layout(tv_ctx* c) {
     c->v2_set = c->v2_hashes = false;
     if (c->v2_list_cap > std::max<uint64_t>(1024, 2 * c->count)) free_v2_list(c);   // (as tv_verify_list's buffers)
+    // the block calls' items: kept while the new shard could list that many blocks (the same rule, in blocks)
+    if (c->v2_blk_cap > std::max<uint64_t>(1024, 2 * c->count * std::max<uint64_t>(1, c->L / TV_V2_LEAF_BYTES)))
+        free_v2_blocks(c);
     // a v2 stream's table and nodes: kept for a layout a v2 stream could run on and whose table they fit
     if ((c->d_v2s_tab || c->d_v2s_nodes) &&
         !(v2_piece_length_ok(c->L) && c->count && reuse_fits(11 * c->count, c->cap_v2s_tab)))
@@ -141,6 +151,160 @@ int v2_run(tv_ctx* c, TvV2& p, bool hash) {
     c->last_kernel = TV_KERNEL_V2;
     c->last_launches = 2 + (int)c->v2_maxlog;
     return TV_OK;
+}
+
+// The entries of a list call (tv_v2_verify_list, tv_v2_leaf_hashes, tv_v2_check_blocks) against the layout: GLOBAL
+// pieces of this shard with tv_v2_set_pieces' ranges and texts.
+int v2_check_entries(tv_ctx* c, uint64_t n, const uint64_t* pieces, const uint32_t* piece_bytes,
+                     const uint32_t* tree_leaves) {
+    const uint64_t W = c->L / TV_V2_LEAF_BYTES;
+    for (uint64_t k = 0; k < n; k++) {
+        if (pieces[k] < c->first || pieces[k] >= c->first + c->count)
+            return fail(c, TV_ERR_ARG, "piece %llu is not in this context's shard [%llu, %llu)",
+                        (unsigned long long)pieces[k], (unsigned long long)c->first,
+                        (unsigned long long)(c->first + c->count));
+        const uint64_t b = piece_bytes[k], w = tree_leaves[k];
+        if (b == 0 || b > c->L)
+            return fail(c, TV_ERR_ARG, "piece_bytes[%llu] = %llu is outside 1 .. %llu", (unsigned long long)k,
+                        (unsigned long long)b, (unsigned long long)c->L);
+        if (w == 0 || (w & (w - 1)) || w < (b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES || w > W)
+            return fail(c, TV_ERR_ARG, "tree_leaves[%llu] = %llu is not a power of two in %llu .. %llu",
+                        (unsigned long long)k, (unsigned long long)w,
+                        (unsigned long long)((b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES), (unsigned long long)W);
+    }
+    return TV_OK;
+}
+
+// A slot pool: every listed piece's slot is free again.
+void v2_release_listed(tv_ctx* c, uint64_t n, const uint64_t* pieces) {
+    if (!c->slots) return;
+    for (uint64_t k = 0; k < n; k++) {
+        auto it = c->slot_of.find(pieces[k] - c->first);
+        if (it == c->slot_of.end()) continue;
+        c->slot_free.push_back(it->second);
+        c->slot_of.erase(it);
+    }
+}
+
+inline uint32_t be32(const uint8_t* d) {
+    return ((uint32_t)d[0] << 24) | ((uint32_t)d[1] << 16) | ((uint32_t)d[2] << 8) | (uint32_t)d[3];
+}
+
+// tv_v2_leaf_hashes (check = false: `out` = leaves_out) and tv_v2_check_blocks (check = true: `out` = ok_bits_out).
+// One tv_v2_block_kernel launch over the items v2_block_items (tv_plan.h) makes of the entries.
+int v2_blocks_call(tv_ctx* c, const char* what, bool check, uint64_t n, const uint64_t* pieces,
+                   const uint32_t* piece_bytes, const uint32_t* tree_leaves, const uint8_t* leaf_hashes,
+                   const uint8_t* want_bits, uint8_t* out, int release) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = require_layout(c, false, true);
+    if (rc) return rc;
+    if (c->win)
+        return fail(c, TV_ERR_STATE, "%s needs the shard resident or a slot pool (TV_OPT_LIST_SLOTS); this layout is "
+                                     "windowed (the shard exceeds the device budget)", what);
+    if (n == 0) return TV_OK;
+    if (!pieces || !piece_bytes || !tree_leaves || !out || (check && !leaf_hashes))
+        return fail(c, TV_ERR_ARG, "NULL argument");
+    if (n >= 0xFFFFFF00ull) return fail(c, TV_ERR_ARG, "list too long");
+    if (!v2_piece_length_ok(c->L))
+        return fail(c, TV_ERR_ARG, "a v2 piece length is a power of two >= %d (the layout has %llu)", TV_V2_LEAF_BYTES,
+                    (unsigned long long)c->L);
+    const uint64_t W = c->L / TV_V2_LEAF_BYTES;
+    // everything is checked before anything is launched or freed: a refused call changes nothing
+    rc = v2_check_entries(c, n, pieces, piece_bytes, tree_leaves);
+    if (rc) return rc;
+    if (!check && (W > TV_V2_BLOCKS_MAX || n > TV_V2_BLOCKS_MAX / W))
+        return fail(c, TV_ERR_ARG, "%s: %llu entries of %llu leaf positions exceed TV_V2_BLOCKS_MAX (%llu)", what,
+                    (unsigned long long)n, (unsigned long long)W, (unsigned long long)TV_V2_BLOCKS_MAX);
+    // entries with nothing to hash: in a slot pool a piece that holds no slot (never staged), anywhere a piece file
+    // staging could not read
+    std::vector<uint8_t> skip(n, 0);
+    for (uint64_t k = 0; k < n; k++) {
+        const uint64_t j = pieces[k] - c->first;
+        const bool no_slot = c->slots && !c->slot_of.count(j);
+        const bool unread = c->any_file_bad && get_bit(c->file_bad.data(), j);
+        if (!no_slot && !unread) continue;
+        if (!check)
+            return fail(c, TV_ERR_STATE, no_slot ? "%s: piece %llu holds no slot (it was never staged, or was listed since)"
+                                                 : "%s: piece %llu was marked unreadable by tv_stage_file(s)",
+                        what, (unsigned long long)pieces[k]);
+        skip[k] = 1;
+    }
+    std::vector<V2BlockItem> items;
+    if (!v2_block_items(n, piece_bytes, W, check ? want_bits : nullptr, skip.data(), TV_V2_BLOCKS_MAX, &items))
+        return fail(c, TV_ERR_ARG, "%s: more than TV_V2_BLOCKS_MAX (%llu) blocks to hash", what,
+                    (unsigned long long)TV_V2_BLOCKS_MAX);
+    const uint64_t m = items.size(), words = (m + 63) / 64;
+    std::vector<uint32_t> tab((check ? 11 : 3) * m);   // rows, leaves, lens, expected leaf words [8][m] (big-endian values)
+    for (uint64_t t = 0; t < m; t++) {
+        const uint64_t k = items[t].entry, j = pieces[k] - c->first;
+        tab[t] = c->slots ? c->slot_of.find(j)->second : (uint32_t)j;
+        tab[m + t] = items[t].leaf;
+        tab[2 * m + t] = items[t].len;
+        if (!check) continue;
+        const uint8_t* d = leaf_hashes + (k * W + items[t].leaf) * 32;
+        for (int q = 0; q < 8; q++) tab[(3 + (uint64_t)q) * m + t] = be32(d + 4 * q);
+    }
+    std::vector<uint64_t> ballots(check ? words : 0);
+    std::vector<uint32_t> soa(check ? 0 : 8 * m);
+    TV_HIP(c, hipSetDevice(c->device));
+    if (m) {
+        DrainGuard drain(c);  // after the host vectors: their H2D / D2H copies end before they go
+        if (c->v2_blk_cap < m) {
+            free_v2_blocks(c);
+            const uint64_t cap = std::max<uint64_t>(m, 1024);
+            // a check's ballot words (one bit per item), then 11 table words per item: within 48 bytes per item
+            TV_HIP(c, hipMalloc((void**)&c->d_v2_blk, cap * 48));
+            c->v2_blk_cap = cap;
+            c->n_device_allocs++;
+        }
+        uint64_t* d_out = reinterpret_cast<uint64_t*>(c->d_v2_blk);
+        uint32_t* d = c->d_v2_blk + 2 * words;
+        TV_HIP(c, hipEventRecord(c->ev_call0, c->stream));
+        TV_HIP(c, hipMemcpyAsync(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+        // fail closed: an item the launch does not write reads as a mismatch
+        if (check) TV_HIP(c, hipMemsetAsync(d_out, 0, words * 8, c->stream));
+        TvV2Blocks p{};
+        p.data = c->d_payload;
+        p.stride = c->stride;
+        p.m = (uint32_t)m;
+        p.rows = d;
+        p.leaves = d + m;
+        p.lens = d + 2 * m;
+        p.expect = d + 3 * m;
+        p.hashes = d + 3 * m;
+        p.out64 = d_out;
+        TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
+        TV_HIP(c, tv_v2_launch_blocks(p, check, c->stream, &c->last_workgroups));
+        TV_HIP(c, hipEventRecord(c->ev_k1, c->stream));
+        if (check) TV_HIP(c, hipMemcpyAsync(ballots.data(), d_out, words * 8, hipMemcpyDeviceToHost, c->stream));
+        else TV_HIP(c, hipMemcpyAsync(soa.data(), p.hashes, soa.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        TV_HIP(c, hipEventRecord(c->ev_call1, c->stream));
+        TV_HIP(c, hipEventSynchronize(c->ev_call1));
+    } else {
+        c->last_workgroups = 0;
+    }
+    if (check) {
+        v2_block_scatter(n, W, items, ballots.data(), out);
+    } else {
+        memset(out, 0, n * W * 32);   // positions past a piece's bytes: zero hashes, out to W
+        for (uint64_t t = 0; t < m; t++) {
+            uint8_t* o = out + ((uint64_t)items[t].entry * W + items[t].leaf) * 32;
+            for (int q = 0; q < 8; q++) {
+                const uint32_t v = soa[(uint64_t)q * m + t];
+                o[4 * q] = (uint8_t)(v >> 24); o[4 * q + 1] = (uint8_t)(v >> 16);
+                o[4 * q + 2] = (uint8_t)(v >> 8); o[4 * q + 3] = (uint8_t)v;
+            }
+        }
+    }
+    if (release) v2_release_listed(c, n, pieces);
+    c->last_kernel = TV_KERNEL_V2_BLOCKS;
+    c->last_launches = m ? 1 : 0;
+    if (!m) {
+        c->kernel_ms = c->total_ms = 0.f;
+        return TV_OK;
+    }
+    return finish_timing(c);
 }
 
 }  // namespace
@@ -276,20 +440,8 @@ int tv_v2_verify_list(tv_ctx* c, uint64_t n, const uint64_t* pieces, const uint3
         return fail(c, TV_ERR_ARG, "tv_v2_verify_list takes pieces of up to %llu bytes (the layout has %llu)",
                     (unsigned long long)TV_V2_LEAF_BYTES << TV_V2_LIST_MAX_LOGW, (unsigned long long)c->L);
     // every entry is checked before anything is launched or freed: a refused call changes nothing
-    for (uint64_t k = 0; k < n; k++) {
-        if (pieces[k] < c->first || pieces[k] >= c->first + c->count)
-            return fail(c, TV_ERR_ARG, "piece %llu is not in this context's shard [%llu, %llu)",
-                        (unsigned long long)pieces[k], (unsigned long long)c->first,
-                        (unsigned long long)(c->first + c->count));
-        const uint64_t b = piece_bytes[k], w = tree_leaves[k];
-        if (b == 0 || b > c->L)
-            return fail(c, TV_ERR_ARG, "piece_bytes[%llu] = %llu is outside 1 .. %llu", (unsigned long long)k,
-                        (unsigned long long)b, (unsigned long long)c->L);
-        if (w == 0 || (w & (w - 1)) || w < (b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES || w > W)
-            return fail(c, TV_ERR_ARG, "tree_leaves[%llu] = %llu is not a power of two in %llu .. %llu",
-                        (unsigned long long)k, (unsigned long long)w,
-                        (unsigned long long)((b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES), (unsigned long long)W);
-    }
+    rc = v2_check_entries(c, n, pieces, piece_bytes, tree_leaves);
+    if (rc) return rc;
     // The entries launched: every listed piece, or, in a slot pool, the listed pieces that hold a slot (the others
     // were never staged: 0).  origin[e] = the entry's index in the caller's arrays.
     std::vector<uint64_t> origin;
@@ -349,13 +501,7 @@ int tv_v2_verify_list(tv_ctx* c, uint64_t n, const uint64_t* pieces, const uint3
     if (c->any_file_bad)  // pieces file staging could not read are 0 here too
         for (uint64_t k = 0; k < n; k++)
             if (get_bit(c->file_bad.data(), pieces[k] - c->first)) ok_out[k] = 0;
-    if (c->slots)  // a listed piece's slot is free again (a failed piece is staged anew when it is re-downloaded)
-        for (uint64_t k = 0; k < n; k++) {
-            auto it = c->slot_of.find(pieces[k] - c->first);
-            if (it == c->slot_of.end()) continue;
-            c->slot_free.push_back(it->second);
-            c->slot_of.erase(it);
-        }
+    v2_release_listed(c, n, pieces);  // (a failed piece is staged anew when it is re-downloaded)
     c->last_kernel = TV_KERNEL_V2_LIST;
     c->last_launches = m ? 1 : 0;
     if (!m) {
@@ -363,6 +509,19 @@ int tv_v2_verify_list(tv_ctx* c, uint64_t n, const uint64_t* pieces, const uint3
         return TV_OK;
     }
     return finish_timing(c);
+}
+
+int tv_v2_leaf_hashes(tv_ctx* c, uint64_t n, const uint64_t* pieces, const uint32_t* piece_bytes,
+                      const uint32_t* tree_leaves, uint8_t* leaves_out, int release) {
+    return v2_blocks_call(c, "tv_v2_leaf_hashes", false, n, pieces, piece_bytes, tree_leaves, nullptr, nullptr,
+                          leaves_out, release);
+}
+
+int tv_v2_check_blocks(tv_ctx* c, uint64_t n, const uint64_t* pieces, const uint32_t* piece_bytes,
+                       const uint32_t* tree_leaves, const uint8_t* leaf_hashes, const uint8_t* want_bits,
+                       uint8_t* ok_bits_out, int release) {
+    return v2_blocks_call(c, "tv_v2_check_blocks", true, n, pieces, piece_bytes, tree_leaves, leaf_hashes, want_bits,
+                          ok_bits_out, release);
 }
 
 }  // extern "C"

@@ -17,6 +17,8 @@
 //   column kernel : a streamed verify's unit (tv_v2_stream_begin): a column of every piece of a window is a whole aligned
 //                   subtree of each piece, hashed and reduced in LDS to one node per piece; the level and finish
 //                   kernels then run over those nodes.
+//   block kernel  : tv_v2_leaf_hashes / tv_v2_check_blocks: one lane per listed 16 KiB block (no tree): its hash out,
+//                   or against the expected leaf hash -> one ballot word per wave.
 // Which lane hashes which leaf (TvV2::map): consecutive leaves of a piece (addresses 16 KiB apart), or one leaf index
 // of 64 consecutive pieces (addresses `stride` apart, the layout the SHA-1 lane kernel reads).
 #include <hip/hip_runtime.h>
@@ -404,8 +406,53 @@ __global__ __launch_bounds__(256) void tv_v2_column_kernel(TvV2Col p) {
 }
 
 // ------------------------------------------------------------------------------------------
+// block kernel (tv_v2_leaf_hashes, tv_v2_check_blocks): the unit is the 16 KiB block, not the piece.  Lane t of the
+// launch hashes item t: the lens[t] bytes at row rows[t], leaf leaves[t].  The host lists a piece's blocks in
+// ascending order, so the lanes of a wave read addresses 16 KiB apart (the TV_V2_MAP_LEAF pattern).  No LDS, no tree
+// and no loop around hash_leaf: the one-tile kernels' register shape (see tv_v2_list_kernel).  Lanes past m call
+// hash_leaf inactive (its block ranges are wave reductions) and no lane returns before it.
+//   CHECK = false: the item's eight hash words out.
+//   CHECK = true : the words against the item's expected ones; lane 0 of each wave stores the wave's ballot (bit l =
+//                  item 64 * wave + l matches).  The host zeroes out64 before the launch: an item the launch does
+//                  not reach reads as a mismatch.
+// ------------------------------------------------------------------------------------------
+template <bool CHECK>
+__global__ __launch_bounds__(256) void tv_v2_block_kernel(TvV2Blocks p) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;       // (m <= 2^22)
+    const bool active = t < p.m;
+    const uint32_t row = active ? p.rows[t] : 0;
+    const uint32_t leaf = active ? p.leaves[t] : 0;
+    const uint32_t len = active ? p.lens[t] : 0;
+    uint32_t h[8];
+    hash_leaf(p.data + (uint64_t)row * p.stride + (uint64_t)leaf * kLeaf, len, active, h);
+    if (CHECK) {
+        bool ok = active;
+        if (active) {
+#pragma unroll
+            for (int q = 0; q < 8; q++) ok &= h[q] == p.expect[(uint64_t)q * p.m + t];
+        }
+        const uint64_t mask = __ballot(ok);
+        if ((threadIdx.x & 63u) == 0 && active) p.out64[t >> 6] = mask;
+    } else if (active) {
+#pragma unroll
+        for (int q = 0; q < 8; q++) p.hashes[(uint64_t)q * p.m + t] = h[q];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // host-side launchers (tv_v2.hip)
 // ------------------------------------------------------------------------------------------
+hipError_t tv_v2_launch_blocks(const TvV2Blocks& p, bool check, hipStream_t s, uint32_t* workgroups) {
+    if (workgroups) *workgroups = 0;
+    if (p.m == 0) return hipSuccess;
+    if (p.m > TV_V2_BLOCKS_MAX_ITEMS) return hipErrorInvalidValue;
+    const uint32_t grid = (p.m + 255u) / 256u;
+    if (workgroups) *workgroups = grid;
+    if (check) hipLaunchKernelGGL(tv_v2_block_kernel<true>, dim3(grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(tv_v2_block_kernel<false>, dim3(grid), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
 hipError_t tv_v2_launch_column(const TvV2Col& p, hipStream_t s, uint32_t* workgroups) {
     if (workgroups) *workgroups = 0;
     if (p.n == 0) return hipSuccess;

@@ -34,6 +34,8 @@ flush_pieces=None leaves flushing to the caller.
 IncrementalVerifierV2 is the same for a BitTorrent v2 torrent: a flush is one tv_v2_verify_list launch (SHA-256
 merkle roots, each piece's tree inside one workgroup), whose serial unit is one 16 KiB leaf plus log2 W tree nodes
 whatever the piece length (flush_cost_ms_v2), so its age bound does not grow with the piece length.
+merkle_v2.BlockRepairVerifierV2 extends it: a failed piece whose leaf layer is known keeps its good blocks and only
+the bad ones are named for re-download.
 """
 from __future__ import annotations
 

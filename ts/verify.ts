@@ -64,6 +64,16 @@ const SYMBOLS = {
     result: "i32",
     nonblocking: true,
   },
+  tv_v2_leaf_hashes: {
+    parameters: ["pointer", "u64", "pointer", "pointer", "pointer", "pointer", "i32"],
+    result: "i32",
+    nonblocking: true,
+  },
+  tv_v2_check_blocks: {
+    parameters: ["pointer", "u64", "pointer", "pointer", "pointer", "pointer", "pointer", "pointer", "i32"],
+    result: "i32",
+    nonblocking: true,
+  },
   tv_v2_stream_begin: {
     parameters: ["pointer", "u64", "pointer", "pointer", "pointer", "pointer"],
     result: "i32",
