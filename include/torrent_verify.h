@@ -360,6 +360,47 @@ int tv_v2_check_blocks(tv_ctx *ctx, uint64_t n, const uint64_t *pieces, const ui
                        uint8_t *ok_bits_out, int release);
 
 /*
+ * Hybrid torrents: one info dict with both descriptions of one payload (BEP 52's upgrade path; what current clients
+ * write by default): the v1 `files` / `pieces` with BEP 47 pad files (`attr` containing `p`) after every file that
+ * does not end a piece, and the v2 `file tree` / `piece layers`.  A client must check BOTH hash sets: a torrent whose
+ * two descriptions disagree can feed different payloads to v1 and v2 peers, and BEP 52 tells clients to refuse it.  The
+ * reference knows neither pad files nor v2 (metainfo.ts:12-44).
+ *
+ * With the pads every file starts a piece, so the v1 linear space IS the aligned space of the v2 calls: one
+ * tv_set_layout (total_length = the v1 length, pads included), one staging of each file at its aligned offset, then
+ * tv_v2_set_pieces (the v2 piece table; with hashes for a verify) and, for a verify, tv_set_digests (the v1 `pieces`
+ * string).  v1 piece i is the piece_bytes[i] file bytes of v2 piece i followed by the pad file's zeros out to
+ * v1_len(i) = min(piece_length, total_length - i * piece_length): every piece has v1_len = piece_length except
+ * possibly the last.  Pad ranges are DEFINED as zeros, as clients treat pad files: both calls first zero
+ * [piece_bytes[i], v1_len(i)) of every resident row that has such a range (one kernel launch over the shard's tail
+ * pieces, at most one per file; none when no piece has one), whatever was staged there, so a host never stages, reads
+ * or looks for a pad file, and tv_read returns zeros there afterwards.  Then the SHA-1 launch of tv_verify / tv_hash
+ * and the launches of tv_v2_verify / tv_v2_hash run over the same resident bytes.
+ *
+ * tv_hybrid_verify: bit j of v1_bits_out = piece shard_first + j is readable (avail_bits, and not marked unreadable by
+ * tv_stage_file(s)) AND SHA-1 of its v1_len bytes equals its `pieces` slice, as tv_verify; of v2_bits_out = readable
+ * AND its merkle root equals its hash, as tv_v2_verify; bitfield_out = v1 AND v2.  v1_bits_out and v2_bits_out may be
+ * NULL; a host that passes them can name the pieces where the descriptions disagree (v1 != v2).  All three are
+ * ceil(shard_count / 8) bytes, spare bits 0.
+ * tv_hybrid_hash (creation mode): the 20-byte SHA-1 of every resident v1 piece (pad zeros included) and the 32-byte
+ * merkle root of every resident v2 piece, in piece order, from one staging.
+ * TV_ERR_STATE: before tv_set_layout, on a windowed layout or a slot pool, with TV_OPT_RESIDENT = 0, during a stream,
+ * without a piece table; tv_hybrid_verify without digests or without v2 hashes.  TV_ERR_ARG: NULL outputs with a
+ * non-empty shard (bitfield_out; digests_out or roots_out), a piece_bytes[i] > v1_len(i) (the layout is not the v1
+ * space of the table), piece_length > 2 GiB.  A refused call changes nothing.  shard_count == 0 is TV_OK.
+ * tv_last_kernel reports kernel id 128 and the launches used (the pad launch when there is one, the SHA-1 launch, the
+ * v2 launches); tv_last_timing's kernel_ms spans from the pad kernel's start to the last hash kernel's end.  Device
+ * memory beyond the layout's and the piece table's: 16 bytes per tail piece (at least 1,024 of them) and, for a verify,
+ * a second bitfield and availability (2 x 8 bytes per 64 pieces), allocated by the first call that needs them, counted
+ * in TV_COUNTER_DEVICE_BYTES / _ALLOCS and reused by later calls they fit.  tv_verify, tv_hash and the tv_v2_* calls on
+ * the same ctx keep their own answers (tv_verify then hashes the zeroed pads, as a v1 client reading pad files would).
+ * Not built: a streamed hybrid verify through the bounded ring, and a hybrid list call on a slot pool.
+ */
+int tv_hybrid_verify(tv_ctx *ctx, const uint8_t *avail_bits, uint8_t *v1_bits_out, uint8_t *v2_bits_out,
+                     uint8_t *bitfield_out);
+int tv_hybrid_hash(tv_ctx *ctx, uint8_t *digests_out /* 20*shard_count */, uint8_t *roots_out /* 32*shard_count */);
+
+/*
  * Streamed verify through a BOUNDED pinned ring (end-to-end resume check, SURVEY 8d cfg5: the
  * resume flow Client.add -> Storage -> bitfield -> sendBitfield, client.ts:53-67, torrent.ts:56-60,101).
  * No resident payload and no whole-shard host buffer are needed: the library hands out requests in the
@@ -514,7 +555,8 @@ int tv_get_option(tv_ctx *ctx, int key, int64_t *value);
 int tv_last_timing(tv_ctx *ctx, double *kernel_ms, double *total_ms);
 
 /* Kernel chosen for the last call (1 lane, 2 split, 4 twin; 8 = the v2 SHA-256 merkle kernels, 16 = the v2 list
- * kernel, 32 = a v2 stream's column kernel, 64 = the v2 block kernel) and launches it used. */
+ * kernel, 32 = a v2 stream's column kernel, 64 = the v2 block kernel, 128 = a hybrid call's pad + SHA-1 + v2 launches)
+ * and launches it used. */
 int tv_last_kernel(tv_ctx *ctx, int *kernel, int *launches);
 
 /* Resource counters of a ctx (tv_get_counter keys): how often tv_set_layout and the calls after it had to

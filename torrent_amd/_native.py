@@ -58,6 +58,8 @@ TV_OPT_STREAM_COLD_REQ = 28
 TV_COUNTER_WINDOW_BUFS = 122
 TV_OPT_V2_MAP = 29
 TV_COUNTER_V2_MAP = 124
+TV_OPT_HYBRID_PAD_PROBE = 31
+TV_COUNTER_HYBRID_PAD_NS = 125
 V2_MAP_LEAF, V2_MAP_PIECE = 1, 2   # tv_internal.h TV_V2_MAP_*
 TV_COUNTER_WINDOW_STREAMS = 123
 WIN_BUFS_DEFAULT = 3    # tv_plan.h kWinBufsDefault: window buffers of a windowed layout
@@ -89,6 +91,7 @@ KERNEL_V2 = 8   # tv_last_kernel after tv_v2_verify / tv_v2_hash
 KERNEL_V2_LIST = 16   # tv_last_kernel after tv_v2_verify_list
 KERNEL_V2_STREAM = 32   # tv_last_kernel after a v2 stream (tv_v2_stream_begin .. tv_stream_end)
 KERNEL_V2_BLOCKS = 64   # tv_last_kernel after tv_v2_leaf_hashes / tv_v2_check_blocks
+KERNEL_HYBRID = 128   # tv_last_kernel after tv_hybrid_verify / tv_hybrid_hash
 
 _u64, _i64, _int, _p = ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
 
@@ -140,6 +143,8 @@ SYMBOLS = [
     ("tv_v2_verify_list", _int, [_p, _u64, _p, _p, _p, _p, _p]),
     ("tv_v2_leaf_hashes", _int, [_p, _u64, _p, _p, _p, _p, _int]),
     ("tv_v2_check_blocks", _int, [_p, _u64, _p, _p, _p, _p, _p, _p, _int]),
+    ("tv_hybrid_verify", _int, [_p, _p, _p, _p, _p]),
+    ("tv_hybrid_hash", _int, [_p, _p, _p]),
     ("tv_v2_stream_begin", _int, [_p, _u64, _p, _p, _p, _p]),
     ("tv_v2_stream_file_table", _int, [_p, _u64, _p, _p, _p, _u64, _p, _p, _u64, _p, _p, _p]),
     ("tv_stream_begin", _int, [_p, _p]),
@@ -715,6 +720,25 @@ class Context:
                                                int(bool(release))))
         del keep, keep_w
         return out.raw[:n * pitch]
+
+    # -- hybrid torrents: the v1 and the v2 hashes of one staging ------------------------------
+    def hybrid_verify(self, avail_bits=None) -> tuple:
+        """tv_hybrid_verify: (bitfield, v1 bits, v2 bits) of the shard: the pad ranges of the resident rows are zeroed,
+        then SHA-1 against the digests (set_digests) and the merkle roots against the table's hashes (v2_set_pieces)
+        over the same bytes; bitfield = v1 AND v2."""
+        n = self._nbits()
+        out, v1, v2 = (ctypes.create_string_buffer(max(1, n)) for _ in range(3))
+        a, keep = _addr(avail_bits)
+        self._check(self._L.tv_hybrid_verify(self._h, a, v1, v2, out))
+        del keep
+        return out.raw[:n], v1.raw[:n], v2.raw[:n]
+
+    def hybrid_hash(self) -> tuple:
+        """tv_hybrid_hash: (20-byte SHA-1 digests, 32-byte merkle roots) of every resident piece, in piece order."""
+        d = ctypes.create_string_buffer(max(1, 20 * self.shard_count))
+        r = ctypes.create_string_buffer(max(1, 32 * self.shard_count))
+        self._check(self._L.tv_hybrid_hash(self._h, d, r))
+        return d.raw[: 20 * self.shard_count], r.raw[: 32 * self.shard_count]
 
     def last_timing(self) -> tuple:
         k, t = ctypes.c_double(0), ctypes.c_double(0)

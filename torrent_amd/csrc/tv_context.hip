@@ -295,6 +295,9 @@ int tv_set_option(tv_ctx* c, int key, int64_t value) {
             if (value < 0 || value > 2) return fail(c, TV_ERR_ARG, "TV_OPT_V2_MAP must be 0 (auto), 1 (leaf-linear) or 2 (piece-major)");
             c->v2_map_opt = (int)value;
             return TV_OK;
+        case TV_OPT_HYBRID_PAD_PROBE:
+            if (value != 1 && value != 2) return fail(c, TV_ERR_ARG, "TV_OPT_HYBRID_PAD_PROBE must be 1 or 2");
+            return hybrid_pad_probe(c, (int)value);
         case TV_OPT_STREAM_ROWS:
             if (value != 0 && value != 1) return fail(c, TV_ERR_ARG, "TV_OPT_STREAM_ROWS must be 0 or 1");
             if (c->st.active) return fail(c, TV_ERR_STATE, "TV_OPT_STREAM_ROWS cannot change during a stream");
@@ -482,6 +485,7 @@ int tv_set_layout(tv_ctx* c, uint64_t total_length, uint64_t piece_length, uint6
     if (c->chunk_bytes && (need_payload || !reuse_fits(stream_chunk_need(c), c->chunk_bytes))) free_chunks(c);
     if (c->list_cap > std::max<uint64_t>(1024, 2 * shard_count)) free_list(c);
     v2_on_layout(c);
+    hybrid_on_layout(c);
     if (shard_count && !c->d_digests) {
         TV_HIP(c, hipMalloc((void**)&c->d_digests, 5 * shard_count * sizeof(uint32_t)));
         TV_HIP(c, hipMalloc((void**)&c->d_state, 5 * shard_count * sizeof(uint32_t)));
@@ -596,7 +600,8 @@ int tv_get_counter(tv_ctx* c, int key, uint64_t* value) {
             *value = c->cap_payload + c->cap_count * 3 * 5 * sizeof(uint32_t) + c->cap_words * 8 * 3 +
                      2 * c->chunk_bytes + c->list_cap * 9 + c->cap_v2_count * 18 * sizeof(uint32_t) +
                      c->cap_v2_nodes * sizeof(uint32_t) + (c->v2_list_cap + c->v2_blk_cap) * 48 +
-                     (c->cap_v2s_tab + c->cap_v2s_nodes) * sizeof(uint32_t);
+                     (c->cap_v2s_tab + c->cap_v2s_nodes) * sizeof(uint32_t) +
+                     c->cap_hy_tails * sizeof(HybridTail) + 2 * c->cap_hy_words * 8;
             return TV_OK;
         case TV_COUNTER_LAST_WORKGROUPS: *value = c->last_workgroups; return TV_OK;
         case TV_COUNTER_NUMA_NODE: *value = c->numa_node < 0 ? UINT64_MAX : (uint64_t)c->numa_node; return TV_OK;
@@ -611,6 +616,7 @@ int tv_get_counter(tv_ctx* c, int key, uint64_t* value) {
         case TV_COUNTER_WINDOW_STREAMS: *value = c->win ? (uint64_t)c->win_nhs : 0; return TV_OK;
         case TV_COUNTER_BUDGET: *value = c->budget; return TV_OK;
         case TV_COUNTER_V2_MAP: *value = (uint64_t)c->v2_last_map; return TV_OK;
+        case TV_COUNTER_HYBRID_PAD_NS: *value = c->hy_probe_ns; return TV_OK;
         case TV_COUNTER_SLOTS_USED: *value = c->slot_of.size(); return TV_OK;
         case TV_COUNTER_FILE_CLOCK + TV_FILE_PHASE_OPEN ... TV_COUNTER_FILE_CLOCK + TV_FILE_CLOCK_N - 1:
             *value = c->file_ns[key - TV_COUNTER_FILE_CLOCK].load();

@@ -352,6 +352,7 @@ void free_device(tv_ctx* c) {
     free_chunks(c);
     free_list(c);
     free_v2(c);
+    free_hybrid(c);
 }
 
 // An allocation of `cap` units is reused for `need` units when it holds them and is not more than twice

@@ -2,7 +2,8 @@
 // translation units share.  tv_context.hip: lifecycle, options, layout, digests, counters; tv_core.hip: errors, NUMA,
 // staging rings, windows, slot pool, kernel choice, the host -> HBM copy path; tv_stage.hip: staging from memory;
 // tv_files.hip: staging from files; tv_stream.hip: the streamed engine; tv_verify.hip: verify / list / hash;
-// tv_v2.hip: the BitTorrent v2 piece table, verify, hash and list verify (the streamed v2 verify: tv_stream.hip).
+// tv_v2.hip: the BitTorrent v2 piece table, verify, hash and list verify (the streamed v2 verify: tv_stream.hip);
+// tv_hybrid.hip: hybrid torrents (the pad kernel, then the SHA-1 and the v2 launches over one staging).
 // Nothing here is exported (the link exports tv_* only: exports.map).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -341,6 +342,18 @@ struct tv_ctx {
     int v2_map_opt = 0;                // TV_OPT_V2_MAP: 0 auto, else TV_V2_MAP_*
     int v2_last_map = 0;               // the mapping the last v2 call's leaf kernel ran with
 
+    // Hybrid torrents (tv_hybrid.hip): both descriptions of one payload checked over the same resident rows.  The
+    // device memory is allocated by the first hybrid call and kept for later calls (and layouts) it fits.
+    std::vector<uint32_t> v2_tab_bytes;  // host copy of the shard's piece_bytes (tv_v2_set_pieces): the tail planner's input
+    bool hy_valid = false;             // d_hy_tails holds this piece table's tails (tv_set_layout / tv_v2_set_pieces drop it)
+    uint32_t hy_n = 0, hy_chunks = 0;  // its entries and the pad launch's workgroups
+    std::vector<tvi::HybridTail> hy_tails_host;   // the table on the host (TV_OPT_HYBRID_PAD_PROBE's memset leg)
+    uint64_t hy_probe_ns = 0;          // TV_COUNTER_HYBRID_PAD_NS
+    tvi::HybridTail* d_hy_tails = nullptr;
+    uint64_t cap_hy_tails = 0;         // entries of d_hy_tails (16 bytes each)
+    uint64_t* d_hy_bits = nullptr;     // [2][cap_hy_words]: the v2 bitfield of a hybrid verify, then its v2 availability
+    uint64_t cap_hy_words = 0;         // 64-bit words of each half of d_hy_bits
+
     bool open_rw = true;               // TV_OPT_OPEN_RW: files opened read + write (fsStorage.get) or read-only
     bool stream_rows = false;          // TV_OPT_STREAM_ROWS: stream requests carry whole pieces (windows of pieces)
     int lane_pairs = 0;                // TV_OPT_LANE_PAIRS: 0 auto (>= 256 x CUs pieces in the launch), 1 on, 2 off
@@ -408,6 +421,16 @@ void v2_on_layout(tv_ctx* c);   // tv_set_layout: drop the v2 piece table, free 
 // tv_v2_stream_begin
 int v2_check_table(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const uint32_t* tree_leaves);
 uint64_t v2_node_words(uint64_t count, uint64_t W);
+// tv_v2_verify / tv_v2_hash's state checks, availability, launch arguments and launch set, shared with the hybrid calls
+// (tv_hybrid.hip).  v2_avail_bits: the caller's bits less the pieces file staging could not read, bit_words * 8 bytes
+// into `dst`; false = every piece is available (dst untouched).  v2_launch: leaf kernel, tree levels, finish.
+int v2_require(tv_ctx* c, const char* what);
+bool v2_avail_bits(const tv_ctx* c, const uint8_t* avail_bits, uint8_t* dst);
+TvV2 v2_launch_args(tv_ctx* c);
+int v2_launch(tv_ctx* c, TvV2& p, bool hash);
+void free_hybrid(tv_ctx* c);
+int hybrid_pad_probe(tv_ctx* c, int mode);
+void hybrid_on_layout(tv_ctx* c);   // tv_set_layout: drop the tail table, free what the new geometry does not fit
 void free_device(tv_ctx* c);
 bool reuse_fits(uint64_t need, uint64_t cap);
 

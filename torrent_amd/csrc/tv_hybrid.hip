@@ -1,0 +1,286 @@
+// tv_hybrid.hip -- hybrid torrents (BEP 52 with the v1 keys, BEP 47 pad files): both descriptions of one payload
+// checked, or created, from ONE staging (tv_hybrid_verify, tv_hybrid_hash).  In a hybrid torrent every file starts a
+// piece, so the v1 linear space is the aligned space of the layout: v1 piece i is v2 piece i's piece_bytes[i] file bytes
+// followed by the pad file's zeros out to v1_len(i).  tv_hybrid_pad_kernel writes those zeros into the resident rows
+// (one launch over the shard's tail table, tv_plan.h hybrid_tails); then the SHA-1 launch of tv_verify / tv_hash and
+// the launch set of tv_v2_verify / tv_v2_hash run over the same rows.
+#include <cstring>
+
+#include "tv_ctx.h"
+
+using namespace tvi;
+
+// ------------------------------------------------------------------------------------------
+// pad kernel: workgroup g zeroes chunk g of the launch (tv_plan.h: chunk k of tail entry e is the bytes of the row's
+// [begin, end) inside [a0 + k * kHybridChunk, a0 + (k + 1) * kHybridChunk), a0 = begin & ~15).  The entry of a chunk is
+// found by a search over the entries' chunk0 (ascending; at most log2(n) + 1 steps, the same in every lane).  Byte
+// stores up to the first 16-byte aligned ADDRESS (whatever the stride makes of the row base), uint4 stores from there,
+// byte stores for what is left before `end`: nothing below begin, nothing at or past end.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+struct TvHybridPad {
+    uint8_t* data;
+    uint64_t stride;
+    const HybridTail* tails;
+    uint32_t n;        // entries
+    uint32_t chunks;   // workgroups
+    uint32_t rows;     // rows of the payload (a tail outside them is skipped: never a store out of bounds)
+    uint32_t L;        // no tail ends past it
+};
+
+__global__ __launch_bounds__(256) void tv_hybrid_pad_kernel(TvHybridPad p) {
+    const uint32_t g = blockIdx.x;
+    if (g >= p.chunks || p.n == 0) return;
+    const HybridTail t = p.tails[hybrid_chunk_entry(p.tails, p.n, g)];
+    uint64_t b, e;
+    if (t.row >= p.rows || t.end > p.L || !hybrid_chunk_range(t, g, &b, &e)) return;
+    const uint64_t row = reinterpret_cast<uint64_t>(p.data) + (uint64_t)t.row * p.stride;
+    const uint64_t pb = row + b, pe = row + e;
+    uint64_t va, ve;
+    hybrid_split(pb, pe, &va, &ve);
+    const uint32_t tid = threadIdx.x;
+    if (pb + tid < va) *reinterpret_cast<uint8_t*>(pb + tid) = 0;   // (at most 15 bytes)
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    for (uint64_t q = va + 16ull * tid; q < ve; q += 16ull * 256) *reinterpret_cast<uint4*>(q) = z;
+    if (ve + tid < pe) *reinterpret_cast<uint8_t*>(ve + tid) = 0;   // (at most 15 bytes)
+}
+
+hipError_t launch_pad(const TvHybridPad& p, hipStream_t s) {
+    if (p.n == 0 || p.chunks == 0) return hipSuccess;
+    if (p.chunks > 0x7FFFFFFFu) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(tv_hybrid_pad_kernel, dim3(p.chunks), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+namespace tvi {
+
+void free_hybrid(tv_ctx* c) {
+    (void)hipFree(c->d_hy_tails); c->d_hy_tails = nullptr;
+    (void)hipFree(c->d_hy_bits); c->d_hy_bits = nullptr;
+    c->cap_hy_tails = c->cap_hy_words = 0;
+    c->hy_valid = false;
+}
+
+// TV_OPT_HYBRID_PAD_PROBE (tools/hybrid_bench.py): zero the tails of the last hybrid call's table once more, timed on
+// the compute stream: mode 1 = the pad kernel's one launch, mode 2 = one hipMemsetAsync per tail (what a host holding
+// the rows would do without the kernel).  The time is TV_COUNTER_HYBRID_PAD_NS.
+int hybrid_pad_probe(tv_ctx* c, int mode) {
+    const int rc = v2_require(c, "TV_OPT_HYBRID_PAD_PROBE");
+    if (rc) return rc;
+    if (!c->hy_valid) return fail(c, TV_ERR_STATE, "TV_OPT_HYBRID_PAD_PROBE follows a hybrid call on this piece table");
+    TV_HIP(c, hipSetDevice(c->device));
+    TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
+    if (mode == 1) {
+        TvHybridPad pad{c->d_payload, c->stride, c->d_hy_tails, c->hy_n, c->hy_chunks, (uint32_t)c->count, (uint32_t)c->L};
+        TV_HIP(c, launch_pad(pad, c->stream));
+    } else {
+        for (const HybridTail& t : c->hy_tails_host)
+            TV_HIP(c, hipMemsetAsync(c->d_payload + (uint64_t)t.row * c->stride + t.begin, 0, t.end - t.begin, c->stream));
+    }
+    TV_HIP(c, hipEventRecord(c->ev_k1, c->stream));
+    TV_HIP(c, hipEventSynchronize(c->ev_k1));
+    float ms = 0.f;
+    TV_HIP(c, hipEventElapsedTime(&ms, c->ev_k0, c->ev_k1));
+    c->hy_probe_ns = (uint64_t)((double)ms * 1e6);
+    return TV_OK;
+}
+
+void hybrid_on_layout(tv_ctx* c) {
+    c->hy_valid = false;
+    c->hy_n = c->hy_chunks = 0;
+    c->hy_tails_host.clear();
+    c->v2_tab_bytes.clear();
+    // (the rules of the list buffers and of the bit words: kept while not far larger than the new shard needs)
+    if (c->d_hy_tails && c->cap_hy_tails > std::max<uint64_t>(1024, 2 * c->count)) {
+        (void)hipFree(c->d_hy_tails); c->d_hy_tails = nullptr;
+        c->cap_hy_tails = 0;
+    }
+    if (c->d_hy_bits && !reuse_fits(c->bit_words, c->cap_hy_words)) {
+        (void)hipFree(c->d_hy_bits); c->d_hy_bits = nullptr;
+        c->cap_hy_words = 0;
+    }
+}
+
+}  // namespace tvi
+
+namespace {
+
+// The state both calls need, in the order the header lists it; nothing is changed before the last check passes.
+int hybrid_require(tv_ctx* c, const char* what, bool verify) {
+    int rc = v2_require(c, what);
+    if (rc) return rc;
+    if (!c->v2_set) return fail(c, TV_ERR_STATE, "%s: tv_v2_set_pieces has not been called for this layout", what);
+    if (verify && !c->digests_set) return fail(c, TV_ERR_STATE, "%s: tv_set_digests has not been called", what);
+    if (verify && !c->v2_hashes)
+        return fail(c, TV_ERR_STATE, "%s: the piece table has no expected hashes (creation mode)", what);
+    return TV_OK;
+}
+
+// The shard's tail table on the device (built once per piece table) and, for a verify, the second bitfield.
+int hybrid_prepare(tv_ctx* c, const char* what, bool verify) {
+    std::vector<HybridTail> tails;
+    uint64_t chunks = 0, bad = 0;
+    if (!c->hy_valid) {
+        if (c->v2_tab_bytes.size() != c->count) return fail(c, TV_ERR_STATE, "%s: no piece table", what);
+        if (!hybrid_tails(c->total, c->L, c->first, c->count, c->v2_tab_bytes.data(), &tails, &chunks, &bad)) {
+            if (bad == UINT64_MAX)
+                return fail(c, TV_ERR_ARG, "%s takes piece lengths up to %llu bytes (the layout has %llu)", what,
+                            (unsigned long long)kHybridMaxL, (unsigned long long)c->L);
+            return fail(c, TV_ERR_ARG, "%s: piece_bytes[%llu] = %llu exceeds the piece's v1 length %llu (total_length "
+                                       "%llu): the layout is not the v1 space of these pieces", what,
+                        (unsigned long long)(c->first + bad), (unsigned long long)c->v2_tab_bytes[bad],
+                        (unsigned long long)hybrid_v1_len(c->total, c->L, c->first + bad), (unsigned long long)c->total);
+        }
+        if (chunks > 0x7FFFFFFFull) return fail(c, TV_ERR_ARG, "%s: too many pad chunks", what);
+    }
+    TV_HIP(c, hipSetDevice(c->device));
+    if (verify && (!c->d_hy_bits || c->cap_hy_words < c->bit_words)) {
+        TV_HIP(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(c->d_hy_bits);
+        c->d_hy_bits = nullptr;
+        c->cap_hy_words = 0;
+        TV_HIP(c, hipMalloc((void**)&c->d_hy_bits, 2 * c->bit_words * 8));
+        c->cap_hy_words = c->bit_words;
+        c->n_device_allocs++;
+    }
+    if (c->hy_valid) return TV_OK;
+    if (!tails.empty()) {
+        TV_HIP(c, hipStreamSynchronize(c->stream));   // (a pad launch of the last table may still read the buffer)
+        if (c->cap_hy_tails < tails.size()) {
+            (void)hipFree(c->d_hy_tails);
+            c->d_hy_tails = nullptr;
+            c->cap_hy_tails = 0;
+            const uint64_t cap = std::max<uint64_t>(tails.size(), 1024);
+            TV_HIP(c, hipMalloc((void**)&c->d_hy_tails, cap * sizeof(HybridTail)));
+            c->cap_hy_tails = cap;
+            c->n_device_allocs++;
+        }
+        TV_HIP(c, hipMemcpyAsync(c->d_hy_tails, tails.data(), tails.size() * sizeof(HybridTail), hipMemcpyHostToDevice,
+                                 c->stream));
+        TV_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    c->hy_n = (uint32_t)tails.size();
+    c->hy_chunks = (uint32_t)chunks;
+    c->hy_tails_host.swap(tails);
+    c->hy_valid = true;
+    return TV_OK;
+}
+
+// Pad kernel, SHA-1 launch, v2 launch set, one after the other on the compute stream; ev_k0 .. ev_k1 bracket them.  (The
+// v2 launches on a second stream beside the SHA-1 launch were measured and not kept: DESIGN.md section 4.)
+int hybrid_run(tv_ctx* c, const TvPieces& p1, TvV2& p2, bool hash) {
+    TvHybridPad pad{};
+    pad.data = c->d_payload;
+    pad.stride = c->stride;
+    pad.tails = c->d_hy_tails;
+    pad.n = c->hy_n;
+    pad.chunks = c->hy_chunks;
+    pad.rows = (uint32_t)c->count;
+    pad.L = (uint32_t)c->L;
+    const int kernel = choose_kernel(c);
+    TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
+    TV_HIP(c, launch_pad(pad, c->stream));   // (a shard with no tail launches nothing)
+    int rc = launch_resident(c, p1, kernel, hash);
+    if (rc) return rc;
+    rc = v2_launch(c, p2, hash);
+    if (rc) return rc;
+    TV_HIP(c, hipEventRecord(c->ev_k1, c->stream));
+    c->last_kernel = TV_KERNEL_HYBRID;
+    c->last_launches = (c->hy_n ? 1 : 0) + 1 + 2 + (int)c->v2_maxlog;
+    return TV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tv_hybrid_verify(tv_ctx* c, const uint8_t* avail_bits, uint8_t* v1_bits_out, uint8_t* v2_bits_out,
+                     uint8_t* bitfield_out) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = hybrid_require(c, "tv_hybrid_verify", true);
+    if (rc) return rc;
+    if (!c->count) return TV_OK;
+    if (!bitfield_out) return fail(c, TV_ERR_ARG, "bitfield_out is NULL");
+    rc = hybrid_prepare(c, "tv_hybrid_verify", true);
+    if (rc) return rc;
+    const size_t wbytes = c->bit_words * 8, nbytes = (c->count + 7) / 8;
+    rc = ensure_hbits(c, 2 * wbytes);
+    if (rc) return rc;
+    std::vector<uint8_t> av2(wbytes);
+    DrainGuard drain(c);   // declared after av2: its H2D copy ends before it goes, also on error paths
+    TV_HIP(c, hipEventRecord(c->ev_call0, c->stream));
+    // v1: base & caller & readable (d_avail or d_base_avail); v2: caller & readable, in the second half of d_hy_bits
+    const uint64_t* av1 = nullptr;
+    rc = launch_avail(c, avail_bits, &av1);
+    if (rc) return rc;
+    uint64_t* out2 = c->d_hy_bits;
+    uint64_t* d_av2 = c->d_hy_bits + c->cap_hy_words;
+    TvV2 p2 = v2_launch_args(c);
+    p2.out64 = out2;
+    if (v2_avail_bits(c, avail_bits, av2.data())) {
+        TV_HIP(c, hipMemcpyAsync(d_av2, av2.data(), wbytes, hipMemcpyHostToDevice, c->stream));
+        p2.avail64 = d_av2;
+    }
+    TvPieces p1 = resident_launch(c);
+    p1.avail64 = av1;
+    // fail closed: a piece a launch does not write reads as 0, never as a stale 1
+    TV_HIP(c, hipMemsetAsync(c->d_out, 0, wbytes, c->stream));
+    TV_HIP(c, hipMemsetAsync(out2, 0, wbytes, c->stream));
+    rc = hybrid_run(c, p1, p2, false);
+    if (rc) return rc;
+    TV_HIP(c, hipMemcpyAsync(c->h_bits, c->d_out, wbytes, hipMemcpyDeviceToHost, c->stream));
+    TV_HIP(c, hipMemcpyAsync(c->h_bits + wbytes, out2, wbytes, hipMemcpyDeviceToHost, c->stream));
+    TV_HIP(c, hipEventRecord(c->ev_call1, c->stream));
+    TV_HIP(c, hipEventSynchronize(c->ev_call1));
+    const uint8_t spare = c->count % 8 ? (uint8_t)(0xFF00u >> (c->count % 8)) : 0xFF;   // spare bits 0
+    for (size_t k = 0; k < nbytes; k++) {
+        const uint8_t m = k + 1 == nbytes ? spare : 0xFF;
+        const uint8_t b1 = c->h_bits[k] & m, b2 = c->h_bits[wbytes + k] & m;
+        if (v1_bits_out) v1_bits_out[k] = b1;
+        if (v2_bits_out) v2_bits_out[k] = b2;
+        bitfield_out[k] = b1 & b2;
+    }
+    return finish_timing(c);
+}
+
+int tv_hybrid_hash(tv_ctx* c, uint8_t* digests_out, uint8_t* roots_out) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = hybrid_require(c, "tv_hybrid_hash", false);
+    if (rc) return rc;
+    if (!c->count) return TV_OK;
+    if (!digests_out || !roots_out) return fail(c, TV_ERR_ARG, "NULL argument");
+    rc = hybrid_prepare(c, "tv_hybrid_hash", false);
+    if (rc) return rc;
+    std::vector<uint32_t> soa1(5 * c->count), soa2(8 * c->count);
+    DrainGuard drain(c);   // declared after the vectors: drains before they are freed, also on error paths
+    TV_HIP(c, hipEventRecord(c->ev_call0, c->stream));
+    TvPieces p1 = resident_launch(c);
+    p1.avail64 = nullptr;
+    TvV2 p2 = v2_launch_args(c);
+    rc = hybrid_run(c, p1, p2, true);
+    if (rc) return rc;
+    TV_HIP(c, hipMemcpyAsync(soa1.data(), c->d_hash, soa1.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    TV_HIP(c, hipMemcpyAsync(soa2.data(), p2.roots, soa2.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    TV_HIP(c, hipEventRecord(c->ev_call1, c->stream));
+    TV_HIP(c, hipEventSynchronize(c->ev_call1));
+    for (uint64_t j = 0; j < c->count; j++) {
+        for (int k = 0; k < 5; k++) {
+            const uint32_t v = soa1[(uint64_t)k * c->count + j];
+            uint8_t* d = digests_out + 20 * j + 4 * k;
+            d[0] = (uint8_t)(v >> 24); d[1] = (uint8_t)(v >> 16); d[2] = (uint8_t)(v >> 8); d[3] = (uint8_t)v;
+        }
+        for (int k = 0; k < 8; k++) {
+            const uint32_t v = soa2[(uint64_t)k * c->count + j];
+            uint8_t* d = roots_out + 32 * j + 4 * k;
+            d[0] = (uint8_t)(v >> 24); d[1] = (uint8_t)(v >> 16); d[2] = (uint8_t)(v >> 8); d[3] = (uint8_t)v;
+        }
+    }
+    return finish_timing(c);
+}
+
+}  // extern "C"

@@ -151,6 +151,9 @@ struct TvV2Blocks {
 };
 hipError_t tv_v2_launch_blocks(const TvV2Blocks& p, bool check, hipStream_t s, uint32_t* workgroups);
 
+// ---- hybrid torrents (tv_hybrid.hip): the pad kernel, then the SHA-1 launch and the v2 launch set over the same rows --
+#define TV_KERNEL_HYBRID 128      // tv_last_kernel id of tv_hybrid_verify / tv_hybrid_hash
+
 // workgroups (optional): set to the launch's grid size, companions included.
 hipError_t tv_launch_verify(const TvPieces& p, int kernel, bool hash, hipStream_t s, int split_pairs = 0,
                             uint32_t* workgroups = nullptr);

@@ -65,6 +65,10 @@
                             leaf-linear (a wave's lanes are consecutive leaves of one piece, 16 KiB apart); 2 =
                             piece-major (a wave's lanes are one leaf index of 64 consecutive pieces, `stride` apart as in
                             the SHA-1 lane kernel; shards of fewer than 64 pieces run leaf-linear); 0 (default) = auto */
+#define TV_OPT_HYBRID_PAD_PROBE 31 /* an action (tools/hybrid_bench.py), after a hybrid call: zero the call's pad ranges once
+                                      more, timed on the compute stream: 1 = the pad kernel's launch, 2 = one
+                                      hipMemsetAsync per tail piece; the time is TV_COUNTER_HYBRID_PAD_NS */
+#define TV_COUNTER_HYBRID_PAD_NS 125 /* nanoseconds of the last TV_OPT_HYBRID_PAD_PROBE */
 #define TV_COUNTER_V2_MAP 124 /* the mapping the last tv_v2_verify / tv_v2_hash ran with (1 or 2; 0: none yet) */
 
 /* ---- file staging phase clock (tv_files.hip), for the stamped breakdown of tools/f2_stamps.py ---------------------

@@ -1,9 +1,10 @@
 // tv_plan.h -- the resident payload's shape under a device budget (tv_set_layout), a stream's windows x columns under
 // one (stream_geometry; v2_stream_geometry for a BitTorrent v2 stream), the file table's walk (walk_file_table) and a
 // v2 torrent's aligned file offsets (v2_file_starts) and the item list of a v2 block launch (v2_block_items,
-// v2_block_scatter), as plain host code with no HIP in it, so they are unit-tested on the CPU (tests/c/plan_test.cpp,
-// tests/c/walk_main.cpp, tests/c/plan_v2_main.cpp, tests/c/plan_v2_blocks_main.cpp; tests/test_plan.py,
-// test_plan_v2.py, test_plan_v2_blocks.py).
+// v2_block_scatter) and the tail table of a hybrid call (hybrid_tails), as plain host code with no HIP in it, so they
+// are unit-tested on the CPU (tests/c/plan_test.cpp, tests/c/walk_main.cpp, tests/c/plan_v2_main.cpp,
+// tests/c/plan_v2_blocks_main.cpp, tests/c/plan_hybrid_main.cpp; tests/test_plan.py, test_plan_v2.py,
+// test_plan_v2_blocks.py, test_plan_hybrid.py).
 #pragma once
 #include <stdint.h>
 
@@ -232,6 +233,84 @@ inline void v2_block_scatter(uint64_t n, uint64_t W, const std::vector<V2BlockIt
     for (uint64_t t = 0; t < items.size(); t++)
         if ((ballots[t >> 6] >> (t & 63)) & 1)
             ok_bits[items[t].entry * pitch + (items[t].leaf >> 3)] |= (uint8_t)(0x80u >> (items[t].leaf & 7));
+}
+
+// ---- the tail table of a hybrid call (tv_hybrid.hip: tv_hybrid_verify, tv_hybrid_hash) --------------------------------
+//
+// In a hybrid torrent (v1 + v2 descriptions of one payload, BEP 47 pad files after every file that does not end a
+// piece) the v1 linear space is the aligned space of the layout: v1 piece i is the piece_bytes[i] file bytes of v2
+// piece i followed by the pad file's zeros out to v1_len(i) = min(L, total - i * L).  A TAIL is a shard piece with
+// piece_bytes < v1_len (at most one per file): payload row `row` (shard-relative piece) must hold zeros in the row's
+// bytes [begin, end) before the SHA-1 kernels read it.  One tv_hybrid_pad_kernel launch zeroes every tail, a workgroup
+// per CHUNK of kHybridChunk bytes: chunk k of an entry is the bytes of [begin, end) inside [a0 + k * kHybridChunk,
+// a0 + (k + 1) * kHybridChunk), a0 = begin rounded down to 16, so every chunk but an entry's first starts 16-byte
+// aligned in a row whose base is (rows are 64-byte aligned: stride = round_up(L, 64) + a multiple of 64).  chunk0 is
+// the entry's first chunk in the launch (the entries' chunk counts summed before it); *chunks their total.
+// piece_bytes: the SHARD's entries (count of them, piece first + j at [j]).  A short last piece (v1_len = its bytes)
+// gives no entry; a trailing pad (total a multiple of L, the last file not) gives one out to L.
+// false: *bad = the shard-relative piece whose piece_bytes exceed v1_len (the table does not describe this layout), or
+// UINT64_MAX when L exceeds kHybridMaxL (offsets in a row are 32-bit).
+struct HybridTail {
+    uint32_t row, begin, end, chunk0;
+};
+constexpr uint64_t kHybridChunk = 64ull << 10;
+constexpr uint64_t kHybridMaxL = 1ull << 31;
+
+inline uint64_t hybrid_v1_len(uint64_t total, uint64_t L, uint64_t i) {
+    return (i > UINT64_MAX / L || i * L >= total) ? 0 : std::min<uint64_t>(L, total - i * L);
+}
+
+inline bool hybrid_tails(uint64_t total, uint64_t L, uint64_t first, uint64_t count, const uint32_t* piece_bytes,
+                         std::vector<HybridTail>* out, uint64_t* chunks, uint64_t* bad) {
+    out->clear();
+    *chunks = 0;
+    if (L == 0 || L > kHybridMaxL) {
+        *bad = UINT64_MAX;
+        return false;
+    }
+    for (uint64_t j = 0; j < count; j++) {
+        const uint64_t v1 = hybrid_v1_len(total, L, first + j), b = piece_bytes[j];
+        if (b > v1) {
+            *bad = j;
+            return false;
+        }
+        if (b == v1) continue;
+        const uint64_t a0 = b & ~15ull;
+        out->push_back({(uint32_t)j, (uint32_t)b, (uint32_t)v1, (uint32_t)*chunks});
+        *chunks += (v1 - a0 + kHybridChunk - 1) / kHybridChunk;
+    }
+    return true;
+}
+
+// What workgroup g of the pad launch does, shared by the kernel (tv_hybrid.hip) and the CPU test that replays it
+// (tests/c/plan_hybrid_main.cpp).  hybrid_chunk_entry: the entry whose chunks hold g (the last with chunk0 <= g; n > 0).
+// hybrid_chunk_range: the row bytes [*b, *e) of chunk g of entry t; false = none.  hybrid_split: byte ADDRESSES
+// [pb, pe) as byte stores [pb, *va), 16-byte vector stores [*va, *ve) (both 16-byte aligned) and byte stores [*ve, pe).
+#if defined(__HIPCC__)
+#define TV_PLAN_HD __host__ __device__
+#else
+#define TV_PLAN_HD
+#endif
+TV_PLAN_HD inline uint32_t hybrid_chunk_entry(const HybridTail* tails, uint32_t n, uint32_t g) {
+    uint32_t lo = 0, hi = n;   // tails[lo].chunk0 <= g, and hi == n or tails[hi].chunk0 > g
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (tails[mid].chunk0 <= g) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+TV_PLAN_HD inline bool hybrid_chunk_range(const HybridTail& t, uint32_t g, uint64_t* b, uint64_t* e) {
+    if (t.begin >= t.end || t.chunk0 > g) return false;
+    const uint64_t c0 = (uint64_t)(t.begin & ~15u) + (uint64_t)(g - t.chunk0) * kHybridChunk;
+    *b = c0 > t.begin ? c0 : t.begin;
+    *e = c0 + kHybridChunk < t.end ? c0 + kHybridChunk : t.end;
+    return *b < *e;
+}
+TV_PLAN_HD inline void hybrid_split(uint64_t pb, uint64_t pe, uint64_t* va, uint64_t* ve) {
+    const uint64_t a = (pb + 15) & ~15ull;
+    *va = a < pe ? a : pe;
+    *ve = *va + ((pe - *va) & ~15ull);
 }
 
 }  // namespace tvi

@@ -88,7 +88,7 @@ int v2_check_table(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const uin
 
 }  // namespace tvi
 
-namespace {
+namespace tvi {
 
 // The calls' common state checks (in the order the header lists them).
 int v2_require(tv_ctx* c, const char* what) {
@@ -101,20 +101,14 @@ int v2_require(tv_ctx* c, const char* what) {
     return TV_OK;
 }
 
-// Availability of one v2 launch: the caller's bits less the pieces file staging could not read; null = all.
-int v2_avail(tv_ctx* c, const uint8_t* avail_bits, const uint64_t** out) {
-    *out = nullptr;
-    if (!avail_bits && !c->any_file_bad) return TV_OK;
-    TV_HIP(c, hipEventSynchronize(c->ev_avail));  // the previous copy out of h_avail is done
+bool v2_avail_bits(const tv_ctx* c, const uint8_t* avail_bits, uint8_t* dst) {
+    if (!avail_bits && !c->any_file_bad) return false;
     const size_t nbytes = c->bit_words * 8, used = (c->count + 7) / 8;
     for (size_t k = 0; k < nbytes; k++) {
         const uint8_t caller = k < used ? (avail_bits ? avail_bits[k] : 0xFF) : 0;
-        c->h_avail[k] = k < used ? (uint8_t)(caller & ~c->file_bad[k]) : 0;
+        dst[k] = k < used ? (uint8_t)(caller & ~c->file_bad[k]) : 0;
     }
-    TV_HIP(c, hipMemcpyAsync(c->d_avail, c->h_avail, nbytes, hipMemcpyHostToDevice, c->stream));
-    TV_HIP(c, hipEventRecord(c->ev_avail, c->stream));
-    *out = c->d_avail;
-    return TV_OK;
+    return true;
 }
 
 TvV2 v2_launch_args(tv_ctx* c) {
@@ -140,14 +134,37 @@ TvV2 v2_launch_args(tv_ctx* c) {
     return p;
 }
 
-// leaf kernel, tree levels, finish; ev_k0 .. ev_k1 bracket them
-int v2_run(tv_ctx* c, TvV2& p, bool hash) {
-    TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
+// leaf kernel, tree levels, finish
+int v2_launch(tv_ctx* c, TvV2& p, bool hash) {
     TV_HIP(c, tv_v2_launch_leaves(p, c->stream, &c->last_workgroups));
     for (uint32_t l = 0; l < c->v2_maxlog; l++) TV_HIP(c, tv_v2_launch_level(p, l, c->v2_maxlog, c->stream));
     TV_HIP(c, tv_v2_launch_finish(p, hash, c->stream));
-    TV_HIP(c, hipEventRecord(c->ev_k1, c->stream));
     c->v2_last_map = (int)p.map;
+    return TV_OK;
+}
+
+}  // namespace tvi
+
+namespace {
+
+// Availability of one v2 launch: the caller's bits less the pieces file staging could not read; null = all.
+int v2_avail(tv_ctx* c, const uint8_t* avail_bits, const uint64_t** out) {
+    *out = nullptr;
+    if (!avail_bits && !c->any_file_bad) return TV_OK;
+    TV_HIP(c, hipEventSynchronize(c->ev_avail));  // the previous copy out of h_avail is done
+    v2_avail_bits(c, avail_bits, c->h_avail);
+    TV_HIP(c, hipMemcpyAsync(c->d_avail, c->h_avail, c->bit_words * 8, hipMemcpyHostToDevice, c->stream));
+    TV_HIP(c, hipEventRecord(c->ev_avail, c->stream));
+    *out = c->d_avail;
+    return TV_OK;
+}
+
+// the launch set of tv_v2_verify / tv_v2_hash on the compute stream; ev_k0 .. ev_k1 bracket it
+int v2_run(tv_ctx* c, TvV2& p, bool hash) {
+    TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
+    const int rc = v2_launch(c, p, hash);
+    if (rc) return rc;
+    TV_HIP(c, hipEventRecord(c->ev_k1, c->stream));
     c->last_kernel = TV_KERNEL_V2;
     c->last_launches = 2 + (int)c->v2_maxlog;
     return TV_OK;
@@ -318,8 +335,10 @@ int tv_v2_set_pieces(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const u
     int rc = v2_require(c, "tv_v2_set_pieces");
     if (rc) return rc;
     c->v2_set = c->v2_hashes = false;
+    c->hy_valid = false;
     rc = v2_check_table(c, n, piece_bytes, tree_leaves);
     if (rc) return rc;
+    c->v2_tab_bytes.assign(piece_bytes + (c->count ? c->first : 0), piece_bytes + (c->count ? c->first + c->count : 0));
     const uint64_t W = c->L / TV_V2_LEAF_BYTES;
     uint32_t logW = 0;
     while ((1ull << logW) < W) logW++;

@@ -1,0 +1,293 @@
+"""Hybrid torrents on MI355X: the v1 (SHA-1 `pieces`) and the v2 (SHA-256 merkle, BEP 52) description of one payload,
+verified or created from ONE staging (tv_hybrid_verify / tv_hybrid_hash in libtorrent_verify.so).
+
+A hybrid info dict carries both descriptions; its v1 file list holds BEP 47 pad files (`attr` containing `p`) after every
+file that does not end a piece, so every file starts a piece and the v1 linear space IS the aligned space the v2 calls
+address.  A client must check both hash sets: a torrent whose descriptions disagree can feed different payloads to v1
+and v2 peers, and BEP 52 tells clients to refuse it.  The library zeroes the pad ranges of the resident rows itself (pad
+files are never looked for on disk, staged or read) and runs the SHA-1 kernel and the v2 kernels over the same bytes.
+
+    parse_metainfo_hybrid(data) -> MetainfoHybrid | None          None unless v2 with v1 keys AND the two are consistent
+    verify_payload_hybrid(meta, files_bytes, devices=None) -> HybridResult     one buffer per (real) file
+    verify_files_hybrid(meta, dir_path, devices=None, threads=None) -> HybridResult
+    hash_files_hybrid(dir_path, piece_length, ...) -> (v1 `pieces`, per-file v2 hashes)      creation mode
+    make_torrent_hybrid(path, tracker, ...) -> bytes of a hybrid .torrent
+
+They shard over `devices` as the v2 calls do and need every shard resident within the device budget.  Not built: a
+streamed hybrid verify through the bounded ring, and a hybrid list call for incremental verify on a slot pool.
+"""
+from __future__ import annotations
+
+import hashlib
+import os
+import time
+from dataclasses import dataclass
+from typing import List, Optional, Sequence
+
+from . import _native
+from .bencode import bdecode_raw, bencode
+from .metainfo_v2 import FileV2, MetainfoV2, V2Layout, layer_root, make_layout, parse_metainfo_v2, valid_piece_length
+from .v2 import (FileHashV2, _file_paths, _stage_files_v2, collect_files_v2, piece_length_for_v2)
+from .verify import _concat, _devices, _run_shards, _set_bit
+
+CREATED_BY = "torrent_amd make_torrent_hybrid"
+
+
+@dataclass
+class MetainfoHybrid:
+    """A consistent hybrid torrent: the v2 description, the v1 `pieces` string (20 bytes per piece of the v2 layout) and
+    the v1 length, pad files included -- the layout's total_length, which gives every piece's v1 length: piece_length,
+    except a last piece that no pad file follows."""
+    v2: MetainfoV2
+    pieces: bytes
+    total_length: int
+    info_hash: bytes                  # v1: SHA-1 over the raw info dict
+    info_hash_v2: bytes               # v2: SHA-256 over the same bytes
+
+    @property
+    def name(self) -> str:
+        return self.v2.name
+
+    @property
+    def piece_length(self) -> int:
+        return self.v2.piece_length
+
+    @property
+    def files(self) -> List[FileV2]:
+        return self.v2.files
+
+    @property
+    def layout(self) -> V2Layout:
+        return self.v2.layout
+
+    @property
+    def n_pieces(self) -> int:
+        return self.v2.layout.n_pieces
+
+
+@dataclass
+class HybridResult:
+    """Have-bits of a hybrid verify: `bitfield` = v1 AND v2; `v1` and `v2` are the two descriptions' own bitfields."""
+    bitfield: bytearray
+    v1: bytearray
+    v2: bytearray
+
+    @property
+    def disagree(self) -> List[int]:
+        """The pieces one description accepts and the other refuses."""
+        out = []
+        for k, (a, b) in enumerate(zip(self.v1, self.v2)):
+            x = a ^ b
+            out += [8 * k + q for q in range(8) if x & (0x80 >> q)]
+        return out
+
+
+def _is_pad(entry: dict) -> bool:
+    attr = entry.get(b"attr")
+    return attr is not None and b"p" in bytes(attr)
+
+
+def parse_metainfo_hybrid(data) -> Optional[MetainfoHybrid]:
+    """A hybrid .torrent -> MetainfoHybrid, or None: not v2, no v1 keys, or the two descriptions are not consistent.
+    Consistent: the v1 file list without its pad entries is the file tree's files, in order, with the same paths and
+    lengths (`length` and `name` for a single-file torrent); every pad has exactly (-len_prev) mod piece_length bytes
+    and follows a file that needs it, before the next file that holds bytes (one after the last file is accepted: the
+    last v1 piece is then full); and `pieces` holds 20 bytes per piece of the v2 layout.  Both descriptions read the one
+    `piece length` key, so a v1 side made for another piece length shows as wrong pads or a wrong `pieces` length."""
+    try:
+        v2 = parse_metainfo_v2(data)
+        if v2 is None or not v2.hybrid:
+            return None
+        d, spans = bdecode_raw(data, spans=True)
+        info = d[b"info"]
+        L = v2.piece_length
+        if info.get(b"piece length") != L:
+            return None
+        pieces = bytes(info[b"pieces"])
+        if b"files" in info:
+            entries = info[b"files"]
+            if not isinstance(entries, list) or b"length" in info:
+                return None
+        else:
+            entries = [{b"length": info[b"length"], b"path": [info[b"name"]]}]
+        k, total, need_pad = 0, 0, 0
+        for e in entries:
+            n = e[b"length"]
+            if not isinstance(n, int) or n < 0:
+                return None
+            if _is_pad(e):
+                if need_pad == 0 or n != need_pad:         # a pad where none is needed, or of the wrong length
+                    return None
+                need_pad = 0
+            else:
+                if need_pad and n:                         # a missing pad (a zero-length file takes no bytes: the
+                    return None                            # pad may stand on either side of it)
+                path = [bytes(c).decode("utf-8", "replace") for c in e[b"path"]]
+                if k >= len(v2.files) or path != v2.files[k].path or n != v2.files[k].length:
+                    return None
+                if n:
+                    need_pad = -n % L
+                k += 1
+            total += n
+        lay = v2.layout
+        if k != len(v2.files) or len(pieces) != 20 * lay.n_pieces or -(-total // L) != lay.n_pieces:
+            return None
+        a, b = spans[b"info"]
+        return MetainfoHybrid(v2=v2, pieces=pieces, total_length=total,
+                              info_hash=hashlib.sha1(memoryview(data)[a:b]).digest(), info_hash_v2=v2.info_hash_v2)
+    except Exception:
+        return None
+
+
+def _hybrid_layout(ctx, lay: V2Layout, total: int, first: int, count: int, hashes: Optional[bytes],
+                   pieces: Optional[bytes], budget: Optional[int]) -> None:
+    """set_layout over the v1 space (= the aligned space), the v2 piece table and, for a verify, the v1 digests."""
+    ctx.set_option(_native.TV_OPT_RESIDENT_BUDGET, int(budget or 0))
+    ctx.set_layout(total, lay.piece_length, lay.n_pieces, first, count)
+    if ctx.counter(_native.TV_COUNTER_WINDOW_PIECES):
+        held = ctx.counter(_native.TV_COUNTER_BUDGET)
+        raise MemoryError(f"a hybrid verify needs its shard resident: {count} pieces of {lay.piece_length} bytes exceed "
+                          f"the device budget of {held} bytes (use more devices)")
+    ctx.v2_set_pieces(lay.piece_bytes, lay.tree_leaves, hashes)
+    if pieces is not None:
+        ctx.set_digests(pieces)
+
+
+def _result(P: int, ranges, slices) -> HybridResult:
+    return HybridResult(*(_concat([s[q] for s in slices], ranges, P) for q in range(3)))
+
+
+def verify_payload_hybrid(meta: MetainfoHybrid, files_bytes: Sequence, devices=None,
+                          budget: Optional[int] = None) -> HybridResult:
+    """Both have-bitfields of a hybrid torrent whose files are in host memory: files_bytes[k] is file k's bytes (the
+    file tree's order; pad files have no buffer).  None, or a buffer shorter than the file, makes exactly the pieces it
+    cannot supply unreadable (0 in all three bitfields)."""
+    lay = meta.layout
+    P, L = lay.n_pieces, lay.piece_length
+    if len(files_bytes) != len(meta.files):
+        raise ValueError("verify_payload_hybrid: one buffer per file")
+    views = [None if b is None else memoryview(b).cast("B") for b in files_bytes]
+
+    def shard(ctx, first: int, count: int) -> tuple:
+        _hybrid_layout(ctx, lay, meta.total_length, first, count, lay.hashes, meta.pieces, budget)
+        avail = bytearray((count + 7) // 8)
+        for j in range(count):
+            i = first + j
+            mv = views[lay.piece_file[i]]
+            if mv is not None and mv.nbytes >= lay.piece_offset[i] + lay.piece_bytes[i]:
+                _set_bit(avail, j)
+        parts = []
+        for k, mv in enumerate(views):
+            n = 0 if mv is None else min(mv.nbytes, meta.files[k].length)
+            if n and lay.file_offset[k] < (first + count) * L and lay.file_offset[k] + n > first * L:
+                parts.append((lay.file_offset[k], mv[:n]))
+        ctx.stage_many(parts)
+        return ctx.hybrid_verify(avail)
+
+    if P == 0:
+        return HybridResult(bytearray(), bytearray(), bytearray())
+    ranges, slices = _run_shards(_devices(devices), P, shard)
+    return _result(P, ranges, slices)
+
+
+def verify_files_hybrid(meta: MetainfoHybrid, dir_path: str, devices=None, threads: Optional[int] = None,
+                        budget: Optional[int] = None) -> HybridResult:
+    """Resume check of a hybrid torrent from disk.  Each real file is staged at its aligned offset (opened read-only);
+    pad files are never looked for.  A missing or short file gives 0 bits for exactly the pieces it cannot supply."""
+    lay = meta.layout
+    P = lay.n_pieces
+    paths = _file_paths(meta.name, meta.files, dir_path)
+    lengths = [f.length for f in meta.files]
+
+    def shard(ctx, first: int, count: int) -> tuple:
+        _hybrid_layout(ctx, lay, meta.total_length, first, count, lay.hashes, meta.pieces, budget)
+        _stage_files_v2(ctx, lay, lengths, paths, first, count, threads or ctx.thread_budget)
+        return ctx.hybrid_verify()
+
+    if P == 0:
+        return HybridResult(bytearray(), bytearray(), bytearray())
+    ranges, slices = _run_shards(_devices(devices), P, shard)
+    return _result(P, ranges, slices)
+
+
+def hash_files_hybrid(dir_path: str, piece_length: int, files: Optional[Sequence[tuple]] = None, devices=None,
+                      threads: Optional[int] = None, budget: Optional[int] = None) -> tuple:
+    """Creation mode from disk, both hash sets from one staging (tv_hybrid_hash): (the v1 `pieces` string over the
+    padded linear space -- no pad after the last file --, [FileHashV2] as hash_files_v2 returns them).  files:
+    [(path components, length)] in file-tree order (default: collect_files_v2).  Raises if a file is missing or short."""
+    if not valid_piece_length(piece_length):
+        raise ValueError("a v2 piece length is a power of two >= 16 KiB")
+    files = collect_files_v2(dir_path) if files is None else list(files)
+    lengths = [n for _, n in files]
+    lay = make_layout(lengths, piece_length)
+    paths = [os.path.join(dir_path, *comps) for comps, _ in files]
+    P = lay.n_pieces
+
+    def shard(ctx, first: int, count: int) -> tuple:
+        _hybrid_layout(ctx, lay, lay.total_length, first, count, None, None, budget)
+        status = _stage_files_v2(ctx, lay, lengths, paths, first, count, threads or ctx.thread_budget)
+        if any(st != _native.TV_OK for st in status):
+            raise FileNotFoundError("hash_files_hybrid: a file is missing or shorter than its declared length")
+        return ctx.hybrid_hash()
+
+    pieces = roots = b""
+    if P:
+        _, slices = _run_shards(_devices(devices), P, shard)
+        pieces = b"".join(s[0] for s in slices)
+        roots = b"".join(s[1] for s in slices)
+    out = []
+    for k, (comps, n) in enumerate(files):
+        p0 = lay.file_first_piece[k]
+        layer = roots[32 * p0:32 * (p0 + -(-n // piece_length))]
+        if n == 0:
+            out.append(FileHashV2(list(comps), 0, None, b""))
+        elif n <= piece_length:
+            out.append(FileHashV2(list(comps), n, layer, b""))
+        else:
+            out.append(FileHashV2(list(comps), n, layer_root(layer, piece_length), layer))
+    return pieces, out
+
+
+def make_torrent_hybrid(path: str, tracker: str, comment: Optional[str] = None, creation_date: Optional[int] = None,
+                        piece_length: Optional[int] = None, devices=None) -> bytes:
+    """A hybrid .torrent for a file or a directory: one info dict with the v1 keys (`files` with a pad entry --
+    `attr` "p", path [".pad", "<length>"] -- after every file that does not end a piece, none after the last file that
+    holds bytes; `length`
+    for a single file; `pieces`) and the v2 keys (`meta version` 2, `file tree`), and the top-level `piece layers`.
+    Both hash sets come from one staging on the GPU.  Dictionary keys are written sorted (canonical bencoding)."""
+    path = os.path.abspath(path)
+    name = os.path.basename(path)
+    single = not os.path.isdir(path)
+    if single:
+        base, files = os.path.dirname(path), [([name], os.stat(path).st_size)]
+    else:
+        base, files = path, collect_files_v2(path)
+    L = piece_length or piece_length_for_v2(sum(n for _, n in files))
+    pieces, hashed = hash_files_hybrid(base, L, files=files, devices=devices)
+    tree: dict = {}
+    for fh in hashed:
+        node = tree
+        for comp in fh.path:
+            node = node.setdefault(os.fsencode(comp), {})
+        node[b""] = {"length": fh.length, "pieces root": fh.pieces_root}   # (a None value is not written)
+    layers = {fh.pieces_root: fh.layer for fh in hashed if fh.layer}
+    info: dict = {"file tree": tree}
+    if single:
+        info["length"] = hashed[0].length
+    else:
+        v1_files = []
+        for k, fh in enumerate(hashed):
+            v1_files.append({"length": fh.length, "path": [os.fsencode(c) for c in fh.path]})
+            pad = -fh.length % L
+            if pad and any(later.length for later in hashed[k + 1:]):
+                v1_files.append({"attr": "p", "length": pad, "path": [".pad", str(pad)]})
+        info["files"] = v1_files
+    info.update({"meta version": 2, "name": name, "piece length": L, "pieces": pieces})
+    return bencode({
+        "announce": tracker,
+        "comment": comment,
+        "created by": CREATED_BY,
+        "creation date": int(time.time()) if creation_date is None else creation_date,
+        "info": info,
+        "piece layers": {k: layers[k] for k in sorted(layers)},
+    })

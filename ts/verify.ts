@@ -74,6 +74,14 @@ const SYMBOLS = {
     result: "i32",
     nonblocking: true,
   },
+  // Hybrid torrents (v1 + v2 hashes of one staging): bound as the v2 calls are; the host functions are
+  // torrent_amd/hybrid.py's.
+  tv_hybrid_verify: {
+    parameters: ["pointer", "pointer", "pointer", "pointer", "pointer"],
+    result: "i32",
+    nonblocking: true,
+  },
+  tv_hybrid_hash: { parameters: ["pointer", "pointer", "pointer"], result: "i32", nonblocking: true },
   tv_v2_stream_begin: {
     parameters: ["pointer", "u64", "pointer", "pointer", "pointer", "pointer"],
     result: "i32",
