@@ -275,7 +275,7 @@ def gen_split_pre_block(off_cur: int, off_next: int):
 
 def gen_split_mid_block(off_cur: int, off_next: int):
     """One block of the split rounds wave with the NEXT block's first 10 K+W quads issued inside this block (the
-    twin kernel's mid-block issue, tools/gen_sha1_asm.py gen_twin): on entry quads 0-9 of this block are in
+    mid-block issue the twin kernel's one-block loop had): on entry quads 0-9 of this block are in
     flight; it issues quads 10-14 at its start, quad 15+g after consuming quad g (g < 5), the next block's quads
     0-4 after round 39 and 5-9 after round 59 (each batch behind a wait that keeps at most 15 reads in flight,
     lgkmcnt's 4-bit limit), then h += r and the barrier.  Ring of 20 register quads, slot = quad.  The helper's
@@ -394,16 +394,16 @@ def gen_helper(src=None, off_base: int = 0):
 # expand W[16..31] with the standard recurrence, then keep their own parity (v_perm with a per-lane selector)
 # and expand W[32..79] with W[t] = rotl2(W[t-6] ^ W[t-16] ^ W[t-28] ^ W[t-32]), whose terms all have t's
 # parity: 192 VALU + 10 ds_write_b128 per block and lane instead of 308 + 20 (gen_helper2).  Every round is
-# five 8-byte instructions, so each 4-byte s_waitcnt is followed by `s_nop 0` to keep the stream 8-byte
-# aligned (a long misaligned run issues at ~5.07 instead of 4.07 cycles), with two waits per block: before
-# round 0 (reads 0-4) and round 40 (reads 5-9).  Buffer layout [k][wave][lane][4 words]: lane 2i+b of wave w
+# five 8-byte instructions, so in the single block (gen_twin, the padded tail blocks) each 4-byte s_waitcnt is
+# followed by `s_nop 0` to keep the stream 8-byte aligned (a long misaligned run issues at ~5.07 instead of
+# 4.07 cycles), with two waits: before round 0 (reads 0-4) and round 40 (reads 5-9); the loop over the full
+# blocks (gen_twin_trip_block) pairs its 4-byte instructions instead and has no s_nop.
+# Buffer layout [k][wave][lane][4 words]: lane 2i+b of wave w
 # holds W[8k+b], W[8k+b+2], W[8k+b+4], W[8k+b+6] (+K) of piece 32w+i at k*2048 + w*1024 + lane*16, written
 # and read as one contiguous KiB per wave (tools/gen_ubench_dpp.py, profiles/r02/ubench_dpp.log: the rounds
 # stream alone 1,723-1,758 vs 1,818 cycles per block for the shipped 20-read stream).
 TWIN_READ_BYTES = 2048
 TWIN_WAITS = tuple(int(x) for x in os.environ.get("TV_GEN_TWIN_WAITS", "0-5").split("-"))   # reads waited for, in pairs
-TWIN_PRE = os.environ.get("TV_GEN_TWIN_PRE", "1") == "1"   # loop: issue the next block's reads after round 79
-TWIN_NONOP = os.environ.get("TV_GEN_TWIN_NONOP", "1") == "1"  # loop: 4-byte instructions paired without s_nop
 # 64-byte placement of the twin loops: rounds loop head at (4 + 8 k) mod 64 for TV_GEN_TWIN_RALIGN = k, helper
 # loop head at 4 m mod 64 for TV_GEN_TWIN_HALIGN = m ("none": wherever the code before them puts them).  The
 # rounds loop at 4 mod 64 (and the helper's at 60) is 0.7-1.6 % faster at cfg2 than at 28, 52 or 60
@@ -420,30 +420,19 @@ TWIN_HALIGN = None if TWIN_HALIGN == "none" else TWIN_HALIGN
 SPLIT_RALIGN = os.environ.get("TV_GEN_SPLIT_RALIGN", "6")
 SPLIT_HALIGN = os.environ.get("TV_GEN_SPLIT_HALIGN")
 SPLIT_RALIGN = None if SPLIT_RALIGN == "none" else SPLIT_RALIGN
-# loop: when the next block's reads are issued -- "end": all 10 after round 79; "mid": 0-4 after the round-40
-# wait, 5-9 after round 79; "spread": read k after round 8k+7 (each as soon as its registers are consumed)
-TWIN_ISSUE = os.environ.get("TV_GEN_TWIN_ISSUE", "mid")   # mid: +1.8 % at cfg2 over end, spread -2 % (profiles/r02/twin_ab.jsonl.log)
 
 
-def gen_twin(off_base: int = 0, reads_next: int | None = None, lead: bool = False):
-    """TWIN rounds block.  lead: issue this block's own 10 reads first (tv_sha1_twin_lds); reads_next:
-    after round 79 issue the 10 reads of the block whose buffer is at that offset (the loop body).
+def gen_twin(off_base: int = 0):
+    """One TWIN rounds block with its own 10 reads issued first (tv_sha1_twin_lds: the padded tail blocks).
     Operands as gen_lds: r0-4 (out), t0-1 (tmp), h0-4 (in), addr (this lane's LDS byte address)."""
-    ins = [("ds_read_b128", k, off_base + k * TWIN_READ_BYTES) for k in range(10)] if lead else []
-    issue = TWIN_ISSUE if reads_next is not None else "end"
-    assert issue == "end" or TWIN_WAITS == (0, 5)
+    ins = [("ds_read_b128", k, off_base + k * TWIN_READ_BYTES) for k in range(10)]
     R = Regs()
     for t in range(80):
         k, b = t // 8, t % 2
-        if issue == "spread" and t % 8 == 0 and t > 0:
-            ins.append(("ds_read_b128", k - 1, reads_next + (k - 1) * TWIN_READ_BYTES))
         if t % 8 == 0 and k in TWIN_WAITS:
             nxt = [x for x in TWIN_WAITS if x > k]
-            # reads k .. (next wait - 1) retired; "spread" has the next block's first 5 behind them at round 40
-            ins.append(("s_waitcnt_lgkm", 5 if issue == "spread" and k == 5 else (10 - nxt[0] if nxt else 0)))
+            ins.append(("s_waitcnt_lgkm", 10 - nxt[0] if nxt else 0))   # reads k .. (next wait - 1) retired
             ins.append(("s_nop",))
-            if issue == "mid" and k == 5:
-                ins += [("ds_read_b128", q, reads_next + q * TWIN_READ_BYTES) for q in range(5)]
         A, B, C, D, E = roles(t)
         e_src = R.rd(E)
         ins.append(("v_add_u32_dpp", R.wr(E), ring_reg(k, (t % 8) // 2), e_src, b))
@@ -453,10 +442,136 @@ def gen_twin(off_base: int = 0, reads_next: int | None = None, lead: bool = Fals
         ins.append(("v_alignbit_b32", R.wr(B), b_src, b_src, 2))
         ins.append(("v_add3_u32", R.rd(E), R.rd(E), "t0", "t1"))
     assert R.cur == [f"r{i}" for i in range(5)]
-    if reads_next is not None:
-        first = {"end": 0, "mid": 5, "spread": 9}[issue]
-        ins += [("ds_read_b128", k, reads_next + k * TWIN_READ_BYTES) for k in range(first, 10)]
     return ins
+
+
+# ---- TWIN rounds loop: two-block trips ----
+# The loop body is two consecutive blocks on two register sets for the K+W quads (set 0 = ring quads 0-9,
+# set 1 = quads 10-19: v[RING_BASE .. RING_BASE + 79]; the rounds wave has a SIMD to itself and the kernel's
+# VGPR count is set by the helper's registers above them).  While a block runs on one set, the ten reads of
+# the next block go out as ONE group into the other set, after round TWIN_TRIP_AT, so a block has one
+# s_waitcnt -- lgkmcnt(0) before its round 0 -- and the loop counter and branch are paid once per two blocks:
+# s_sub_u32 borrows when no pair is left, so there is no s_cmp.  Non-VALU issue slots per block: 10 reads +
+# 1 wait + 1 barrier + (s_sub + s_cbranch) / 2 = 13.  The one-block loop this replaces (next block's reads
+# 0-4 after a second wait at round 40 and 5-9 after round 79 into the same ten quads; s_sub, s_cmp and
+# s_cbranch per block) had 16.  cfg2, interleaved with that loop (profiles/twin_trips/): kernel 11.88-11.92 ->
+# 11.76-11.79 ms, 1,732 -> 1,713 cycles per block.
+# Where the reads go out (TV_GEN_TWIN_TRIP_AT, cfg2 kernel ms against 11.84 for the one-block loop,
+# profiles/twin_trips/read_placement.jsonl): after round 9 11.72, 19 11.70, 29 11.73, 39 11.73, 49 11.72,
+# 59 11.70, 69 11.77 (too late: the last reads are not back at the block's end).  19 leaves them 60 rounds.
+TWIN_TRIP_AT = int(os.environ.get("TV_GEN_TWIN_TRIP_AT", "19"))   # the next block's reads follow this round
+TWIN_SET_QUADS = 10
+
+
+def twin_set_reg(s: int, k: int, j: int) -> str:
+    return f"v{RING_BASE + 4 * (TWIN_SET_QUADS * s + k) + j}"
+
+
+def gen_twin_trip_block(s: int, off_next: int):
+    """One block of the two-block-trip TWIN rounds loop on register set s.  On entry this block's ten reads
+    (issued by the previous block, or the prologue) are the only LDS operations in flight; its single wait
+    retires them.  After round TWIN_TRIP_AT it issues the ten reads of the next block (buffer at off_next)
+    into the other set, whose last use was the previous block's round 79."""
+    ins = [("s_waitcnt_lgkm", 0)]
+    R = Regs()
+    for t in range(80):
+        k, b = t // 8, t % 2
+        A, B, C, D, E = roles(t)
+        e_src = R.rd(E)
+        ins.append(("v_add_u32_dpp", R.wr(E), twin_set_reg(s, k, (t % 8) // 2), e_src, b))
+        ins.append(("v_alignbit_b32", "t0", R.rd(A), R.rd(A), 27))
+        ins.append(_fop(t, "t1", R.rd(B), R.rd(C), R.rd(D)))
+        b_src = R.rd(B)
+        ins.append(("v_alignbit_b32", R.wr(B), b_src, b_src, 2))
+        ins.append(("v_add3_u32", R.rd(E), R.rd(E), "t0", "t1"))
+        if t == TWIN_TRIP_AT:
+            ins += [("ds_read_b128_abs", TWIN_SET_QUADS * (1 - s) + q, off_next + q * TWIN_READ_BYTES)
+                    for q in range(TWIN_SET_QUADS)]
+    assert R.cur == [f"r{i}" for i in range(5)]
+    return ins
+
+
+def twin_trips_plan():
+    """Block parameters (register set, own buffer, next buffer) of the two-block-trip loop.  The loop body is
+    lcm(2 sets, LDS_BUFS buffers) = 6 blocks: the pairs (0,1) (2,0) (1,2) on sets (0,1), with an exit test after
+    each pair.  An odd block count runs `pre` first -- one block on set 1 and buffer 0 -- and enters the
+    loop at the pair that starts on buffer 1 (pair index `odd_entry`)."""
+    assert LDS_BUFS == 3
+    loop = [(i % 2, i % LDS_BUFS, (i + 1) % LDS_BUFS) for i in range(2 * LDS_BUFS)]
+    odd_entry = next(p for p in range(LDS_BUFS) if loop[2 * p][1] == 1)
+    assert odd_entry > 0
+    return {"pre": (1, 0, 1), "loop": loop, "odd_entry": odd_entry}
+
+
+def twin_trips_walk(nsteps: int):
+    """The blocks the loop text executes for nsteps blocks, in order, following its scalar control flow:
+    [(register set, buffer, next buffer)]; the first entry's set and buffer are the prologue's."""
+    plan = twin_trips_plan()
+    out, cnt = [], nsteps >> 1
+    if nsteps & 1:
+        out.append(plan["pre"])
+        if cnt == 0:             # s_sub_u32 cnt, cnt, 1 borrows: L_rdone
+            return out
+        cnt -= 1
+        pair = plan["odd_entry"]
+    else:
+        cnt -= 1
+        pair = 0
+    while True:
+        out += plan["loop"][2 * pair:2 * pair + 2]
+        if cnt == 0:             # the pair's s_sub_u32 borrows: L_rdone
+            return out
+        cnt -= 1
+        pair = (pair + 1) % LDS_BUFS
+
+
+def twin_rounds_loop_text() -> str:
+    """The TWIN rounds wave over nsteps (>= 1) blocks from ring buffer 0 in two-block trips (twin_trips_plan).
+    LDS ordering, with the helper two blocks ahead: block j + 1 was written before the barrier that started
+    block j, so block j may read it at any round; and the lgkmcnt(0) that starts block j + 1 retires those
+    reads of buffer (j + 1) % 3 before the barrier that ends block j + 1, after which the helper may rewrite
+    that buffer.  No read is in flight across more than one barrier.  The reads the final block issues (of the
+    helper's spare block) are drained at L_rdone."""
+    plan = twin_trips_plan()
+
+    def prologue(s):
+        return _emit_lines([("ds_read_b128_abs", TWIN_SET_QUADS * s + q, q * TWIN_READ_BYTES)
+                            for q in range(TWIN_SET_QUADS)])
+
+    def block(s, nxt):
+        # 4-byte instructions only in even groups: [wait] of a block pairs with the 4-byte tail of the block
+        # before it (four e32 h adds, barrier, and after a pair s_sub + s_cbranch), so every 8-byte
+        # instruction sits at 0 mod 8 and the loop needs no s_nop
+        body = _emit_lines(gen_twin_trip_block(s, nxt * RING_BYTES))
+        body.append("v_add_u32_e64 %[h0], %[h0], %[r0]")
+        body.extend(f"v_add_u32 %[h{i}], %[h{i}], %[r{i}]" for i in range(1, 5))
+        return body + (STAMP_SEQ if STAMP else ["s_barrier"])
+
+    L = ["s_waitcnt lgkmcnt(0)", "s_lshr_b32 %[cnt], %[nsteps], 1", "s_bitcmp1_b32 %[nsteps], 0",
+         "s_cbranch_scc1 L_rodd_%="]
+    L += prologue(0) + ["s_sub_u32 %[cnt], %[cnt], 1", "s_branch L_rloop_%="]
+    # odd block count: one single-block trip on set 1, then into the loop at the pair starting on buffer 1
+    s, _, nxt = plan["pre"]
+    L += ["L_rodd_%=:"] + prologue(s) + [".p2align 3", "s_nop 0"] + block(s, nxt)
+    L += ["s_sub_u32 %[cnt], %[cnt], 1", "s_cbranch_scc1 L_rdone_%=", f"s_branch L_rpair{plan['odd_entry']}_%="]
+    if TWIN_RALIGN is not None:
+        L += [".p2align 6"] + ["s_nop 0"] * (1 + 2 * int(TWIN_RALIGN))
+    else:
+        L += [".p2align 3", "s_nop 0"]
+    L.append("L_rloop_%=:")
+    for p in range(LDS_BUFS):
+        if p:
+            L.append(f"L_rpair{p}_%=:")
+        for s, _, nxt in plan["loop"][2 * p:2 * p + 2]:
+            L += block(s, nxt)
+        L += ["s_sub_u32 %[cnt], %[cnt], 1",
+              "s_cbranch_scc1 L_rdone_%=" if p < LDS_BUFS - 1 else "s_cbranch_scc0 L_rloop_%="]
+    L += ["L_rdone_%=:", "s_waitcnt lgkmcnt(0)"]
+    if TWIN_RALIGN is not None:
+        # the statement ends at 8 mod 64, where the one-block loop (3 blocks, head at 4 mod 64) ended: the
+        # code that follows (the loop over the padded tail blocks) keeps its 64-byte placement
+        L += [".p2align 6", "s_nop 0", "s_nop 0"]
+    return "\n".join(f'    "{l}\\n"' for l in L)
 
 
 def rounds_loop_text() -> str:
@@ -542,52 +657,6 @@ def gen_helper2(src=None, off_base: int = 0):
         if j % 4 == 3:
             quad(j // 4)
     return ins
-
-
-def twin_rounds_loop_text() -> str:
-    """The TWIN rounds wave over nsteps (>= 1) blocks starting at ring buffer 0: the first block's reads,
-    then per block gen_twin (its last instructions issue the next block's reads), h += r, barrier.  The
-    reads issued after the final block (of the helper's spare block) are drained before it returns.
-    Safe because the helper runs two blocks ahead: block j + 1 was written before the barrier that
-    started block j, and buffer (j + 1) % 3 is not rewritten until after the barrier that ends block j + 1."""
-    L = ["s_waitcnt lgkmcnt(0)", "s_mov_b32 %[cnt], %[nsteps]"]
-    if TWIN_PRE:
-        L.extend(_emit_lines([("ds_read_b128", k, k * TWIN_READ_BYTES) for k in range(10)]))
-    if TWIN_PRE and TWIN_WAITS == (0, 5) and TWIN_NONOP:
-        # No s_nop inside the loop: a block's 4-byte instructions come in even groups between its 8-byte runs.
-        # The first wait sits at 4 mod 8 (the previous block's tail -- four 4-byte h adds, barrier, s_cmp,
-        # s_cbranch -- precedes it; h0 += r0 is the 8-byte VOP3 form), and the loop counter's s_sub pairs
-        # with the round-40 wait.
-        if TWIN_RALIGN is not None:
-            L += [".p2align 6"] + ["s_nop 0"] * (1 + 2 * int(TWIN_RALIGN)) + ["L_rloop_%=:"]
-        else:
-            L += [".p2align 3", "s_nop 0", "L_rloop_%=:"]
-        for k in range(LDS_BUFS):
-            body = _emit_lines(gen_twin(k * RING_BYTES, reads_next=((k + 1) % LDS_BUFS) * RING_BYTES))
-            nops = [i for i, x in enumerate(body) if x == "s_nop 0"]
-            assert len(nops) == 2 and body[nops[0] - 1].startswith("s_waitcnt") and nops[0] == 1
-            body[nops[1]] = "s_sub_u32 %[cnt], %[cnt], 1"
-            del body[nops[0]]
-            L.extend(body)
-            L.append("v_add_u32_e64 %[h0], %[h0], %[r0]")
-            L.extend(f"v_add_u32 %[h{i}], %[h{i}], %[r{i}]" for i in range(1, 5))
-            L += (STAMP_SEQ if STAMP else ["s_barrier"]) + ["s_cmp_eq_u32 %[cnt], 0",
-                  "s_cbranch_scc1 L_rdone_%=" if k < LDS_BUFS - 1 else "s_cbranch_scc0 L_rloop_%="]
-        L += ["L_rdone_%=:", "s_waitcnt lgkmcnt(0)"]
-        return "\n".join(f'    "{l}\\n"' for l in L)
-    L.append("L_rloop_%=:")
-    for k in range(LDS_BUFS):
-        L.append(".p2align 3")
-        if TWIN_PRE:
-            L.extend(_emit_lines(gen_twin(k * RING_BYTES, reads_next=((k + 1) % LDS_BUFS) * RING_BYTES)))
-        else:
-            L.extend(_emit_lines(gen_twin(k * RING_BYTES, lead=True)))
-        L.extend(f"v_add_u32 %[h{i}], %[h{i}], %[r{i}]" for i in range(5))
-        L.append("s_barrier")
-        L += ["s_sub_u32 %[cnt], %[cnt], 1", "s_cmp_eq_u32 %[cnt], 0",
-              "s_cbranch_scc1 L_rdone_%=" if k < LDS_BUFS - 1 else "s_cbranch_scc0 L_rloop_%="]
-    L += ["L_rdone_%=:", "s_waitcnt lgkmcnt(0)"]
-    return "\n".join(f'    "{l}\\n"' for l in L)
 
 
 P0_BASE, P1_BASE, VL = 112, 128, 144   # prefetch buffers (2 blocks) and the running load pointer
@@ -737,9 +806,9 @@ def emulate(ins, regs: dict, lds: dict | None = None, addr: int = 0, on_barrier=
             base, off = op[1], op[2]
             for j in range(4):
                 lds[addr + off + 4 * j] = v(f"v{base + j}")
-        elif o == "ds_read_b128":
+        elif o in ("ds_read_b128", "ds_read_b128_abs"):
             q, off = op[1], op[2]
-            rs = [ring_reg(q, j) for j in range(4)]
+            rs = [ring_reg(q, j) if o == "ds_read_b128" else f"v{RING_BASE + 4 * q + j}" for j in range(4)]
             for x in rs:
                 for prs, _, _ in pending:
                     assert x not in prs, f"ds_read into {x} while it is in flight"
@@ -846,7 +915,7 @@ def _check_block(block: bytes, h):
             a = 1024 + (t // 8) * TWIN_READ_BYTES + (2 + t % 2) * 16 + 4 * ((t % 8) // 2)
             assert lds[a] == (ww[t] + K[t // 20]) & M32, "SHA1_HELPER2 mismatch"
         regs2 = [dict(base), dict(base)]
-        emulate_twin(gen_twin(0, lead=True), regs2, lds, [1024 + 2 * 16, 1024 + 3 * 16])
+        emulate_twin(gen_twin(0), regs2, lds, [1024 + 2 * 16, 1024 + 3 * 16])
         for ln in range(2):
             got = [(h[i] + regs2[ln][f"r{i}"]) & M32 for i in range(5)]
             assert got == exp, f"SHA1_TWIN mismatch (lane {ln})"
@@ -961,12 +1030,13 @@ def check_twin_stream(blocks, h):
             put(k + 2, kws[k + 2], in_flight)
 
     regs2 = [{f"h{i}": h[i] for i in range(5)} for _ in range(2)]
-    ins = [("ds_read_b128", k, k * TWIN_READ_BYTES) for k in range(10)] if TWIN_PRE else []
+    walk = twin_trips_walk(len(blocks))   # the blocks in the order the loop text's control flow runs them
+    assert [buf for _, buf, _ in walk] == [k % LDS_BUFS for k in range(len(blocks))]
+    ins = [("ds_read_b128_abs", TWIN_SET_QUADS * walk[0][0] + q, q * TWIN_READ_BYTES) for q in range(TWIN_SET_QUADS)]
     for k in range(len(blocks)):
-        if TWIN_PRE:
-            ins += gen_twin((k % LDS_BUFS) * RING_BYTES, reads_next=((k + 1) % LDS_BUFS) * RING_BYTES)
-        else:
-            ins += gen_twin((k % LDS_BUFS) * RING_BYTES, lead=True)
+        s, _, nxt = walk[k]
+        assert k == 0 or (walk[k - 1][0] != s and walk[k - 1][2] == walk[k][1])   # the reads the block before issued
+        ins += gen_twin_trip_block(s, nxt * RING_BYTES)
         ins += [("v_add_u32", f"h{i}", f"h{i}", f"r{i}") for i in range(5)] + [("s_barrier",)]
     ins.append(("s_waitcnt_lgkm", 0))
     emulate_twin(ins, regs2, lds, [0, 16], on_barrier=on_barrier)
@@ -1006,8 +1076,9 @@ def self_check():
         h0 = [0x67452301, 0xEFCDAB89, 0x98BADCFE, 0x10325476, 0xC3D2E1F0]
         h = check_split_mid_stream([padded[i:i + 64] for i in range(0, len(padded), 64)], h0, pre=True)
         assert struct.pack(">5I", *h) == hashlib.sha1(msg).digest(), ("split pre stream", n)
-    # the TWIN rounds loop over 1 .. 7 consecutive blocks (every buffer phase)
-    for n in ([0, 55, 64, 119, 200, 310, 400] if LDS_BUFS == 3 and not K_IN_ROUNDS else []):
+    # the TWIN rounds loop over 1 .. 7, 8, 13 and 15 consecutive blocks: every buffer phase, and both parities of
+    # the block count go round the six-block loop body
+    for n in ([0, 55, 64, 119, 200, 310, 400, 500, 800, 900] if LDS_BUFS == 3 and not K_IN_ROUNDS else []):
         msg = bytes(rng.randrange(256) for _ in range(n))
         padded = msg + b"\x80" + b"\0" * ((55 - n) % 64) + struct.pack(">Q", 8 * n)
         h0 = [0x67452301, 0xEFCDAB89, 0x98BADCFE, 0x10325476, 0xC3D2E1F0]
@@ -1037,6 +1108,10 @@ def _emit_lines(ins, full: bool = False):
             lo = RING_BASE + 4 * (q % RING_QUADS)
             a, off = ("%[addr2]", off - 65536) if off >= 65536 else ("%[addr]", off)   # (16-bit DS offsets)
             lines.append(f"ds_read_b128 v[{lo}:{lo + 3}], {a} offset:{off}")
+        elif o == "ds_read_b128_abs":   # quad index without the ring's wrap (the twin loop's register sets)
+            lo = RING_BASE + 4 * op[1]
+            assert op[2] < 65536
+            lines.append(f"ds_read_b128 v[{lo}:{lo + 3}], %[addr] offset:{op[2]}")
         elif o == "v_bitop3_b32":
             lines.append(f"v_bitop3_b32 {_opnd(op[1], full)}, {_opnd(op[2], full)}, {_opnd(op[3], full)}, "
                          f"{_opnd(op[4], full)} bitop3:0x{op[5]:02x}")
@@ -1189,7 +1264,7 @@ __device__ __forceinline__ void tv_sha1_twin_rounds_loop(uint32_t h[5], uint32_t
       [r0] "=&v"(r[0]), [r1] "=&v"(r[1]), [r2] "=&v"(r[2]), [r3] "=&v"(r[3]), [r4] "=&v"(r[4]),
       [t0] "=&v"(t0), [t1] "=&v"(t1), [cnt] "=&s"(cnt)
     : [addr] "v"(addr){addr2}, [nsteps] "s"(nsteps)
-    : {ring_clobbers}, "scc", "memory");
+    : {twin_ring_clobbers}, "scc", "memory");
 }}
 
 // The TWIN helper wave (64 pieces, one lane each) over its nraw (>= 1) raw blocks: as
@@ -1226,6 +1301,8 @@ def render() -> str:
     ring = ", ".join(f'"v{RING_BASE + i}"' for i in range(4 * RING_QUADS))
     hregs = list(range(HW_BASE, HW_BASE + 16)) + [HT, HT2] + list(range(HOUT_BASE, HOUT_BASE + 4 * HOUT_QUADS))
     helper = ", ".join(f'"v{i}"' for i in hregs)
+    # (the two-block-trip twin loop: two sets of ten quads)
+    twin_ring = ", ".join(f'"v{RING_BASE + i}"' for i in range(4 * max(RING_QUADS, 2 * TWIN_SET_QUADS)))
     loop = ", ".join(f'"v{i}"' for i in hregs + list(range(P0_BASE, VL + 2)))
     h2regs = list(range(H2_F, H2_O + 12))
     h2 = ", ".join(f'"v{i}"' for i in h2regs)
@@ -1238,11 +1315,11 @@ def render() -> str:
                          helper_loop=helper_loop_text(), rounds_loop=rounds_loop_text(),
                          ring_clobbers=ring, helper_clobbers=helper,
                          loop_clobbers=loop) + ("" if K_IN_ROUNDS else TWIN_HEADER.format(
-                             twin_lds='    ".p2align 3\\n"\n' + emit(gen_twin(0, lead=True), False),
+                             twin_lds='    ".p2align 3\\n"\n' + emit(gen_twin(0), False),
                              twin_rounds_loop=twin_rounds_loop_text(),
                              twin_helper_loop=helper_loop_text(twin=True),
                              twin_helper=emit(gen_helper2(), False),
-                             ring_clobbers=ring, twin_helper_clobbers=h2, twin_loop_clobbers=h2loop, addr2=addr2))
+                             ring_clobbers=ring, twin_ring_clobbers=twin_ring, twin_helper_clobbers=h2, twin_loop_clobbers=h2loop, addr2=addr2))
 
 
 def _stamp_patch(txt: str) -> str:

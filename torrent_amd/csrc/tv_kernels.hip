@@ -457,8 +457,9 @@ __global__ __launch_bounds__(128 * PAIRS) void tv_split_kernel(TvPieces p) {
 // and helper waves 2, 3 over 64 pieces; in each wave lane 2i + b runs piece 32(wave & 1) + i and owns its
 // schedule words of parity b (tools/gen_sha1_asm.py gen_twin / gen_helper2).  Rounds: both lanes of a pair
 // run the same rounds; lane b reads only its own K+W words and each round's `e + KW` add takes KW from lane
-// t % 2 of the pair through DPP: 10 ds_read_b128 per block instead of 20, serial stream 405 VALU + 10 LDS
-// + 2 waits.  Helper: 192 VALU + 10 ds_write_b128 per block (W[32..79] from the parity-closed recurrence
+// t % 2 of the pair through DPP: 10 ds_read_b128 per block instead of 20.  The loop over the full blocks runs
+// two blocks per trip on two register sets for the K+W quads: serial stream 405 VALU + 10 LDS + 1 wait +
+// barrier per block and one s_sub + s_cbranch per two blocks.  Helper: 192 VALU + 10 ds_write_b128 per block (W[32..79] from the parity-closed recurrence
 // W[t] = rotl2(W[t-6] ^ W[t-16] ^ W[t-28] ^ W[t-32])), half a split helper's stream.  K+W ring: 3 x 20 KiB,
 // the helpers two blocks ahead, one 4-wave barrier per block.  Four waves per 64 pieces fill the SIMDs up
 // to 16,384 pieces (cfg2: 256 workgroups, one per CU).
