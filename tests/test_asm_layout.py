@@ -71,6 +71,8 @@ def test_built_hot_loops_alignment():
         # pinned at 4 mod 64 (1 % faster at cfg2 than where the code before it happened to put it in round 3:
         # profiles/r03/twin_ralign.jsonl)
         assert int(r["first"], 16) % 64 == 4, r
-    # the twin helper loop (3 blocks, ~350 instructions) pinned at 60 mod 64
-    helper = [r for r in rep["twin"] if 300 <= r["instrs"] <= 400]
+    # the twin helper loop (6 blocks of 192 VALU + 10 ds_write_b128 + loads and waits: ~1,300 instructions, a
+    # third of them 4-byte) pinned at 60 mod 64.  (The rounds wave's loop over the padded tail blocks, ~350
+    # instructions, is not pinned: it runs only in the short last piece's workgroup.)
+    helper = [r for r in rep["twin"] if 1000 <= r["instrs"] < 1500 and r["eight_byte"] < 0.7 * r["instrs"]]
     assert helper and all(int(r["first"], 16) % 64 == 60 for r in helper), rep["twin"]

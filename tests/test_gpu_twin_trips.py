@@ -14,6 +14,12 @@ parity, and the padded tail blocks must follow on the right ring buffer.  Here t
     with companion workgroups (TV_OPT_TWIN_FILL) on and off;
   * creation mode (tv_hash), tv_verify with one digest in seven corrupted, and the twin list kernel
     (tv_verify_list) over the same pieces in shuffled order.
+
+The split kernel runs the same helper-wave and rounds-wave bodies as the twin kernel (tv_kernels.hip helper_wave /
+rounds_wave), so the same lengths, counts, short last pieces and checks also run with the 2-pair twin workgroup
+(TV_OPT_SPLIT_PAIRS = 2) and with the split kernel forced (TV_OPT_KERNEL = 2) at 1 and 2 pairs per workgroup.  A
+split workgroup covers 64 pieces per pair, so its rows add 65, 128 and 129 pieces: one 1-pair workgroup and a bit,
+exactly two, two and a bit.
 """
 import hashlib
 import random
@@ -21,7 +27,11 @@ import random
 import pytest
 
 TWIN = 4
+SPLIT = 2
+# the other kernels on the shared wave bodies: name -> (TV_OPT_KERNEL, TV_OPT_SPLIT_PAIRS)
+VARIANTS = {"twin2": (TWIN, 2), "split1": (SPLIT, 1), "split2": (SPLIT, 2)}
 COUNTS = [1, 31, 32, 33, 64, 96]
+SPLIT_COUNTS = [65, 128, 129]
 # 64 k - 9, 64 k - 8, 64 k, 64 k + 1 for k = 1 .. 6 (k, k + 1, k + 1, k + 1 blocks), and the one-byte piece
 LENGTHS = [1] + [64 * k + d for k in range(1, 7) for d in (-9, -8, 0, 1)]
 
@@ -38,7 +48,7 @@ def _bits(bf, P):
     return [(bf[i >> 3] >> (7 - (i & 7))) & 1 for i in range(P)]
 
 
-def _check(native, ctx, L, P, last, seed):
+def _check(native, ctx, L, P, last, seed, kernel=TWIN):
     total = L * (P - 1) + last
     rng = random.Random(seed)
     payload = rng.randbytes(total)
@@ -46,7 +56,7 @@ def _check(native, ctx, L, P, last, seed):
     ctx.set_layout(total, L, P)
     ctx.stage(0, payload)
     assert ctx.hash() == good, (L, P, last)
-    assert ctx.last_kernel()[0] == native.KERNEL_TWIN
+    assert ctx.last_kernel()[0] == kernel
     bad = set(range(P // 2 % 7, P, 7))          # one digest in seven
     pieces = bytearray(good)
     for i in bad:
@@ -55,7 +65,7 @@ def _check(native, ctx, L, P, last, seed):
     want = [0 if i in bad else 1 for i in range(P)]
     bf = ctx.verify()
     assert len(bf) == (P + 7) // 8 and _bits(bf, P) == want, (L, P, last)
-    assert ctx.last_kernel()[0] == native.KERNEL_TWIN
+    assert ctx.last_kernel()[0] == kernel
     order = list(range(P))
     rng.shuffle(order)
     assert list(ctx.verify_list(order)) == [want[i] for i in order], (L, P, last)
@@ -69,6 +79,22 @@ def test_lengths_cover_every_block_count_and_padding_class():
     assert _nblocks(1) == 1 and _nblocks(55) == 1 and _nblocks(56) == 2
 
 
+def _block_counts(native, ctx, P, kernel):
+    for L in LENGTHS:
+        _check(native, ctx, L, P, L, seed=L * 131 + P, kernel=kernel)
+
+
+def _short_last_piece(native, ctx, P, kernel):
+    for L in [l for l in LENGTHS if _nblocks(l) >= 2]:
+        lasts = {L - 64 if L > 64 else L - 9, 1}
+        assert any(_nblocks(x) % 2 != _nblocks(L) % 2 for x in lasts)
+        for last in sorted(lasts):
+            _check(native, ctx, L, P, last, seed=L * 977 + P * 7 + last, kernel=kernel)
+    assert _nblocks(16384) == 257 and _nblocks(8192) == 129
+    _check(native, ctx, 16384, P, 8192 - 64, seed=P, kernel=kernel)          # 257 blocks, last piece 128
+    _check(native, ctx, 16384 - 64, P, 8192, seed=P + 1, kernel=kernel)      # 256 blocks, last piece 129
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("fill", [1, 0])
 @pytest.mark.parametrize("P", COUNTS)
@@ -77,8 +103,7 @@ def test_twin_block_counts(native, P, fill):
     with native.Context(0) as ctx:
         ctx.set_option(native.TV_OPT_KERNEL, TWIN)
         ctx.set_option(native.TV_OPT_TWIN_FILL, fill)
-        for L in LENGTHS:
-            _check(native, ctx, L, P, L, seed=L * 131 + P)
+        _block_counts(native, ctx, P, TWIN)
 
 
 @pytest.mark.gpu
@@ -91,11 +116,33 @@ def test_twin_short_last_piece_of_other_parity(native, P, fill):
     with native.Context(0) as ctx:
         ctx.set_option(native.TV_OPT_KERNEL, TWIN)
         ctx.set_option(native.TV_OPT_TWIN_FILL, fill)
-        for L in [l for l in LENGTHS if _nblocks(l) >= 2]:
-            lasts = {L - 64 if L > 64 else L - 9, 1}
-            assert any(_nblocks(x) % 2 != _nblocks(L) % 2 for x in lasts)
-            for last in sorted(lasts):
-                _check(native, ctx, L, P, last, seed=L * 977 + P * 7 + last)
-        assert _nblocks(16384) == 257 and _nblocks(8192) == 129
-        _check(native, ctx, 16384, P, 8192 - 64, seed=P)          # 257 blocks, last piece 128
-        _check(native, ctx, 16384 - 64, P, 8192, seed=P + 1)      # 256 blocks, last piece 129
+        _short_last_piece(native, ctx, P, TWIN)
+
+
+def _variant_cases(counts):
+    """(variant, P): the twin counts for every variant, and for the split rows the split counts too."""
+    return [(v, P) for v, (kernel, _) in VARIANTS.items()
+            for P in counts + ([c for c in SPLIT_COUNTS if c not in counts] if kernel == SPLIT else [])]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant,P", _variant_cases(COUNTS))
+def test_variant_block_counts(native, variant, P):
+    """As test_twin_block_counts, for the 2-pair twin workgroup and the split kernel at 1 and 2 pairs."""
+    kernel, pairs = VARIANTS[variant]
+    with native.Context(0) as ctx:
+        ctx.set_option(native.TV_OPT_KERNEL, kernel)
+        ctx.set_option(native.TV_OPT_SPLIT_PAIRS, pairs)
+        _block_counts(native, ctx, P, kernel)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant,P", _variant_cases([2, 33, 65, 97]))
+def test_variant_short_last_piece_of_other_parity(native, variant, P):
+    """As test_twin_short_last_piece_of_other_parity, for the 2-pair twin workgroup and the split kernel at 1 and
+    2 pairs (the short last piece's own workgroup follows 1, 32, 64, 96 and, split, 127 and 128 full pieces)."""
+    kernel, pairs = VARIANTS[variant]
+    with native.Context(0) as ctx:
+        ctx.set_option(native.TV_OPT_KERNEL, kernel)
+        ctx.set_option(native.TV_OPT_SPLIT_PAIRS, pairs)
+        _short_last_piece(native, ctx, P, kernel)
