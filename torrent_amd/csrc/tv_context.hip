@@ -426,7 +426,7 @@ int tv_set_layout(tv_ctx* c, uint64_t total_length, uint64_t piece_length, uint6
         if (!budget) {
             size_t fr = 0, tot = 0;
             TV_HIP(c, hipMemGetInfo(&fr, &tot));
-            const uint64_t avail = (uint64_t)fr + c->cap_payload + 2 * c->chunk_bytes;
+            const uint64_t avail = (uint64_t)fr + c->cap_payload + c->d_chunk[0].bytes() + c->d_chunk[1].bytes();
             const uint64_t margin = (4ull << 30) + 64 * shard_count;
             budget = avail > margin ? avail - margin : 0;
         }
@@ -482,8 +482,12 @@ int tv_set_layout(tv_ctx* c, uint64_t total_length, uint64_t piece_length, uint6
     c->budget = budget;
     if (!reuse_fits(shard_count, c->cap_count)) free_per_piece(c);
     if (!reuse_fits(c->bit_words, c->cap_words)) free_words(c);
-    if (c->chunk_bytes && (need_payload || !reuse_fits(stream_chunk_need(c), c->chunk_bytes))) free_chunks(c);
-    if (c->list_cap > std::max<uint64_t>(1024, 2 * shard_count)) free_list(c);
+    for (DevBuf& b : c->d_chunk)
+        if (need_payload || !reuse_fits(stream_chunk_need(c), b.cap)) free_buf(b);
+    if (c->d_list.cap > std::max<uint64_t>(1024, 2 * shard_count)) {
+        free_buf(c->d_list);
+        free_buf(c->d_list_out);
+    }
     v2_on_layout(c);
     hybrid_on_layout(c);
     if (shard_count && !c->d_digests) {
@@ -529,10 +533,7 @@ int tv_set_digests(tv_ctx* c, const uint8_t* pieces, uint64_t pieces_len) {
     for (uint64_t j = 0; j < c->count; j++) {
         const uint64_t i = c->first + j;
         if (20 * i + 20 > pieces_len) continue;  // short or missing slice: never equal
-        const uint8_t* d = pieces + 20 * i;
-        for (int k = 0; k < 5; k++)
-            soa[(uint64_t)k * c->count + j] = ((uint32_t)d[4 * k] << 24) | ((uint32_t)d[4 * k + 1] << 16) |
-                                              ((uint32_t)d[4 * k + 2] << 8) | (uint32_t)d[4 * k + 3];
+        digest_pack(pieces + 20 * i, 5, soa.data(), c->count, j);
         set_bit(c->digest_ok.data(), j);
     }
     if (c->count) {
@@ -596,12 +597,9 @@ int tv_get_counter(tv_ctx* c, int key, uint64_t* value) {
         case TV_COUNTER_PAYLOAD_ALLOCS: *value = c->n_payload_allocs; return TV_OK;
         case TV_COUNTER_DEVICE_ALLOCS: *value = c->n_device_allocs; return TV_OK;
         case TV_COUNTER_PAYLOAD_BYTES: *value = c->cap_payload; return TV_OK;
-        case TV_COUNTER_DEVICE_BYTES:
-            *value = c->cap_payload + c->cap_count * 3 * 5 * sizeof(uint32_t) + c->cap_words * 8 * 3 +
-                     2 * c->chunk_bytes + c->list_cap * 9 + c->cap_v2_count * 18 * sizeof(uint32_t) +
-                     c->cap_v2_nodes * sizeof(uint32_t) + (c->v2_list_cap + c->v2_blk_cap) * 48 +
-                     (c->cap_v2s_tab + c->cap_v2s_nodes) * sizeof(uint32_t) +
-                     c->cap_hy_tails * sizeof(HybridTail) + 2 * c->cap_hy_words * 8;
+        case TV_COUNTER_DEVICE_BYTES:   // what tv_set_layout allocates, and every buffer of the calls
+            *value = c->cap_payload + c->cap_count * 3 * 5 * sizeof(uint32_t) + c->cap_words * 8 * 3;
+            for (const DevBuf* b : c->call_bufs) *value += b->bytes();
             return TV_OK;
         case TV_COUNTER_LAST_WORKGROUPS: *value = c->last_workgroups; return TV_OK;
         case TV_COUNTER_NUMA_NODE: *value = c->numa_node < 0 ? UINT64_MAX : (uint64_t)c->numa_node; return TV_OK;

@@ -334,25 +334,30 @@ void free_words(tv_ctx* c) {
     c->cap_words = 0;
 }
 
-void free_chunks(tv_ctx* c) {
-    for (auto& p : c->d_chunk) { (void)hipFree(p); p = nullptr; }
-    c->chunk_bytes = 0;
+void free_buf(DevBuf& b) {
+    if (b.ptr) (void)hipFree(b.ptr);
+    b.ptr = nullptr;
+    b.cap = 0;
 }
 
-void free_list(tv_ctx* c) {
-    (void)hipFree(c->d_list); c->d_list = nullptr;
-    (void)hipFree(c->d_list_out); c->d_list_out = nullptr;
-    c->list_cap = 0;
+bool buf_fits(const DevBuf& b, uint64_t need, bool reuse) {
+    return b.ptr && (reuse ? reuse_fits(need, b.cap) : b.cap >= need);
+}
+
+int grow_buf(tv_ctx* c, DevBuf& b, uint64_t need, bool reuse, uint64_t cap) {
+    if (buf_fits(b, need, reuse)) return TV_OK;
+    free_buf(b);
+    TV_HIP(c, hipMalloc(&b.ptr, cap * b.unit));
+    b.cap = cap;
+    c->n_device_allocs++;
+    return TV_OK;
 }
 
 void free_device(tv_ctx* c) {
     free_payload(c);
     free_per_piece(c);
     free_words(c);
-    free_chunks(c);
-    free_list(c);
-    free_v2(c);
-    free_hybrid(c);
+    for (DevBuf* b : c->call_bufs) free_buf(*b);
 }
 
 // An allocation of `cap` units is reused for `need` units when it holds them and is not more than twice
@@ -360,12 +365,6 @@ void free_device(tv_ctx* c) {
 bool reuse_fits(uint64_t need, uint64_t cap) {
     return need <= cap && (cap <= (64ull << 20) || need >= cap / 2);
 }
-
-// Staging lane `which`: 0 = copy_stream + ring, 1 = copy_stream2 + ring2.  Lane 1 is used only by
-// tv_stage_files' helper thread, so the two lanes never share a ring slot or a stream.
-
-
-// The CPUs the context's library threads run on: the GPU's NUMA node when bound, else none (unpinned).
 
 void apply_numa(tv_ctx* c) {
     for (auto& p : c->pool) p.set_affinity(numa_cpus(c), c->proc_cpus_ok ? &c->proc_cpus : nullptr);
@@ -419,8 +418,6 @@ int release_slot(tv_ctx* c, int slot, int which) {
     return TV_OK;
 }
 
-// A lent slot that goes back to the ring on every exit of its scope (error paths included).
-
 // Base availability of every shard piece, computed once per tv_set_digests and kept in HBM: the
 // digest slice is complete (metainfo.ts:111) and the piece's bytes lie inside the torrent (piece.ts:16-19
 // length at offset i*L must end <= total).
@@ -437,25 +434,68 @@ int upload_base_avail(tv_ctx* c) {
     return TV_OK;
 }
 
-// Availability for one launch: the base bits, or base & the caller's bits (Storage.get -> null for
-// a missing / short file) & not the pieces file staging could not read, queued on the compute stream from
-// the pinned bounce buffer (no host sync).
-int launch_avail(tv_ctx* c, const uint8_t* avail_bits, const uint64_t** out) {
-    const bool unhashed = c->win && c->any_unhashed;
-    if (!avail_bits && !c->any_file_bad && !unhashed) {
-        *out = c->d_base_avail;
-        return TV_OK;
-    }
-    TV_HIP(c, hipEventSynchronize(c->ev_avail));  // the previous copy out of h_avail is done
+// The availability bytes of one launch, bit_words * 8 of them: the caller's bits (Storage.get -> null for a missing /
+// short file; NULL: all) & not the pieces file staging could not read and, for a v1 launch, & the base bits & not the
+// pieces a windowed pass never hashed.  false = nothing narrows the default (dst untouched).
+static bool avail_bytes(const tv_ctx* c, const uint8_t* avail_bits, bool v1, uint8_t* dst) {
+    const bool unhashed = v1 && c->win && c->any_unhashed;
+    if (!avail_bits && !c->any_file_bad && !unhashed) return false;
     const size_t nbytes = c->bit_words * 8, used = (c->count + 7) / 8;
     for (size_t k = 0; k < nbytes; k++) {
         const uint8_t caller = k < used ? (avail_bits ? avail_bits[k] : 0xFF) : 0;
         const uint8_t bad = k < used ? (uint8_t)(c->file_bad[k] | (unhashed ? c->unhashed[k] : 0)) : 0;
-        c->h_avail[k] = c->base_avail[k] & caller & (uint8_t)~bad;
+        dst[k] = (v1 ? c->base_avail[k] : 0xFF) & caller & (uint8_t)~bad;
     }
-    TV_HIP(c, hipMemcpyAsync(c->d_avail, c->h_avail, nbytes, hipMemcpyHostToDevice, c->stream));
+    return true;
+}
+
+bool v2_avail_bits(const tv_ctx* c, const uint8_t* avail_bits, uint8_t* dst) {
+    return avail_bytes(c, avail_bits, false, dst);
+}
+
+// Availability for one launch, queued on the compute stream from the pinned bounce buffer (no host sync).  By default
+// a v1 launch reads the base bits and a v2 launch (v1 = false) none: null = every piece.
+int launch_avail(tv_ctx* c, const uint8_t* avail_bits, const uint64_t** out, bool v1) {
+    *out = v1 ? c->d_base_avail : nullptr;
+    if (!avail_bits && !c->any_file_bad && !(v1 && c->win && c->any_unhashed)) return TV_OK;
+    TV_HIP(c, hipEventSynchronize(c->ev_avail));  // the previous copy out of h_avail is done
+    avail_bytes(c, avail_bits, v1, c->h_avail);
+    TV_HIP(c, hipMemcpyAsync(c->d_avail, c->h_avail, c->bit_words * 8, hipMemcpyHostToDevice, c->stream));
     TV_HIP(c, hipEventRecord(c->ev_avail, c->stream));
     *out = c->d_avail;
+    return TV_OK;
+}
+
+// ---- the steps the list calls share ------------------------------------------------------------------------------------
+
+int list_in_shard(tv_ctx* c, uint64_t piece) {
+    if (piece >= c->first && piece < c->first + c->count) return TV_OK;
+    return fail(c, TV_ERR_ARG, "piece %llu is not in this context's shard [%llu, %llu)", (unsigned long long)piece,
+                (unsigned long long)c->first, (unsigned long long)(c->first + c->count));
+}
+
+// (a failed piece is staged anew when it is re-downloaded)
+void list_release(tv_ctx* c, uint64_t n, const uint64_t* pieces) {
+    if (!c->slots) return;
+    for (uint64_t k = 0; k < n; k++) {
+        auto it = c->slot_of.find(pieces[k] - c->first);
+        if (it == c->slot_of.end()) continue;
+        c->slot_free.push_back(it->second);
+        c->slot_of.erase(it);
+    }
+}
+
+void list_zero_unread(const tv_ctx* c, uint64_t n, const uint64_t* pieces, uint8_t* ok_out) {
+    if (!c->any_file_bad) return;
+    for (uint64_t k = 0; k < n; k++)
+        if (get_bit(c->file_bad.data(), pieces[k] - c->first)) ok_out[k] = 0;
+}
+
+int list_finish(tv_ctx* c, int kernel, uint64_t m) {
+    c->last_kernel = kernel;
+    c->last_launches = m ? 1 : 0;
+    if (m) return finish_timing(c);
+    c->kernel_ms = c->total_ms = 0.f;
     return TV_OK;
 }
 

@@ -4,6 +4,9 @@
 // tv_files.hip: staging from files; tv_stream.hip: the streamed engine; tv_verify.hip: verify / list / hash;
 // tv_v2.hip: the BitTorrent v2 piece table, verify, hash and list verify (the streamed v2 verify: tv_stream.hip);
 // tv_hybrid.hip: hybrid torrents (the pad kernel, then the SHA-1 and the v2 launches over one staging).
+// The device memory a call allocates is a DevBuf each (grow_buf / free_buf, tv_core.hip): the context lists them, so
+// free_device and TV_COUNTER_DEVICE_BYTES cover every one.  The steps the list calls share (list_*) are in tv_core.hip,
+// their pure parts (the digest-word codec, the v1 list's launch order) in tv_plan.h.
 // Nothing here is exported (the link exports tv_* only: exports.map).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -155,8 +158,23 @@ struct Bounce {
     bool recorded = false;
 };
 
+// One device allocation made by a call (not by tv_set_layout): `cap` units of `unit` bytes at `ptr`.  It registers
+// itself with its context (tv_ctx::call_bufs), which frees (free_device) and counts (TV_COUNTER_DEVICE_BYTES) by that
+// list.  grow_buf / free_buf (tv_core.hip) are the only code that allocates or frees one.
+struct DevBuf {
+    const uint32_t unit;
+    void* ptr = nullptr;
+    uint64_t cap = 0;
+    DevBuf(std::vector<DevBuf*>& all, uint32_t unit_bytes) : unit(unit_bytes) { all.push_back(this); }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    template <class T> T* get() const { return static_cast<T*>(ptr); }
+    uint64_t bytes() const { return cap * unit; }
+};
+
 }  // namespace tvi
 
+using tvi::DevBuf;
 using tvi::kRingSlots;
 using tvi::Pool;
 using tvi::StreamState;
@@ -206,6 +224,8 @@ struct tv_ctx {
     hipStream_t pack_stream = nullptr;       // twin launches CU-masked to pack_cus CUs (TV_OPT_TWIN_PACK)
     int pack_cus = 0;
 
+    std::vector<DevBuf*> call_bufs;   // every DevBuf below (declared before them: they register as they are built)
+
     // allocation capacities (tv_set_layout reuses what fits)
     uint64_t cap_payload = 0;   // bytes of d_payload
     uint64_t cap_count = 0;     // pieces of d_digests / d_state / d_hash
@@ -221,11 +241,9 @@ struct tv_ctx {
     uint64_t* d_out = nullptr;
     uint32_t* d_state = nullptr;      // [5][count]
     uint32_t* d_hash = nullptr;       // [5][count]
-    uint8_t* d_chunk[2] = {nullptr, nullptr};
-    uint32_t* d_list = nullptr;       // tv_verify_list indices
-    uint8_t* d_list_out = nullptr;
-    uint64_t list_cap = 0;
-    uint64_t chunk_bytes = 0;
+    DevBuf d_chunk[2] = {{call_bufs, 1}, {call_bufs, 1}};   // a stream's chunk buffers (bytes; both of one size)
+    DevBuf d_list{call_bufs, 8};      // tv_verify_list: cap indices, then cap rows (slot pool), 32-bit
+    DevBuf d_list_out{call_bufs, 1};  // ... and its cap out bytes
     size_t bit_words = 0;
 
     bool digests_set = false;
@@ -324,21 +342,16 @@ struct tv_ctx {
     bool v2_hashes = false;            // ... with expected hashes (tv_v2_verify needs them)
     uint32_t v2_logW = 0;              // log2(L / 16 KiB)
     uint32_t v2_maxlog = 0;            // log2 of the widest tree in the shard (tree levels to run)
-    uint32_t* d_v2_tab = nullptr;      // [18][cap_v2_count]: piece bytes, tree leaves, expected [8], roots [8]
-    uint32_t* d_v2_nodes = nullptr;    // level buffers A [8][count x W] then B [8][count x max(W/2, 1)]
-    uint64_t cap_v2_count = 0;         // pieces of d_v2_tab
-    uint64_t cap_v2_nodes = 0;         // words of d_v2_nodes
-    uint32_t* d_v2_list = nullptr;     // tv_v2_verify_list: [11][m] rows, bytes, widths, expected [8], then v2_list_cap out bytes
-    uint64_t v2_list_cap = 0;          // entries of d_v2_list (48 bytes each)
-    // tv_v2_leaf_hashes / tv_v2_check_blocks: ceil(m / 64) ballot words of a check, then [11][m] rows, leaves, lens,
-    // hash words [8] (expected or out)
-    uint32_t* d_v2_blk = nullptr;
-    uint64_t v2_blk_cap = 0;           // items of d_v2_blk (48 bytes each)
+    DevBuf d_v2_tab{call_bufs, 18 * 4};   // [18][cap] words per piece: piece bytes, tree leaves, expected [8], roots [8]
+    DevBuf d_v2_nodes{call_bufs, 4};      // words: level buffers A [8][count x W] then B [8][count x max(W/2, 1)]
+    // tv_v2_verify_list, 48 bytes per entry: [11][m] rows, bytes, widths, expected [8], then (at 11 x cap words) cap out bytes
+    DevBuf d_v2_list{call_bufs, 48};
+    // tv_v2_leaf_hashes / tv_v2_check_blocks, 48 bytes per item: ceil(m / 64) ballot words of a check, then [11][m]
+    // rows, leaves, lens, hash words [8] (expected or out)
+    DevBuf d_v2_blk{call_bufs, 48};
     // a v2 stream's device memory beyond the chunk buffers (tv_v2_stream_begin; kept for a later stream that fits)
-    uint32_t* d_v2s_tab = nullptr;     // [11][count]: piece bytes, tree leaves, top-tree widths, expected [8] per window
-    uint32_t* d_v2s_nodes = nullptr;   // a window's partial nodes: level buffers A [8][wn x ncol], B [8][wn x max(ncol/2, 1)]
-    uint64_t cap_v2s_tab = 0;          // words of d_v2s_tab
-    uint64_t cap_v2s_nodes = 0;        // words of d_v2s_nodes
+    DevBuf d_v2s_tab{call_bufs, 4};    // words, [11][count]: piece bytes, tree leaves, top-tree widths, expected [8] per window
+    DevBuf d_v2s_nodes{call_bufs, 4};  // words, a window's partial nodes: level buffers A [8][wn x ncol], B [8][wn x max(ncol/2, 1)]
     int v2_map_opt = 0;                // TV_OPT_V2_MAP: 0 auto, else TV_V2_MAP_*
     int v2_last_map = 0;               // the mapping the last v2 call's leaf kernel ran with
 
@@ -349,10 +362,8 @@ struct tv_ctx {
     uint32_t hy_n = 0, hy_chunks = 0;  // its entries and the pad launch's workgroups
     std::vector<tvi::HybridTail> hy_tails_host;   // the table on the host (TV_OPT_HYBRID_PAD_PROBE's memset leg)
     uint64_t hy_probe_ns = 0;          // TV_COUNTER_HYBRID_PAD_NS
-    tvi::HybridTail* d_hy_tails = nullptr;
-    uint64_t cap_hy_tails = 0;         // entries of d_hy_tails (16 bytes each)
-    uint64_t* d_hy_bits = nullptr;     // [2][cap_hy_words]: the v2 bitfield of a hybrid verify, then its v2 availability
-    uint64_t cap_hy_words = 0;         // 64-bit words of each half of d_hy_bits
+    DevBuf d_hy_tails{call_bufs, sizeof(tvi::HybridTail)};   // tail entries
+    DevBuf d_hy_bits{call_bufs, 2 * 8};   // [2][cap] 64-bit words: the v2 bitfield of a hybrid verify, then its v2 availability
 
     bool open_rw = true;               // TV_OPT_OPEN_RW: files opened read + write (fsStorage.get) or read-only
     bool stream_rows = false;          // TV_OPT_STREAM_ROWS: stream requests carry whole pieces (windows of pieces)
@@ -413,13 +424,18 @@ void apply_numa(tv_ctx* c);
 void free_payload(tv_ctx* c);
 void free_per_piece(tv_ctx* c);
 void free_words(tv_ctx* c);
-void free_chunks(tv_ctx* c);
-void free_list(tv_ctx* c);
-void free_v2(tv_ctx* c);
+// A call's buffer: buf_fits = it holds `need` units (reuse: by reuse_fits, so not far more than that; else any capacity
+// >= need).  grow_buf keeps a buffer that fits, else frees it and allocates `cap` units (TV_ERR_NOMEM / TV_ERR_HIP, the
+// buffer then empty); nothing queued may still use the old memory.  free_buf leaves it empty.
+bool buf_fits(const DevBuf& b, uint64_t need, bool reuse);
+int grow_buf(tv_ctx* c, DevBuf& b, uint64_t need, bool reuse, uint64_t cap);
+void free_buf(DevBuf& b);
 void v2_on_layout(tv_ctx* c);   // tv_set_layout: drop the v2 piece table, free what the new geometry does not fit
 // tv_v2_set_pieces' checks of a GLOBAL piece table against the layout (TV_ERR_ARG and its texts), shared with
 // tv_v2_stream_begin
 int v2_check_table(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const uint32_t* tree_leaves);
+// ... and of one entry, piece table or list alike: piece_bytes[k] = b, tree_leaves[k] = w
+int v2_check_entry(tv_ctx* c, uint64_t k, uint64_t b, uint64_t w);
 uint64_t v2_node_words(uint64_t count, uint64_t W);
 // tv_v2_verify / tv_v2_hash's state checks, availability, launch arguments and launch set, shared with the hybrid calls
 // (tv_hybrid.hip).  v2_avail_bits: the caller's bits less the pieces file staging could not read, bit_words * 8 bytes
@@ -428,7 +444,6 @@ int v2_require(tv_ctx* c, const char* what);
 bool v2_avail_bits(const tv_ctx* c, const uint8_t* avail_bits, uint8_t* dst);
 TvV2 v2_launch_args(tv_ctx* c);
 int v2_launch(tv_ctx* c, TvV2& p, bool hash);
-void free_hybrid(tv_ctx* c);
 int hybrid_pad_probe(tv_ctx* c, int mode);
 void hybrid_on_layout(tv_ctx* c);   // tv_set_layout: drop the tail table, free what the new geometry does not fit
 void free_device(tv_ctx* c);
@@ -525,7 +540,7 @@ void clear_bad(tv_ctx* c, uint64_t a, uint64_t b);
 // ---- availability, kernel choice, launches ------------------------------------------------------------------------
 
 int upload_base_avail(tv_ctx* c);
-int launch_avail(tv_ctx* c, const uint8_t* avail_bits, const uint64_t** out);
+int launch_avail(tv_ctx* c, const uint8_t* avail_bits, const uint64_t** out, bool v1 = true);
 int choose_kernel_n(const tv_ctx* c, uint64_t n, bool short_last);
 int choose_kernel(const tv_ctx* c);
 uint32_t lane_pairs_for(const tv_ctx* c, uint64_t n);
@@ -547,6 +562,16 @@ int win_enter(tv_ctx* c, uint64_t w);
 int win_finalize(tv_ctx* c);
 inline uint64_t win_of(const tv_ctx* c, uint64_t j) { return j / c->win_n; }  // the window of shard piece j
 uint64_t win_end_linear(const tv_ctx* c, uint64_t w);
+
+// ---- the steps the list calls share (tv_verify_list, tv_v2_verify_list, the v2 block calls) ---------------------------
+
+int list_in_shard(tv_ctx* c, uint64_t piece);            // TV_ERR_ARG and its text for a piece outside the shard
+// Shard piece j of a resident shard or a slot pool: whether it has bytes to hash, and the payload row that holds them.
+inline bool list_held(const tv_ctx* c, uint64_t j) { return !c->slots || c->slot_of.count(j); }
+inline uint32_t list_row(const tv_ctx* c, uint64_t j) { return c->slots ? c->slot_of.find(j)->second : (uint32_t)j; }
+void list_release(tv_ctx* c, uint64_t n, const uint64_t* pieces);   // a slot pool: the listed pieces' slots are free again
+void list_zero_unread(const tv_ctx* c, uint64_t n, const uint64_t* pieces, uint8_t* ok_out);  // file staging's bad pieces: 0
+int list_finish(tv_ctx* c, int kernel, uint64_t m);      // the call's record and timing (m = 0: nothing was launched)
 
 // ---- the streamed engine (tv_stream.hip) -----------------------------------------------------------------------------
 

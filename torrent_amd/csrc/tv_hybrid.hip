@@ -57,13 +57,6 @@ hipError_t launch_pad(const TvHybridPad& p, hipStream_t s) {
 
 namespace tvi {
 
-void free_hybrid(tv_ctx* c) {
-    (void)hipFree(c->d_hy_tails); c->d_hy_tails = nullptr;
-    (void)hipFree(c->d_hy_bits); c->d_hy_bits = nullptr;
-    c->cap_hy_tails = c->cap_hy_words = 0;
-    c->hy_valid = false;
-}
-
 // TV_OPT_HYBRID_PAD_PROBE (tools/hybrid_bench.py): zero the tails of the last hybrid call's table once more, timed on
 // the compute stream: mode 1 = the pad kernel's one launch, mode 2 = one hipMemsetAsync per tail (what a host holding
 // the rows would do without the kernel).  The time is TV_COUNTER_HYBRID_PAD_NS.
@@ -74,7 +67,8 @@ int hybrid_pad_probe(tv_ctx* c, int mode) {
     TV_HIP(c, hipSetDevice(c->device));
     TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
     if (mode == 1) {
-        TvHybridPad pad{c->d_payload, c->stride, c->d_hy_tails, c->hy_n, c->hy_chunks, (uint32_t)c->count, (uint32_t)c->L};
+        TvHybridPad pad{c->d_payload, c->stride, c->d_hy_tails.get<HybridTail>(), c->hy_n, c->hy_chunks,
+                        (uint32_t)c->count, (uint32_t)c->L};
         TV_HIP(c, launch_pad(pad, c->stream));
     } else {
         for (const HybridTail& t : c->hy_tails_host)
@@ -94,14 +88,8 @@ void hybrid_on_layout(tv_ctx* c) {
     c->hy_tails_host.clear();
     c->v2_tab_bytes.clear();
     // (the rules of the list buffers and of the bit words: kept while not far larger than the new shard needs)
-    if (c->d_hy_tails && c->cap_hy_tails > std::max<uint64_t>(1024, 2 * c->count)) {
-        (void)hipFree(c->d_hy_tails); c->d_hy_tails = nullptr;
-        c->cap_hy_tails = 0;
-    }
-    if (c->d_hy_bits && !reuse_fits(c->bit_words, c->cap_hy_words)) {
-        (void)hipFree(c->d_hy_bits); c->d_hy_bits = nullptr;
-        c->cap_hy_words = 0;
-    }
+    if (c->d_hy_tails.cap > std::max<uint64_t>(1024, 2 * c->count)) free_buf(c->d_hy_tails);
+    if (!reuse_fits(c->bit_words, c->d_hy_bits.cap)) free_buf(c->d_hy_bits);
 }
 
 }  // namespace tvi
@@ -137,29 +125,18 @@ int hybrid_prepare(tv_ctx* c, const char* what, bool verify) {
         if (chunks > 0x7FFFFFFFull) return fail(c, TV_ERR_ARG, "%s: too many pad chunks", what);
     }
     TV_HIP(c, hipSetDevice(c->device));
-    if (verify && (!c->d_hy_bits || c->cap_hy_words < c->bit_words)) {
+    if (verify && !buf_fits(c->d_hy_bits, c->bit_words, false)) {
         TV_HIP(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_hy_bits);
-        c->d_hy_bits = nullptr;
-        c->cap_hy_words = 0;
-        TV_HIP(c, hipMalloc((void**)&c->d_hy_bits, 2 * c->bit_words * 8));
-        c->cap_hy_words = c->bit_words;
-        c->n_device_allocs++;
+        const int rc = grow_buf(c, c->d_hy_bits, c->bit_words, false, c->bit_words);
+        if (rc) return rc;
     }
     if (c->hy_valid) return TV_OK;
     if (!tails.empty()) {
         TV_HIP(c, hipStreamSynchronize(c->stream));   // (a pad launch of the last table may still read the buffer)
-        if (c->cap_hy_tails < tails.size()) {
-            (void)hipFree(c->d_hy_tails);
-            c->d_hy_tails = nullptr;
-            c->cap_hy_tails = 0;
-            const uint64_t cap = std::max<uint64_t>(tails.size(), 1024);
-            TV_HIP(c, hipMalloc((void**)&c->d_hy_tails, cap * sizeof(HybridTail)));
-            c->cap_hy_tails = cap;
-            c->n_device_allocs++;
-        }
-        TV_HIP(c, hipMemcpyAsync(c->d_hy_tails, tails.data(), tails.size() * sizeof(HybridTail), hipMemcpyHostToDevice,
-                                 c->stream));
+        const int rc = grow_buf(c, c->d_hy_tails, tails.size(), false, std::max<uint64_t>(tails.size(), 1024));
+        if (rc) return rc;
+        TV_HIP(c, hipMemcpyAsync(c->d_hy_tails.ptr, tails.data(), tails.size() * sizeof(HybridTail),
+                                 hipMemcpyHostToDevice, c->stream));
         TV_HIP(c, hipStreamSynchronize(c->stream));
     }
     c->hy_n = (uint32_t)tails.size();
@@ -175,7 +152,7 @@ int hybrid_run(tv_ctx* c, const TvPieces& p1, TvV2& p2, bool hash) {
     TvHybridPad pad{};
     pad.data = c->d_payload;
     pad.stride = c->stride;
-    pad.tails = c->d_hy_tails;
+    pad.tails = c->d_hy_tails.get<HybridTail>();
     pad.n = c->hy_n;
     pad.chunks = c->hy_chunks;
     pad.rows = (uint32_t)c->count;
@@ -217,8 +194,8 @@ int tv_hybrid_verify(tv_ctx* c, const uint8_t* avail_bits, uint8_t* v1_bits_out,
     const uint64_t* av1 = nullptr;
     rc = launch_avail(c, avail_bits, &av1);
     if (rc) return rc;
-    uint64_t* out2 = c->d_hy_bits;
-    uint64_t* d_av2 = c->d_hy_bits + c->cap_hy_words;
+    uint64_t* out2 = c->d_hy_bits.get<uint64_t>();
+    uint64_t* d_av2 = out2 + c->d_hy_bits.cap;
     TvV2 p2 = v2_launch_args(c);
     p2.out64 = out2;
     if (v2_avail_bits(c, avail_bits, av2.data())) {
@@ -269,16 +246,8 @@ int tv_hybrid_hash(tv_ctx* c, uint8_t* digests_out, uint8_t* roots_out) {
     TV_HIP(c, hipEventRecord(c->ev_call1, c->stream));
     TV_HIP(c, hipEventSynchronize(c->ev_call1));
     for (uint64_t j = 0; j < c->count; j++) {
-        for (int k = 0; k < 5; k++) {
-            const uint32_t v = soa1[(uint64_t)k * c->count + j];
-            uint8_t* d = digests_out + 20 * j + 4 * k;
-            d[0] = (uint8_t)(v >> 24); d[1] = (uint8_t)(v >> 16); d[2] = (uint8_t)(v >> 8); d[3] = (uint8_t)v;
-        }
-        for (int k = 0; k < 8; k++) {
-            const uint32_t v = soa2[(uint64_t)k * c->count + j];
-            uint8_t* d = roots_out + 32 * j + 4 * k;
-            d[0] = (uint8_t)(v >> 24); d[1] = (uint8_t)(v >> 16); d[2] = (uint8_t)(v >> 8); d[3] = (uint8_t)v;
-        }
+        digest_unpack(soa1.data(), c->count, j, 5, digests_out + 20 * j);
+        digest_unpack(soa2.data(), c->count, j, 8, roots_out + 32 * j);
     }
     return finish_timing(c);
 }

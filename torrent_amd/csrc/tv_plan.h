@@ -1,10 +1,11 @@
 // tv_plan.h -- the resident payload's shape under a device budget (tv_set_layout), a stream's windows x columns under
 // one (stream_geometry; v2_stream_geometry for a BitTorrent v2 stream), the file table's walk (walk_file_table) and a
 // v2 torrent's aligned file offsets (v2_file_starts) and the item list of a v2 block launch (v2_block_items,
-// v2_block_scatter) and the tail table of a hybrid call (hybrid_tails), as plain host code with no HIP in it, so they
-// are unit-tested on the CPU (tests/c/plan_test.cpp, tests/c/walk_main.cpp, tests/c/plan_v2_main.cpp,
-// tests/c/plan_v2_blocks_main.cpp, tests/c/plan_hybrid_main.cpp; tests/test_plan.py, test_plan_v2.py,
-// test_plan_v2_blocks.py, test_plan_hybrid.py).
+// v2_block_scatter), the digest-word codec (digest_pack, digest_unpack), the launch order of a v1 list (list_plan)
+// and the tail table of a hybrid call (hybrid_tails), as plain host code with no HIP in it, so they are unit-tested
+// on the CPU (tests/c/plan_test.cpp, tests/c/walk_main.cpp, tests/c/plan_v2_main.cpp, tests/c/plan_v2_blocks_main.cpp,
+// tests/c/plan_codec_main.cpp, tests/c/plan_list_main.cpp, tests/c/plan_hybrid_main.cpp; tests/test_plan.py,
+// test_plan_v2.py, test_plan_v2_blocks.py, test_plan_codec.py, test_plan_list.py, test_plan_hybrid.py).
 #pragma once
 #include <stdint.h>
 
@@ -233,6 +234,59 @@ inline void v2_block_scatter(uint64_t n, uint64_t W, const std::vector<V2BlockIt
     for (uint64_t t = 0; t < items.size(); t++)
         if ((ballots[t >> 6] >> (t & 63)) & 1)
             ok_bits[items[t].entry * pitch + (items[t].leaf >> 3)] |= (uint8_t)(0x80u >> (items[t].leaf & 7));
+}
+
+// ---- digest words -------------------------------------------------------------------------------------------------------
+//
+// The library keeps every digest (SHA-1: 5 words, SHA-256: 8) as big-endian 32-bit VALUES, struct of arrays: word k
+// of the digest in column `col` of a table of row length `pitch` is tab[k * pitch + col].  A table inside a larger
+// one (the expected rows of a piece table, a stream window's rows) is passed as the pointer to its first word.
+inline void digest_pack(const uint8_t* d, uint32_t words, uint32_t* tab, uint64_t pitch, uint64_t col) {
+    for (uint32_t k = 0; k < words; k++, d += 4)
+        tab[k * pitch + col] = ((uint32_t)d[0] << 24) | ((uint32_t)d[1] << 16) | ((uint32_t)d[2] << 8) | (uint32_t)d[3];
+}
+
+inline void digest_unpack(const uint32_t* tab, uint64_t pitch, uint64_t col, uint32_t words, uint8_t* d) {
+    for (uint32_t k = 0; k < words; k++, d += 4) {
+        const uint32_t v = tab[k * pitch + col];
+        d[0] = (uint8_t)(v >> 24); d[1] = (uint8_t)(v >> 16); d[2] = (uint8_t)(v >> 8); d[3] = (uint8_t)v;
+    }
+}
+
+// ---- the launch order of a v1 list (tv_verify.hip: tv_verify_list) ------------------------------------------------------
+//
+// pieces: the n listed shard-relative pieces in the caller's order.  held (optional): held[k] != 0 = entry k holds a
+// slot of a slot pool (NULL: every entry); the others were never staged and are not launched.  short_last: the
+// shard-relative index of the torrent's SHORT last piece (piece.ts:16-19), UINT64_MAX when the shard has none.  Listed
+// together with full pieces it goes into waves of its own: launch = [the other entries..., copies of launch[0] up to a
+// multiple of 64, the last-piece entries...], so no wave mixes the short piece's padding blocks with the others' raw
+// blocks (the slow path); a list of last-piece entries only, or of none, is launched in the caller's order, unpadded.
+// origin[t] = the entry launch position t answers (-1: padding).
+inline void list_plan(uint64_t n, const uint32_t* pieces, const uint8_t* held, uint64_t short_last,
+                      std::vector<uint32_t>* launch, std::vector<int64_t>* origin) {
+    launch->clear();
+    origin->clear();
+    uint64_t launched = 0, nlast = 0;
+    for (uint64_t k = 0; k < n; k++)
+        if (!held || held[k]) {
+            launched++;
+            nlast += pieces[k] == short_last;
+        }
+    const bool separate = nlast && nlast < launched;
+    launch->reserve(launched + 64);
+    origin->reserve(launched + 64);
+    for (int part = 0; part < (separate ? 2 : 1); part++) {
+        for (uint64_t k = 0; k < n; k++)
+            if ((!held || held[k]) && (!separate || (pieces[k] == short_last) == (part == 1))) {
+                launch->push_back(pieces[k]);
+                origin->push_back((int64_t)k);
+            }
+        if (separate && part == 0)
+            while (launch->size() % 64) {
+                launch->push_back((*launch)[0]);
+                origin->push_back(-1);
+            }
+    }
 }
 
 // ---- the tail table of a hybrid call (tv_hybrid.hip: tv_hybrid_verify, tv_hybrid_hash) --------------------------------

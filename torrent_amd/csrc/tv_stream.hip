@@ -87,16 +87,42 @@ void budget_geometry(const tv_ctx* c, uint64_t budget, uint64_t min_win, uint64_
     stream_geometry(c->L, c->count, budget, min_win, kRingSlotBytes, kSlack, col, win);
 }
 
-int stream_begin_locked(tv_ctx* c, const uint8_t* avail_bits, uint64_t col_override = 0, uint64_t win_override = 0,
-                        uint64_t req_bytes = 0) {
+// What both begin calls start with: a fresh state holding the availability bits.  false = the shard is empty and the
+// stream is active already: there is nothing to hash, the first tv_stream_next reports completion.
+static bool begin_state(tv_ctx* c, const uint8_t* avail_bits) {
     StreamState& st = c->st;
     st = StreamState{};
     st.av.assign((c->count + 7) / 8, 0xFF);
     if (avail_bits) memcpy(st.av.data(), avail_bits, st.av.size());
-    if (c->count == 0) {  // nothing to hash: the first tv_stream_next reports completion
-        st.active = true;
-        return TV_OK;
+    st.active = c->count == 0;
+    return !st.active;
+}
+
+// The two chunk buffers of `need` bytes each; both go before either is replaced.
+static int grow_chunks(tv_ctx* c, uint64_t need) {
+    if (buf_fits(c->d_chunk[0], need, true) && buf_fits(c->d_chunk[1], need, true)) return TV_OK;
+    for (DevBuf& b : c->d_chunk) free_buf(b);
+    for (DevBuf& b : c->d_chunk) {
+        const int rc = grow_buf(c, b, need, true, need);
+        if (rc) return rc;
     }
+    return TV_OK;
+}
+
+// ... and end with: the call's first event, the bitfield words cleared, both chunk buffers free to be written.
+static int begin_done(tv_ctx* c) {
+    TV_HIP(c, hipEventRecord(c->ev_call0, c->stream));
+    TV_HIP(c, hipMemsetAsync(c->d_out, 0, c->bit_words * 8, c->stream));  // fail closed, as tv_verify
+    TV_HIP(c, hipEventRecord(c->done_ev[0], c->stream));
+    TV_HIP(c, hipEventRecord(c->done_ev[1], c->stream));
+    c->st.active = true;
+    return TV_OK;
+}
+
+int stream_begin_locked(tv_ctx* c, const uint8_t* avail_bits, uint64_t col_override = 0, uint64_t win_override = 0,
+                        uint64_t req_bytes = 0) {
+    StreamState& st = c->st;
+    if (!begin_state(c, avail_bits)) return TV_OK;
     if (stream_rows(c)) {  // whole pieces per row, windows of wn pieces
         st.C = (c->L + 63) / 64 * 64;
         st.wn = stream_row_window(c);
@@ -105,25 +131,13 @@ int stream_begin_locked(tv_ctx* c, const uint8_t* avail_bits, uint64_t col_overr
         st.wn = win_override ? std::min(win_override, c->count) : c->count;
     }
     st.row_pitch = st.C + 256;  // (tail over-read slack per row)
-    const uint64_t need = st.row_pitch * st.wn + kSlack;
-    if (!reuse_fits(need, c->chunk_bytes)) {
-        free_chunks(c);
-        for (auto& p : c->d_chunk) {
-            TV_HIP(c, hipMalloc((void**)&p, need));
-            c->n_device_allocs++;
-        }
-        c->chunk_bytes = need;
-    }
+    const int rc = grow_chunks(c, st.row_pitch * st.wn + kSlack);
+    if (rc) return rc;
     st.ncol = (c->L + st.C - 1) / st.C;
     st.nwin = (c->count + st.wn - 1) / st.wn;
     st.nunits = st.nwin * st.ncol;
     st.rows_per_req = std::max<uint64_t>(1, (req_bytes ? std::min<uint64_t>(req_bytes, kRingSlotBytes) : kRingSlotBytes) / st.C);
-    TV_HIP(c, hipEventRecord(c->ev_call0, c->stream));
-    TV_HIP(c, hipMemsetAsync(c->d_out, 0, c->bit_words * 8, c->stream));  // fail closed, as tv_verify
-    TV_HIP(c, hipEventRecord(c->done_ev[0], c->stream));
-    TV_HIP(c, hipEventRecord(c->done_ev[1], c->stream));
-    st.active = true;
-    return TV_OK;
+    return begin_done(c);
 }
 
 // A BitTorrent v2 stream (tv_v2_stream_begin): the same ring, requests and chunk buffers, the units hashed as merkle
@@ -135,15 +149,10 @@ int stream_begin_locked(tv_ctx* c, const uint8_t* avail_bits, uint64_t col_overr
 int v2_stream_begin_locked(tv_ctx* c, const uint32_t* piece_bytes, const uint32_t* tree_leaves, const uint8_t* hashes,
                            const uint8_t* avail_bits, uint64_t req_bytes = 0) {
     StreamState& st = c->st;
-    st = StreamState{};
+    const bool hashes_any = begin_state(c, avail_bits);
     st.v2 = true;
     st.kernel = TV_KERNEL_V2_STREAM;
-    st.av.assign((c->count + 7) / 8, 0xFF);
-    if (avail_bits) memcpy(st.av.data(), avail_bits, st.av.size());
-    if (c->count == 0) {  // nothing to hash: the first tv_stream_next reports completion
-        st.active = true;
-        return TV_OK;
-    }
+    if (!hashes_any) return TV_OK;
     uint64_t C = 0, wn = 0;
     v2_stream_geometry(c->L, c->count, c->budget_opt ? c->budget_opt : (1ull << 30), c->stream_chunk, kSlack, &C, &wn);
     st.C = C;
@@ -156,33 +165,12 @@ int v2_stream_begin_locked(tv_ctx* c, const uint32_t* piece_bytes, const uint32_
     while ((1ull << st.v2_logn) < st.ncol) st.v2_logn++;
     st.rows_per_req = std::max<uint64_t>(1, (req_bytes ? std::min<uint64_t>(req_bytes, kRingSlotBytes) : kRingSlotBytes) / C);
     TV_HIP(c, hipStreamSynchronize(c->stream));   // (nothing queued still reads the buffers replaced below)
-    const uint64_t need = st.row_pitch * wn + kSlack;
-    if (!reuse_fits(need, c->chunk_bytes)) {
-        free_chunks(c);
-        for (auto& p : c->d_chunk) {
-            TV_HIP(c, hipMalloc((void**)&p, need));
-            c->n_device_allocs++;
-        }
-        c->chunk_bytes = need;
-    }
     // (whole-piece columns run no level: the finish launch reads the column nodes themselves, level buffer A alone)
     const uint64_t need_tab = 11 * c->count, need_nodes = st.ncol > 1 ? v2_node_words(wn, st.ncol) : 8 * wn;
-    if (!c->d_v2s_tab || !reuse_fits(need_tab, c->cap_v2s_tab)) {
-        (void)hipFree(c->d_v2s_tab);
-        c->d_v2s_tab = nullptr;
-        c->cap_v2s_tab = 0;
-        TV_HIP(c, hipMalloc((void**)&c->d_v2s_tab, need_tab * sizeof(uint32_t)));
-        c->cap_v2s_tab = need_tab;
-        c->n_device_allocs++;
-    }
-    if (!c->d_v2s_nodes || !reuse_fits(need_nodes, c->cap_v2s_nodes)) {
-        (void)hipFree(c->d_v2s_nodes);
-        c->d_v2s_nodes = nullptr;
-        c->cap_v2s_nodes = 0;
-        TV_HIP(c, hipMalloc((void**)&c->d_v2s_nodes, need_nodes * sizeof(uint32_t)));
-        c->cap_v2s_nodes = need_nodes;
-        c->n_device_allocs++;
-    }
+    int rc = grow_chunks(c, st.row_pitch * wn + kSlack);
+    if (!rc) rc = grow_buf(c, c->d_v2s_tab, need_tab, true, need_tab);
+    if (!rc) rc = grow_buf(c, c->d_v2s_nodes, need_nodes, true, need_nodes);
+    if (rc) return rc;
     // the shard's rows: bytes, leaves, the width of each piece's top tree over its column nodes, and the expected root
     // words (big-endian values), SoA [8][pieces of the window] window after window: a window's launches see a table
     // of their own at piece j0 (expected words at 8 * j0)
@@ -193,20 +181,11 @@ int v2_stream_begin_locked(tv_ctx* c, const uint32_t* piece_bytes, const uint32_
         st.v2_bytes[j] = tab[j] = piece_bytes[i];
         tab[c->count + j] = tree_leaves[i];
         tab[2 * c->count + j] = std::max<uint32_t>(1, tree_leaves[i] >> st.v2_logc);
-        const uint8_t* d = hashes + 32 * i;
-        for (int k = 0; k < 8; k++)
-            tab[3 * c->count + 8 * j0 + (uint64_t)k * wcount + (j - j0)] =
-                ((uint32_t)d[4 * k] << 24) | ((uint32_t)d[4 * k + 1] << 16) | ((uint32_t)d[4 * k + 2] << 8) |
-                (uint32_t)d[4 * k + 3];
+        digest_pack(hashes + 32 * i, 8, tab.data() + 3 * c->count + 8 * j0, wcount, j - j0);
     }
-    TV_HIP(c, hipMemcpyAsync(c->d_v2s_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    TV_HIP(c, hipMemcpyAsync(c->d_v2s_tab.ptr, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
     TV_HIP(c, hipStreamSynchronize(c->stream));   // (tab is the call's own)
-    TV_HIP(c, hipEventRecord(c->ev_call0, c->stream));
-    TV_HIP(c, hipMemsetAsync(c->d_out, 0, c->bit_words * 8, c->stream));  // fail closed, as tv_verify
-    TV_HIP(c, hipEventRecord(c->done_ev[0], c->stream));
-    TV_HIP(c, hipEventRecord(c->done_ev[1], c->stream));
-    st.active = true;
-    return TV_OK;
+    return begin_done(c);
 }
 
 // A completed unit of a v2 stream: the column kernel on the chunk buffer, and after a window's last column its top
@@ -215,9 +194,9 @@ int v2_stream_begin_locked(tv_ctx* c, const uint32_t* piece_bytes, const uint32_
 int v2_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount) {
     StreamState& st = c->st;
     const uint64_t col = st.unit % st.ncol;
-    uint32_t* tab = c->d_v2s_tab;
+    uint32_t* tab = c->d_v2s_tab.get<uint32_t>();
     TvV2Col k{};
-    k.data = c->d_chunk[buf];
+    k.data = c->d_chunk[buf].get<uint8_t>();
     k.stride = st.row_pitch;
     k.n = (uint32_t)wcount;
     k.logc = st.v2_logc;
@@ -225,7 +204,7 @@ int v2_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount) {
     k.col = (uint32_t)col;
     k.piece_bytes = tab + j0;
     k.tree_leaves = tab + c->count + j0;
-    k.nodes = c->d_v2s_nodes;
+    k.nodes = c->d_v2s_nodes.get<uint32_t>();
     k.clock = c->clock_probe ? c->d_clock : nullptr;
     TV_HIP(c, tv_v2_launch_column(k, c->stream, &c->last_workgroups));
     st.launches++;
@@ -236,8 +215,8 @@ int v2_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount) {
     p.logW = st.v2_logn;
     p.piece_bytes = tab + j0;
     p.tree_leaves = tab + 2 * c->count + j0;
-    p.nodes_a = c->d_v2s_nodes;
-    p.nodes_b = c->d_v2s_nodes + 8 * wcount * st.ncol;
+    p.nodes_a = k.nodes;
+    p.nodes_b = k.nodes + 8 * wcount * st.ncol;
     p.expect = tab + 3 * c->count + 8 * j0;
     p.out64 = c->d_out + j0 / 64;   // (availability: st.av, applied at the end with the unreadable pieces)
     p.out_words = (uint32_t)((wcount + 63) / 64);
@@ -287,7 +266,7 @@ int stream_commit_locked(tv_ctx* c, const tv_stream_req* req, const uint8_t* src
     const tv_stream_req r = st.req;
     const int buf = (int)(st.unit & 1);
     const uint64_t j0 = st.unit / st.ncol * st.wn, wcount = std::min(st.wn, c->count - j0);
-    uint8_t* dst = c->d_chunk[buf] + st.row * st.row_pitch;
+    uint8_t* dst = c->d_chunk[buf].get<uint8_t>() + st.row * st.row_pitch;
     uint8_t* slot = c->ring[st.slot];
     const uint64_t n = std::min(rows_copy, r.rows);
     if (st.v2) {
@@ -376,7 +355,7 @@ int stream_commit_locked(tv_ctx* c, const tv_stream_req* req, const uint8_t* src
     const bool last = st.unit % st.ncol + 1 == st.ncol;
     // the window's pieces (the shard's digest / state rows from j0; bitfield words from j0 / 64: a window of a
     // multi-window stream is a multiple of 64 pieces)
-    TvPieces p = window_launch(c, j0, wcount, c->d_chunk[buf]);
+    TvPieces p = window_launch(c, j0, wcount, c->d_chunk[buf].get<uint8_t>());
     p.stride = st.row_pitch;
     p.avail64 = c->d_base_avail + j0 / 64;
     p.out64 = c->d_out + j0 / 64;

@@ -11,36 +11,6 @@ using namespace tvi;
 
 namespace tvi {
 
-static void free_v2_table(tv_ctx* c) {
-    (void)hipFree(c->d_v2_tab); c->d_v2_tab = nullptr;
-    (void)hipFree(c->d_v2_nodes); c->d_v2_nodes = nullptr;
-    c->cap_v2_count = c->cap_v2_nodes = 0;
-    c->v2_set = c->v2_hashes = false;
-}
-
-static void free_v2_list(tv_ctx* c) {
-    (void)hipFree(c->d_v2_list); c->d_v2_list = nullptr;
-    c->v2_list_cap = 0;
-}
-
-static void free_v2_blocks(tv_ctx* c) {
-    (void)hipFree(c->d_v2_blk); c->d_v2_blk = nullptr;
-    c->v2_blk_cap = 0;
-}
-
-static void free_v2_stream(tv_ctx* c) {
-    (void)hipFree(c->d_v2s_tab); c->d_v2s_tab = nullptr;
-    (void)hipFree(c->d_v2s_nodes); c->d_v2s_nodes = nullptr;
-    c->cap_v2s_tab = c->cap_v2s_nodes = 0;
-}
-
-void free_v2(tv_ctx* c) {
-    free_v2_table(c);
-    free_v2_list(c);
-    free_v2_blocks(c);
-    free_v2_stream(c);
-}
-
 static bool v2_piece_length_ok(uint64_t L) { return L >= TV_V2_LEAF_BYTES && (L & (L - 1)) == 0; }
 
 // Words of the two level buffers for `count` pieces of W leaves: A [8][count x W], B [8][count x max(W/2, 1)].
@@ -48,20 +18,34 @@ uint64_t v2_node_words(uint64_t count, uint64_t W) { return 8 * count * (W + (W 
 
 void v2_on_layout(tv_ctx* c) {
     c->v2_set = c->v2_hashes = false;
-    if (c->v2_list_cap > std::max<uint64_t>(1024, 2 * c->count)) free_v2_list(c);   // (as tv_verify_list's buffers)
+    if (c->d_v2_list.cap > std::max<uint64_t>(1024, 2 * c->count)) free_buf(c->d_v2_list);   // (as tv_verify_list's buffers)
     // the block calls' items: kept while the new shard could list that many blocks (the same rule, in blocks)
-    if (c->v2_blk_cap > std::max<uint64_t>(1024, 2 * c->count * std::max<uint64_t>(1, c->L / TV_V2_LEAF_BYTES)))
-        free_v2_blocks(c);
+    if (c->d_v2_blk.cap > std::max<uint64_t>(1024, 2 * c->count * std::max<uint64_t>(1, c->L / TV_V2_LEAF_BYTES)))
+        free_buf(c->d_v2_blk);
     // a v2 stream's table and nodes: kept for a layout a v2 stream could run on and whose table they fit
-    if ((c->d_v2s_tab || c->d_v2s_nodes) &&
-        !(v2_piece_length_ok(c->L) && c->count && reuse_fits(11 * c->count, c->cap_v2s_tab)))
-        free_v2_stream(c);
-    if (!c->d_v2_tab && !c->d_v2_nodes) return;
+    if (!(v2_piece_length_ok(c->L) && c->count && reuse_fits(11 * c->count, c->d_v2s_tab.cap))) {
+        free_buf(c->d_v2s_tab);
+        free_buf(c->d_v2s_nodes);
+    }
     // keep what a v2 table of the new geometry would reuse; anything else goes (a v1 layout holds no v2 memory)
     const bool v2 = v2_piece_length_ok(c->L) && c->count && !c->win && !c->slots;
-    if (!v2 || !reuse_fits(c->count, c->cap_v2_count) ||
-        !reuse_fits(v2_node_words(c->count, c->L / TV_V2_LEAF_BYTES), c->cap_v2_nodes))
-        free_v2_table(c);
+    if (!v2 || !reuse_fits(c->count, c->d_v2_tab.cap) ||
+        !reuse_fits(v2_node_words(c->count, c->L / TV_V2_LEAF_BYTES), c->d_v2_nodes.cap)) {
+        free_buf(c->d_v2_tab);
+        free_buf(c->d_v2_nodes);
+    }
+}
+
+int v2_check_entry(tv_ctx* c, uint64_t k, uint64_t b, uint64_t w) {
+    const uint64_t W = c->L / TV_V2_LEAF_BYTES;
+    if (b == 0 || b > c->L)
+        return fail(c, TV_ERR_ARG, "piece_bytes[%llu] = %llu is outside 1 .. %llu", (unsigned long long)k,
+                    (unsigned long long)b, (unsigned long long)c->L);
+    if (w == 0 || (w & (w - 1)) || w < (b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES || w > W)
+        return fail(c, TV_ERR_ARG, "tree_leaves[%llu] = %llu is not a power of two in %llu .. %llu",
+                    (unsigned long long)k, (unsigned long long)w,
+                    (unsigned long long)((b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES), (unsigned long long)W);
+    return TV_OK;
 }
 
 int v2_check_table(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const uint32_t* tree_leaves) {
@@ -72,23 +56,12 @@ int v2_check_table(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const uin
         return fail(c, TV_ERR_ARG, "the piece table has %llu entries, the layout %llu pieces", (unsigned long long)n,
                     (unsigned long long)c->P);
     if (n && (!piece_bytes || !tree_leaves)) return fail(c, TV_ERR_ARG, "NULL argument");
-    const uint64_t W = c->L / TV_V2_LEAF_BYTES;
     for (uint64_t p = 0; p < n; p++) {
-        const uint64_t b = piece_bytes[p], w = tree_leaves[p];
-        if (b == 0 || b > c->L)
-            return fail(c, TV_ERR_ARG, "piece_bytes[%llu] = %llu is outside 1 .. %llu", (unsigned long long)p,
-                        (unsigned long long)b, (unsigned long long)c->L);
-        if (w == 0 || (w & (w - 1)) || w < (b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES || w > W)
-            return fail(c, TV_ERR_ARG, "tree_leaves[%llu] = %llu is not a power of two in %llu .. %llu",
-                        (unsigned long long)p, (unsigned long long)w,
-                        (unsigned long long)((b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES), (unsigned long long)W);
+        const int rc = v2_check_entry(c, p, piece_bytes[p], tree_leaves[p]);
+        if (rc) return rc;
     }
     return TV_OK;
 }
-
-}  // namespace tvi
-
-namespace tvi {
 
 // The calls' common state checks (in the order the header lists them).
 int v2_require(tv_ctx* c, const char* what) {
@@ -101,16 +74,6 @@ int v2_require(tv_ctx* c, const char* what) {
     return TV_OK;
 }
 
-bool v2_avail_bits(const tv_ctx* c, const uint8_t* avail_bits, uint8_t* dst) {
-    if (!avail_bits && !c->any_file_bad) return false;
-    const size_t nbytes = c->bit_words * 8, used = (c->count + 7) / 8;
-    for (size_t k = 0; k < nbytes; k++) {
-        const uint8_t caller = k < used ? (avail_bits ? avail_bits[k] : 0xFF) : 0;
-        dst[k] = k < used ? (uint8_t)(caller & ~c->file_bad[k]) : 0;
-    }
-    return true;
-}
-
 TvV2 v2_launch_args(tv_ctx* c) {
     TvV2 p{};
     const uint64_t W = 1ull << c->v2_logW;
@@ -121,14 +84,14 @@ TvV2 v2_launch_args(tv_ctx* c) {
     // piece-major needs a full wave of pieces; below that (and by default) leaf-linear
     const int want = c->v2_map_opt ? c->v2_map_opt : TV_V2_MAP_LEAF;
     p.map = (want == TV_V2_MAP_PIECE && c->count >= 64) ? TV_V2_MAP_PIECE : TV_V2_MAP_LEAF;
-    uint32_t* tab = c->d_v2_tab;
-    const uint64_t cap = c->cap_v2_count;
+    uint32_t* tab = c->d_v2_tab.get<uint32_t>();
+    const uint64_t cap = c->d_v2_tab.cap;
     p.piece_bytes = tab;
     p.tree_leaves = tab + cap;
     p.expect = tab + 2 * cap;     // [8][count] packed at the row length `count` (<= cap)
     p.roots = tab + 10 * cap;
-    p.nodes_a = c->d_v2_nodes;
-    p.nodes_b = c->d_v2_nodes + 8 * c->count * W;
+    p.nodes_a = c->d_v2_nodes.get<uint32_t>();
+    p.nodes_b = p.nodes_a + 8 * c->count * W;
     p.out64 = c->d_out;
     p.clock = c->clock_probe ? c->d_clock : nullptr;
     return p;
@@ -147,18 +110,6 @@ int v2_launch(tv_ctx* c, TvV2& p, bool hash) {
 
 namespace {
 
-// Availability of one v2 launch: the caller's bits less the pieces file staging could not read; null = all.
-int v2_avail(tv_ctx* c, const uint8_t* avail_bits, const uint64_t** out) {
-    *out = nullptr;
-    if (!avail_bits && !c->any_file_bad) return TV_OK;
-    TV_HIP(c, hipEventSynchronize(c->ev_avail));  // the previous copy out of h_avail is done
-    v2_avail_bits(c, avail_bits, c->h_avail);
-    TV_HIP(c, hipMemcpyAsync(c->d_avail, c->h_avail, c->bit_words * 8, hipMemcpyHostToDevice, c->stream));
-    TV_HIP(c, hipEventRecord(c->ev_avail, c->stream));
-    *out = c->d_avail;
-    return TV_OK;
-}
-
 // the launch set of tv_v2_verify / tv_v2_hash on the compute stream; ev_k0 .. ev_k1 bracket it
 int v2_run(tv_ctx* c, TvV2& p, bool hash) {
     TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
@@ -174,37 +125,12 @@ int v2_run(tv_ctx* c, TvV2& p, bool hash) {
 // pieces of this shard with tv_v2_set_pieces' ranges and texts.
 int v2_check_entries(tv_ctx* c, uint64_t n, const uint64_t* pieces, const uint32_t* piece_bytes,
                      const uint32_t* tree_leaves) {
-    const uint64_t W = c->L / TV_V2_LEAF_BYTES;
     for (uint64_t k = 0; k < n; k++) {
-        if (pieces[k] < c->first || pieces[k] >= c->first + c->count)
-            return fail(c, TV_ERR_ARG, "piece %llu is not in this context's shard [%llu, %llu)",
-                        (unsigned long long)pieces[k], (unsigned long long)c->first,
-                        (unsigned long long)(c->first + c->count));
-        const uint64_t b = piece_bytes[k], w = tree_leaves[k];
-        if (b == 0 || b > c->L)
-            return fail(c, TV_ERR_ARG, "piece_bytes[%llu] = %llu is outside 1 .. %llu", (unsigned long long)k,
-                        (unsigned long long)b, (unsigned long long)c->L);
-        if (w == 0 || (w & (w - 1)) || w < (b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES || w > W)
-            return fail(c, TV_ERR_ARG, "tree_leaves[%llu] = %llu is not a power of two in %llu .. %llu",
-                        (unsigned long long)k, (unsigned long long)w,
-                        (unsigned long long)((b + TV_V2_LEAF_BYTES - 1) / TV_V2_LEAF_BYTES), (unsigned long long)W);
+        int rc = list_in_shard(c, pieces[k]);
+        if (!rc) rc = v2_check_entry(c, k, piece_bytes[k], tree_leaves[k]);
+        if (rc) return rc;
     }
     return TV_OK;
-}
-
-// A slot pool: every listed piece's slot is free again.
-void v2_release_listed(tv_ctx* c, uint64_t n, const uint64_t* pieces) {
-    if (!c->slots) return;
-    for (uint64_t k = 0; k < n; k++) {
-        auto it = c->slot_of.find(pieces[k] - c->first);
-        if (it == c->slot_of.end()) continue;
-        c->slot_free.push_back(it->second);
-        c->slot_of.erase(it);
-    }
-}
-
-inline uint32_t be32(const uint8_t* d) {
-    return ((uint32_t)d[0] << 24) | ((uint32_t)d[1] << 16) | ((uint32_t)d[2] << 8) | (uint32_t)d[3];
 }
 
 // tv_v2_leaf_hashes (check = false: `out` = leaves_out) and tv_v2_check_blocks (check = true: `out` = ok_bits_out).
@@ -238,7 +164,7 @@ int v2_blocks_call(tv_ctx* c, const char* what, bool check, uint64_t n, const ui
     std::vector<uint8_t> skip(n, 0);
     for (uint64_t k = 0; k < n; k++) {
         const uint64_t j = pieces[k] - c->first;
-        const bool no_slot = c->slots && !c->slot_of.count(j);
+        const bool no_slot = !list_held(c, j);
         const bool unread = c->any_file_bad && get_bit(c->file_bad.data(), j);
         if (!no_slot && !unread) continue;
         if (!check)
@@ -255,28 +181,21 @@ int v2_blocks_call(tv_ctx* c, const char* what, bool check, uint64_t n, const ui
     std::vector<uint32_t> tab((check ? 11 : 3) * m);   // rows, leaves, lens, expected leaf words [8][m] (big-endian values)
     for (uint64_t t = 0; t < m; t++) {
         const uint64_t k = items[t].entry, j = pieces[k] - c->first;
-        tab[t] = c->slots ? c->slot_of.find(j)->second : (uint32_t)j;
+        tab[t] = list_row(c, j);
         tab[m + t] = items[t].leaf;
         tab[2 * m + t] = items[t].len;
-        if (!check) continue;
-        const uint8_t* d = leaf_hashes + (k * W + items[t].leaf) * 32;
-        for (int q = 0; q < 8; q++) tab[(3 + (uint64_t)q) * m + t] = be32(d + 4 * q);
+        if (check) digest_pack(leaf_hashes + (k * W + items[t].leaf) * 32, 8, tab.data() + 3 * m, m, t);
     }
     std::vector<uint64_t> ballots(check ? words : 0);
     std::vector<uint32_t> soa(check ? 0 : 8 * m);
     TV_HIP(c, hipSetDevice(c->device));
     if (m) {
         DrainGuard drain(c);  // after the host vectors: their H2D / D2H copies end before they go
-        if (c->v2_blk_cap < m) {
-            free_v2_blocks(c);
-            const uint64_t cap = std::max<uint64_t>(m, 1024);
-            // a check's ballot words (one bit per item), then 11 table words per item: within 48 bytes per item
-            TV_HIP(c, hipMalloc((void**)&c->d_v2_blk, cap * 48));
-            c->v2_blk_cap = cap;
-            c->n_device_allocs++;
-        }
-        uint64_t* d_out = reinterpret_cast<uint64_t*>(c->d_v2_blk);
-        uint32_t* d = c->d_v2_blk + 2 * words;
+        // a check's ballot words (one bit per item), then 11 table words per item: within 48 bytes per item
+        rc = grow_buf(c, c->d_v2_blk, m, false, std::max<uint64_t>(m, 1024));
+        if (rc) return rc;
+        uint64_t* d_out = c->d_v2_blk.get<uint64_t>();
+        uint32_t* d = c->d_v2_blk.get<uint32_t>() + 2 * words;
         TV_HIP(c, hipEventRecord(c->ev_call0, c->stream));
         TV_HIP(c, hipMemcpyAsync(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
         // fail closed: an item the launch does not write reads as a mismatch
@@ -305,23 +224,11 @@ int v2_blocks_call(tv_ctx* c, const char* what, bool check, uint64_t n, const ui
         v2_block_scatter(n, W, items, ballots.data(), out);
     } else {
         memset(out, 0, n * W * 32);   // positions past a piece's bytes: zero hashes, out to W
-        for (uint64_t t = 0; t < m; t++) {
-            uint8_t* o = out + ((uint64_t)items[t].entry * W + items[t].leaf) * 32;
-            for (int q = 0; q < 8; q++) {
-                const uint32_t v = soa[(uint64_t)q * m + t];
-                o[4 * q] = (uint8_t)(v >> 24); o[4 * q + 1] = (uint8_t)(v >> 16);
-                o[4 * q + 2] = (uint8_t)(v >> 8); o[4 * q + 3] = (uint8_t)v;
-            }
-        }
+        for (uint64_t t = 0; t < m; t++)
+            digest_unpack(soa.data(), m, t, 8, out + ((uint64_t)items[t].entry * W + items[t].leaf) * 32);
     }
-    if (release) v2_release_listed(c, n, pieces);
-    c->last_kernel = TV_KERNEL_V2_BLOCKS;
-    c->last_launches = m ? 1 : 0;
-    if (!m) {
-        c->kernel_ms = c->total_ms = 0.f;
-        return TV_OK;
-    }
-    return finish_timing(c);
+    if (release) list_release(c, n, pieces);
+    return list_finish(c, TV_KERNEL_V2_BLOCKS, m);
 }
 
 }  // namespace
@@ -352,24 +259,11 @@ int tv_v2_set_pieces(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const u
     TV_HIP(c, hipSetDevice(c->device));
     TV_HIP(c, hipStreamSynchronize(c->stream));   // (a v2 call of the last table may still read the buffers)
     const uint64_t need_nodes = v2_node_words(c->count, W);
-    if (!c->d_v2_tab || !reuse_fits(c->count, c->cap_v2_count)) {
-        (void)hipFree(c->d_v2_tab);
-        c->d_v2_tab = nullptr;
-        c->cap_v2_count = 0;
-        TV_HIP(c, hipMalloc((void**)&c->d_v2_tab, 18 * c->count * sizeof(uint32_t)));
-        c->cap_v2_count = c->count;
-        c->n_device_allocs++;
-    }
-    if (!c->d_v2_nodes || !reuse_fits(need_nodes, c->cap_v2_nodes)) {
-        (void)hipFree(c->d_v2_nodes);
-        c->d_v2_nodes = nullptr;
-        c->cap_v2_nodes = 0;
-        TV_HIP(c, hipMalloc((void**)&c->d_v2_nodes, need_nodes * sizeof(uint32_t)));
-        c->cap_v2_nodes = need_nodes;
-        c->n_device_allocs++;
-    }
+    rc = grow_buf(c, c->d_v2_tab, c->count, true, c->count);
+    if (!rc) rc = grow_buf(c, c->d_v2_nodes, need_nodes, true, need_nodes);
+    if (rc) return rc;
     // the shard's rows: bytes, leaves, expected root words (big-endian values, SoA)
-    const uint64_t cap = c->cap_v2_count;
+    const uint64_t cap = c->d_v2_tab.cap;
     std::vector<uint32_t> tab(10 * cap, 0);
     uint32_t maxw = 1;
     for (uint64_t j = 0; j < c->count; j++) {
@@ -377,14 +271,10 @@ int tv_v2_set_pieces(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const u
         tab[j] = piece_bytes[i];
         tab[cap + j] = tree_leaves[i];
         maxw = std::max(maxw, tree_leaves[i]);
-        if (!hashes) continue;
-        const uint8_t* d = hashes + 32 * i;
-        for (int k = 0; k < 8; k++)
-            tab[2 * cap + (uint64_t)k * c->count + j] = ((uint32_t)d[4 * k] << 24) | ((uint32_t)d[4 * k + 1] << 16) |
-                                                        ((uint32_t)d[4 * k + 2] << 8) | (uint32_t)d[4 * k + 3];
+        if (hashes) digest_pack(hashes + 32 * i, 8, tab.data() + 2 * cap, c->count, j);
     }
     while ((1u << c->v2_maxlog) < maxw) c->v2_maxlog++;
-    TV_HIP(c, hipMemcpyAsync(c->d_v2_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    TV_HIP(c, hipMemcpyAsync(c->d_v2_tab.ptr, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
     TV_HIP(c, hipStreamSynchronize(c->stream));
     c->v2_set = true;
     c->v2_hashes = hashes != nullptr;
@@ -403,7 +293,7 @@ int tv_v2_verify(tv_ctx* c, const uint8_t* avail_bits, uint8_t* bitfield_out) {
     TV_HIP(c, hipSetDevice(c->device));
     TV_HIP(c, hipEventRecord(c->ev_call0, c->stream));
     TvV2 p = v2_launch_args(c);
-    rc = v2_avail(c, avail_bits, &p.avail64);
+    rc = launch_avail(c, avail_bits, &p.avail64, false);
     if (rc) return rc;
     rc = v2_run(c, p, false);   // (the finish kernel writes every word of d_out)
     if (rc) return rc;
@@ -430,12 +320,7 @@ int tv_v2_hash(tv_ctx* c, uint8_t* roots_out) {
     TV_HIP(c, hipMemcpyAsync(soa.data(), p.roots, soa.size() * 4, hipMemcpyDeviceToHost, c->stream));
     TV_HIP(c, hipEventRecord(c->ev_call1, c->stream));
     TV_HIP(c, hipEventSynchronize(c->ev_call1));
-    for (uint64_t j = 0; j < c->count; j++)
-        for (int k = 0; k < 8; k++) {
-            const uint32_t v = soa[(uint64_t)k * c->count + j];
-            uint8_t* d = roots_out + 32 * j + 4 * k;
-            d[0] = (uint8_t)(v >> 24); d[1] = (uint8_t)(v >> 16); d[2] = (uint8_t)(v >> 8); d[3] = (uint8_t)v;
-        }
+    for (uint64_t j = 0; j < c->count; j++) digest_unpack(soa.data(), c->count, j, 8, roots_out + 32 * j);
     return finish_timing(c);
 }
 
@@ -466,35 +351,29 @@ int tv_v2_verify_list(tv_ctx* c, uint64_t n, const uint64_t* pieces, const uint3
     std::vector<uint64_t> origin;
     origin.reserve(n);
     for (uint64_t k = 0; k < n; k++) {
-        if (!c->slots || c->slot_of.count(pieces[k] - c->first)) origin.push_back(k);
+        if (list_held(c, pieces[k] - c->first)) origin.push_back(k);
         else ok_out[k] = 0;
     }
     const uint64_t m = origin.size();
     std::vector<uint32_t> tab(11 * m);   // rows, bytes, widths, expected root words [8][m] (big-endian values)
     for (uint64_t e = 0; e < m; e++) {
         const uint64_t k = origin[e], j = pieces[k] - c->first;
-        tab[e] = c->slots ? c->slot_of.find(j)->second : (uint32_t)j;
+        tab[e] = list_row(c, j);
         tab[m + e] = piece_bytes[k];
         tab[2 * m + e] = tree_leaves[k];
-        const uint8_t* d = hashes + 32 * k;
-        for (int q = 0; q < 8; q++)
-            tab[(3 + (uint64_t)q) * m + e] = ((uint32_t)d[4 * q] << 24) | ((uint32_t)d[4 * q + 1] << 16) |
-                                             ((uint32_t)d[4 * q + 2] << 8) | (uint32_t)d[4 * q + 3];
+        digest_pack(hashes + 32 * k, 8, tab.data() + 3 * m, m, e);
     }
     std::vector<uint8_t> ok_launch(m);
     TV_HIP(c, hipSetDevice(c->device));
     if (m) {
         DrainGuard drain(c);  // after the host vectors: their H2D / D2H copies end before they go
-        if (c->v2_list_cap < m) {
-            free_v2_list(c);
-            const uint64_t cap = std::max<uint64_t>(m, 1024);
-            TV_HIP(c, hipMalloc((void**)&c->d_v2_list, cap * 48));   // 11 table words and 4 out bytes per entry
-            c->v2_list_cap = cap;
-            c->n_device_allocs++;
-        }
-        uint8_t* d_ok = reinterpret_cast<uint8_t*>(c->d_v2_list + 11 * c->v2_list_cap);
+        // (11 table words and 4 out bytes per entry)
+        rc = grow_buf(c, c->d_v2_list, m, false, std::max<uint64_t>(m, 1024));
+        if (rc) return rc;
+        uint32_t* d = c->d_v2_list.get<uint32_t>();
+        uint8_t* d_ok = reinterpret_cast<uint8_t*>(d + 11 * c->d_v2_list.cap);
         TV_HIP(c, hipEventRecord(c->ev_call0, c->stream));
-        TV_HIP(c, hipMemcpyAsync(c->d_v2_list, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+        TV_HIP(c, hipMemcpyAsync(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
         // fail closed: an entry the launch does not write reads as 0
         TV_HIP(c, hipMemsetAsync(d_ok, 0, m, c->stream));
         TvV2List p{};
@@ -502,10 +381,10 @@ int tv_v2_verify_list(tv_ctx* c, uint64_t n, const uint64_t* pieces, const uint3
         p.stride = c->stride;
         p.m = (uint32_t)m;
         while ((1ull << p.logW) < W) p.logW++;
-        p.rows = c->d_v2_list;
-        p.bytes = c->d_v2_list + m;
-        p.widths = c->d_v2_list + 2 * m;
-        p.expect = c->d_v2_list + 3 * m;
+        p.rows = d;
+        p.bytes = d + m;
+        p.widths = d + 2 * m;
+        p.expect = d + 3 * m;
         p.out_bytes = d_ok;
         TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
         TV_HIP(c, tv_v2_launch_list(p, c->stream, &c->last_workgroups));
@@ -517,17 +396,9 @@ int tv_v2_verify_list(tv_ctx* c, uint64_t n, const uint64_t* pieces, const uint3
         c->last_workgroups = 0;
     }
     for (uint64_t e = 0; e < m; e++) ok_out[origin[e]] = ok_launch[e];
-    if (c->any_file_bad)  // pieces file staging could not read are 0 here too
-        for (uint64_t k = 0; k < n; k++)
-            if (get_bit(c->file_bad.data(), pieces[k] - c->first)) ok_out[k] = 0;
-    v2_release_listed(c, n, pieces);  // (a failed piece is staged anew when it is re-downloaded)
-    c->last_kernel = TV_KERNEL_V2_LIST;
-    c->last_launches = m ? 1 : 0;
-    if (!m) {
-        c->kernel_ms = c->total_ms = 0.f;
-        return TV_OK;
-    }
-    return finish_timing(c);
+    list_zero_unread(c, n, pieces, ok_out);
+    list_release(c, n, pieces);
+    return list_finish(c, TV_KERNEL_V2_LIST, m);
 }
 
 int tv_v2_leaf_hashes(tv_ctx* c, uint64_t n, const uint64_t* pieces, const uint32_t* piece_bytes,

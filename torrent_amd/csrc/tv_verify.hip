@@ -62,68 +62,44 @@ int tv_verify_list(tv_ctx* c, const uint64_t* pieces, uint64_t n, uint8_t* ok_ou
                                      "this layout is windowed (the shard exceeds the device budget)");
     std::vector<uint32_t> local(n);
     for (uint64_t k = 0; k < n; k++) {
-        if (pieces[k] < c->first || pieces[k] >= c->first + c->count)
-            return fail(c, TV_ERR_ARG, "piece %llu is not in this context's shard [%llu, %llu)",
-                        (unsigned long long)pieces[k], (unsigned long long)c->first,
-                        (unsigned long long)(c->first + c->count));
+        rc = list_in_shard(c, pieces[k]);
+        if (rc) return rc;
         local[k] = (uint32_t)(pieces[k] - c->first);
     }
     // The entries launched: every listed piece, or, in a slot pool, the listed pieces that hold a slot (the others
-    // were never staged: 0).  A short last piece (piece.ts:16-19) listed together with full pieces goes into waves
-    // of its own: the launch list is [full pieces..., padding to a multiple of 64, last-piece entries...], so no
-    // wave mixes the short piece's padding blocks with the others' raw blocks (the slow path).
-    std::vector<uint64_t> sel;
-    sel.reserve(n);
-    for (uint64_t k = 0; k < n; k++) {
-        if (!c->slots || c->slot_of.count(local[k])) sel.push_back(k);
-        else ok_out[k] = 0;
+    // were never staged: 0), in tv_plan.h list_plan's order (a short last piece in waves of its own).
+    std::vector<uint8_t> held(c->slots ? n : 0);
+    for (uint64_t k = 0; k < held.size(); k++) {
+        held[k] = list_held(c, local[k]);
+        if (!held[k]) ok_out[k] = 0;
     }
-    const uint64_t lastj = c->first + c->count - 1 == c->P - 1 ? c->count - 1 : UINT64_MAX;
-    uint64_t nlast = 0;
-    if (lastj != UINT64_MAX && piece_len(c, c->P - 1) != c->L)
-        for (uint64_t k : sel) nlast += local[k] == lastj;
+    const bool short_last = c->first + c->count == c->P && piece_len(c, c->P - 1) != c->L;
     std::vector<uint32_t> launch;  // shard-relative pieces in launch order (then, for a slot pool, their slots)
     std::vector<int64_t> origin;   // launch position -> index in `pieces` (-1 = padding)
-    launch.reserve(sel.size() + 64);
-    origin.reserve(sel.size() + 64);
-    const bool separate = nlast && nlast < sel.size();
-    for (int part = 0; part < (separate ? 2 : 1); part++) {
-        for (uint64_t k : sel)
-            if (!separate || (local[k] == lastj) == (part == 1)) {
-                launch.push_back(local[k]);
-                origin.push_back((int64_t)k);
-            }
-        if (separate && part == 0)
-            while (launch.size() % 64) {
-                launch.push_back(launch[0]);
-                origin.push_back(-1);
-            }
-    }
+    list_plan(n, local.data(), c->slots ? held.data() : nullptr, short_last ? c->count - 1 : UINT64_MAX, &launch,
+              &origin);
     const uint64_t m = launch.size();
     if (c->slots)  // the rows: each entry's slot (the kernels read piece launch[j]'s bytes from slot rows[j])
-        for (uint64_t j = 0; j < m; j++) launch.push_back(c->slot_of.find(launch[j])->second);
+        for (uint64_t j = 0; j < m; j++) launch.push_back(list_row(c, launch[j]));
     std::vector<uint8_t> ok_launch(m);
     TV_HIP(c, hipSetDevice(c->device));
     int kernel = 0;
     if (m) {
         DrainGuard drain(c);  // after the host vectors: their H2D / D2H copies end before they go
-        if (c->list_cap < m) {
-            free_list(c);
-            const uint64_t cap = std::max<uint64_t>(m, 1024);
-            TV_HIP(c, hipMalloc((void**)&c->d_list, 2 * cap * 4));  // indices, then (slot pool) rows
-            TV_HIP(c, hipMalloc((void**)&c->d_list_out, cap));
-            c->list_cap = cap;
-            c->n_device_allocs += 2;
-        }
+        rc = grow_buf(c, c->d_list, m, false, std::max<uint64_t>(m, 1024));
+        if (!rc) rc = grow_buf(c, c->d_list_out, m, false, std::max<uint64_t>(m, 1024));
+        if (rc) return rc;
+        uint32_t* d_list = c->d_list.get<uint32_t>();
+        uint8_t* d_ok = c->d_list_out.get<uint8_t>();
         TV_HIP(c, hipEventRecord(c->ev_call0, c->stream));
-        TV_HIP(c, hipMemcpyAsync(c->d_list, launch.data(), launch.size() * 4, hipMemcpyHostToDevice, c->stream));
+        TV_HIP(c, hipMemcpyAsync(d_list, launch.data(), launch.size() * 4, hipMemcpyHostToDevice, c->stream));
         TvPieces p = resident_launch(c);
         p.n = (uint32_t)m;
         p.n_main = (uint32_t)m;
-        p.idx = c->d_list;
-        p.rows = c->slots ? c->d_list + m : nullptr;
+        p.idx = d_list;
+        p.rows = c->slots ? d_list + m : nullptr;
         p.clock = nullptr;
-        p.out_bytes = c->d_list_out;
+        p.out_bytes = d_ok;
         TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
         // twin (two lanes per piece) while its 2-wave workgroups fit two per CU, then split (rounds + helper pair,
         // ~30 % shorter serial stream per block than lane) while one pair per CU suffices, like choose_kernel;
@@ -143,29 +119,15 @@ int tv_verify_list(tv_ctx* c, const uint64_t* pieces, uint64_t n, uint8_t* ok_ou
         }
         TV_HIP(c, tv_launch_verify_list(p, kernel, c->stream, &c->last_workgroups));
         TV_HIP(c, hipEventRecord(c->ev_k1, c->stream));
-        TV_HIP(c, hipMemcpyAsync(ok_launch.data(), c->d_list_out, m, hipMemcpyDeviceToHost, c->stream));
+        TV_HIP(c, hipMemcpyAsync(ok_launch.data(), d_ok, m, hipMemcpyDeviceToHost, c->stream));
         TV_HIP(c, hipEventRecord(c->ev_call1, c->stream));
         TV_HIP(c, hipEventSynchronize(c->ev_call1));
     }
     for (uint64_t i = 0; i < m; i++)
         if (origin[i] >= 0) ok_out[origin[i]] = ok_launch[i];
-    if (c->any_file_bad)  // pieces file staging could not read (recover_segment) are 0 here too
-        for (uint64_t k = 0; k < n; k++)
-            if (get_bit(c->file_bad.data(), local[k])) ok_out[k] = 0;
-    if (c->slots)  // a listed piece's slot is free again (a failed piece is staged anew when it is re-downloaded)
-        for (uint64_t k = 0; k < n; k++) {
-            auto it = c->slot_of.find(local[k]);
-            if (it == c->slot_of.end()) continue;
-            c->slot_free.push_back(it->second);
-            c->slot_of.erase(it);
-        }
-    c->last_kernel = kernel;
-    c->last_launches = m ? 1 : 0;
-    if (!m) {
-        c->kernel_ms = c->total_ms = 0.f;
-        return TV_OK;
-    }
-    return finish_timing(c);
+    list_zero_unread(c, n, pieces, ok_out);   // (recover_segment's marks)
+    list_release(c, n, pieces);
+    return list_finish(c, kernel, m);
 }
 
 int tv_hash(tv_ctx* c, uint8_t* digests_out) {
@@ -197,12 +159,7 @@ int tv_hash(tv_ctx* c, uint8_t* digests_out) {
     TV_HIP(c, hipMemcpyAsync(soa.data(), c->d_hash, soa.size() * 4, hipMemcpyDeviceToHost, c->stream));
     TV_HIP(c, hipEventRecord(c->ev_call1, c->stream));
     TV_HIP(c, hipEventSynchronize(c->ev_call1));
-    for (uint64_t j = 0; j < c->count; j++)
-        for (int k = 0; k < 5; k++) {
-            const uint32_t v = soa[(uint64_t)k * c->count + j];
-            uint8_t* d = digests_out + 20 * j + 4 * k;
-            d[0] = (uint8_t)(v >> 24); d[1] = (uint8_t)(v >> 16); d[2] = (uint8_t)(v >> 8); d[3] = (uint8_t)v;
-        }
+    for (uint64_t j = 0; j < c->count; j++) digest_unpack(soa.data(), c->count, j, 5, digests_out + 20 * j);
     c->last_kernel = kernel;
     c->last_launches = c->win ? (int)c->win_launched : 1;
     return finish_timing(c);
