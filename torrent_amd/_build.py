@@ -85,7 +85,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     deps = srcs + host_srcs + [header, os.path.join(CSRC, "tv_internal.h"), os.path.join(CSRC, "tv_host.h"),
                                os.path.join(CSRC, "tv_ctx.h"), os.path.join(CSRC, "tv_options_internal.h"), EXPORTS,
                                os.path.join(CSRC, "tv_plan.h"), os.path.join(CSRC, "tv_block.h"),
-                               os.path.join(CSRC, "tv_sha256.h"),
+                               os.path.join(CSRC, "tv_sha256.h"), os.path.join(CSRC, "tv_fileio.h"),
                                os.path.join(ROOT, "include", "torrent_verify.h")]
     if not (force or _newer(LIB, deps)):
         return LIB

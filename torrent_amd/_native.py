@@ -216,6 +216,48 @@ def _addr(buf, writable: bool = False) -> tuple:
     return ctypes.addressof(c), c
 
 
+def _path_blob(what: str, paths) -> bytes:
+    """Every path of a table, NUL-terminated, in one buffer (paths hold no NUL); b"\\0" for an empty table.  str paths
+    are encoded in one call (os.fsencode per path cost ~5 ms for 10,000 files)."""
+    if not len(paths):
+        return b"\0"
+    if all(type(x) is str for x in paths):
+        blob = ("\0".join(paths) + "\0").encode(sys.getfilesystemencoding(), "surrogateescape")
+    else:
+        blob = b"\0".join(os.fsencode(x) for x in paths) + b"\0"
+    if blob.count(b"\0") != len(paths):
+        raise ValueError(f"{what}: a path contains a NUL byte")
+    return blob
+
+
+def _v2_arrays(what: str, piece_bytes, tree_leaves, pieces=None) -> tuple:
+    """A v2 piece table's (or, with `pieces`, an entry list's) columns as the arrays the library reads, lengths checked:
+    (piece_bytes, tree_leaves) or (pieces, piece_bytes, tree_leaves)."""
+    import numpy as np
+    pb = np.ascontiguousarray(piece_bytes, dtype=np.uint32)
+    tl = np.ascontiguousarray(tree_leaves, dtype=np.uint32)
+    if pieces is None:
+        if len(pb) != len(tl):
+            raise ValueError(f"{what}: piece_bytes and tree_leaves differ in length")
+        return pb, tl
+    pc = np.ascontiguousarray(pieces, dtype=np.uint64)
+    if len(pb) != len(pc) or len(tl) != len(pc):
+        raise ValueError(f"{what}: pieces, piece_bytes and tree_leaves differ in length")
+    return pc, pb, tl
+
+
+def _v2_hashes(what: str, hashes, nbytes, n: int, per: str = "piece") -> tuple:
+    """(address, keepalive) of the n expected 32-byte roots, `nbytes` long as the caller measures them (None: there are
+    none); an empty table: any non-NULL pointer."""
+    if nbytes != 32 * n:
+        raise ValueError(f"{what}: hashes must hold 32 bytes per {per}")
+    a, keep = _addr(hashes)
+    if a is None:
+        keep = ctypes.create_string_buffer(1)
+        a = ctypes.addressof(keep)
+    return a, keep
+
+
 def device_count() -> int:
     n = _int(0)
     rc = lib().tv_device_count(ctypes.byref(n))
@@ -404,12 +446,7 @@ class Context:
             raise ValueError("stage_file_table: lengths and paths differ in length")
         if n == 0:
             return []
-        if all(type(x) is str for x in paths):
-            blob = ("\0".join(paths) + "\0").encode(sys.getfilesystemencoding(), "surrogateescape")
-        else:
-            blob = b"\0".join(os.fsencode(x) for x in paths) + b"\0"
-        if blob.count(b"\0") != n:
-            raise ValueError("stage_file_table: a path contains a NUL byte")
+        blob = _path_blob("stage_file_table", paths)
         ln = np.ascontiguousarray(lengths, dtype=np.uint64)
         st = np.zeros(n, dtype=np.int32)
         self._check(self._L.tv_stage_file_table(self._h, n, ln.ctypes.data, blob, len(blob), st.ctypes.data))
@@ -423,15 +460,10 @@ class Context:
         n = len(paths)
         if len(lengths) != n:
             raise ValueError("stream_file_table: lengths and paths differ in length")
-        if n and all(type(x) is str for x in paths):
-            blob = ("\0".join(paths) + "\0").encode(sys.getfilesystemencoding(), "surrogateescape")
-        else:
-            blob = b"\0".join(os.fsencode(x) for x in paths) + b"\0" if n else b"\0"
-        if n and blob.count(b"\0") != n:
-            raise ValueError("stream_file_table: a path contains a NUL byte")
+        blob = _path_blob("stream_file_table", paths)
         ln = np.ascontiguousarray(lengths if n else [0], dtype=np.uint64)
         st = np.zeros(max(1, n), dtype=np.int32)
-        out = ctypes.create_string_buffer(max(1, self._nbits()))
+        out = self._bits_out()
         a, keep = _addr(avail)
         self._check(self._L.tv_stream_file_table(self._h, n, ln.ctypes.data, blob, len(blob), a, out, st.ctypes.data))
         del keep
@@ -448,14 +480,8 @@ class Context:
             return []
         if any(len(v) != n for v in (file_offsets, linear_offsets, lens)):
             raise ValueError("stage_files: paths, file_offsets, linear_offsets and lens differ in length")
-        # all paths in one NUL-separated buffer (paths hold no NUL), and the char* array pointing into it;
-        # str paths are encoded in one call (os.fsencode per path cost ~5 ms for 10,000 files)
-        if all(type(x) is str for x in paths):
-            blob = ("\0".join(paths) + "\0").encode(sys.getfilesystemencoding(), "surrogateescape")
-        else:
-            blob = b"\0".join(os.fsencode(x) for x in paths) + b"\0"
-        if blob.count(b"\0") != n:
-            raise ValueError("stage_files: a path contains a NUL byte")
+        # all paths in one NUL-separated buffer, and the char* array pointing into it
+        blob = _path_blob("stage_files", paths)
         cblob = ctypes.create_string_buffer(blob, len(blob))
         nul = np.flatnonzero(np.frombuffer(blob, dtype=np.uint8) == 0)
         starts = np.empty(n, dtype=np.uint64)
@@ -483,15 +509,19 @@ class Context:
     def _nbits(self) -> int:
         return (self.shard_count + 7) // 8
 
+    def _bits_out(self):
+        """The output buffer of a shard bitfield (never empty: the library is given a non-NULL pointer)."""
+        return ctypes.create_string_buffer(max(1, self._nbits()))
+
     def verify(self, avail_bits=None) -> bytes:
-        out = ctypes.create_string_buffer(max(1, self._nbits()))
+        out = self._bits_out()
         a, keep = _addr(avail_bits)
         self._check(self._L.tv_verify(self._h, a, out))
         del keep
         return out.raw[: self._nbits()]
 
     def verify_host(self, src, avail_bits=None) -> bytes:
-        out = ctypes.create_string_buffer(max(1, self._nbits()))
+        out = self._bits_out()
         a, k1 = _addr(src)
         b, k2 = _addr(avail_bits)
         n = memoryview(src).nbytes if src is not None else 0
@@ -517,17 +547,8 @@ class Context:
         del keep
 
     def _v2_table(self, what: str, piece_bytes, tree_leaves, hashes):
-        import numpy as np
-        pb = np.ascontiguousarray(piece_bytes, dtype=np.uint32)
-        tl = np.ascontiguousarray(tree_leaves, dtype=np.uint32)
-        if len(pb) != len(tl):
-            raise ValueError(f"{what}: piece_bytes and tree_leaves differ in length")
-        if hashes is None or memoryview(hashes).nbytes != 32 * len(pb):
-            raise ValueError(f"{what}: hashes must hold 32 bytes per piece")
-        a, keep = _addr(hashes)
-        if a is None:   # (an empty table: any non-NULL pointer)
-            keep = ctypes.create_string_buffer(1)
-            a = ctypes.addressof(keep)
+        pb, tl = _v2_arrays(what, piece_bytes, tree_leaves)
+        a, keep = _v2_hashes(what, hashes, None if hashes is None else memoryview(hashes).nbytes, len(pb))
         return pb, tl, a, keep
 
     def v2_stream_begin(self, piece_bytes, tree_leaves, hashes, avail_bits=None) -> None:
@@ -550,15 +571,10 @@ class Context:
         n = len(paths)
         if len(lengths) != n:
             raise ValueError("v2_stream_file_table: lengths and paths differ in length")
-        if n and all(type(x) is str for x in paths):
-            blob = ("\0".join(paths) + "\0").encode(sys.getfilesystemencoding(), "surrogateescape")
-        else:
-            blob = b"\0".join(os.fsencode(x) for x in paths) + b"\0" if n else b"\0"
-        if n and blob.count(b"\0") != n:
-            raise ValueError("v2_stream_file_table: a path contains a NUL byte")
+        blob = _path_blob("v2_stream_file_table", paths)
         ln = np.ascontiguousarray(lengths if n else [0], dtype=np.uint64)
         st = np.zeros(max(1, n), dtype=np.int32)
-        out = ctypes.create_string_buffer(max(1, self._nbits()))
+        out = self._bits_out()
         a, keep2 = _addr(avail)
         self._check(self._L.tv_v2_stream_file_table(self._h, len(pb), pb.ctypes.data, tl.ctypes.data, h, n,
                                                     ln.ctypes.data, blob, len(blob), a, out, st.ctypes.data))
@@ -610,7 +626,7 @@ class Context:
         self._check(self._L.tv_stream_fill_synthetic(self._h, ctypes.byref(req), seed))
 
     def stream_end(self) -> bytes:
-        out = ctypes.create_string_buffer(max(1, self._nbits()))
+        out = self._bits_out()
         self._check(self._L.tv_stream_end(self._h, out))
         return out.raw[: self._nbits()]
 
@@ -626,23 +642,14 @@ class Context:
     def v2_set_pieces(self, piece_bytes, tree_leaves, hashes: Optional[bytes] = None) -> None:
         """tv_v2_set_pieces: the v2 piece table of the layout (GLOBAL entries, one per piece of the aligned space):
         valid bytes and merkle tree width of every piece, and the expected 32-byte roots (None: creation mode)."""
-        import numpy as np
-        pb = np.ascontiguousarray(piece_bytes, dtype=np.uint32)
-        tl = np.ascontiguousarray(tree_leaves, dtype=np.uint32)
-        if len(pb) != len(tl):
-            raise ValueError("v2_set_pieces: piece_bytes and tree_leaves differ in length")
-        if hashes is not None and len(hashes) != 32 * len(pb):
-            raise ValueError("v2_set_pieces: hashes must hold 32 bytes per piece")
-        a, keep = _addr(hashes)
-        if hashes is not None and a is None:   # (an empty table in verify mode: any non-NULL pointer)
-            keep = ctypes.create_string_buffer(1)
-            a = ctypes.addressof(keep)
+        pb, tl = _v2_arrays("v2_set_pieces", piece_bytes, tree_leaves)
+        a, keep = (None, None) if hashes is None else _v2_hashes("v2_set_pieces", hashes, len(hashes), len(pb))
         self._check(self._L.tv_v2_set_pieces(self._h, len(pb), pb.ctypes.data, tl.ctypes.data, a))
         del keep
 
     def v2_verify(self, avail_bits=None) -> bytes:
         """tv_v2_verify: the shard's have-bits (as verify), piece roots against the table's hashes."""
-        out = ctypes.create_string_buffer(max(1, self._nbits()))
+        out = self._bits_out()
         a, keep = _addr(avail_bits)
         self._check(self._L.tv_v2_verify(self._h, a, out))
         del keep
@@ -657,31 +664,19 @@ class Context:
     def v2_verify_list(self, pieces, piece_bytes, tree_leaves, hashes) -> bytes:
         """tv_v2_verify_list: one byte (0/1) per listed entry: GLOBAL piece pieces[k] with piece_bytes[k] valid
         bytes, a merkle tree of tree_leaves[k] leaves and the expected root hashes[32 k : 32 k + 32]."""
-        import numpy as np
-        pc = np.ascontiguousarray(pieces, dtype=np.uint64)
-        pb = np.ascontiguousarray(piece_bytes, dtype=np.uint32)
-        tl = np.ascontiguousarray(tree_leaves, dtype=np.uint32)
+        pc, pb, tl = _v2_arrays("v2_verify_list", piece_bytes, tree_leaves, pieces)
         n = len(pc)
-        if len(pb) != n or len(tl) != n:
-            raise ValueError("v2_verify_list: pieces, piece_bytes and tree_leaves differ in length")
-        if memoryview(hashes).nbytes != 32 * n:
-            raise ValueError("v2_verify_list: hashes must hold 32 bytes per entry")
+        a, keep = _v2_hashes("v2_verify_list", hashes, memoryview(hashes).nbytes, n, "entry")
         if n == 0:
             self._check(self._L.tv_v2_verify_list(self._h, 0, None, None, None, None, None))
             return b""
-        a, keep = _addr(hashes)
         out = ctypes.create_string_buffer(n)
         self._check(self._L.tv_v2_verify_list(self._h, n, pc.ctypes.data, pb.ctypes.data, tl.ctypes.data, a, out))
         del keep
         return out.raw[:n]
 
     def _v2_entries(self, what: str, pieces, piece_bytes, tree_leaves):
-        import numpy as np
-        pc = np.ascontiguousarray(pieces, dtype=np.uint64)
-        pb = np.ascontiguousarray(piece_bytes, dtype=np.uint32)
-        tl = np.ascontiguousarray(tree_leaves, dtype=np.uint32)
-        if len(pb) != len(pc) or len(tl) != len(pc):
-            raise ValueError(f"{what}: pieces, piece_bytes and tree_leaves differ in length")
+        pc, pb, tl = _v2_arrays(what, piece_bytes, tree_leaves, pieces)
         return pc, pb, tl, max(1, getattr(self, "piece_length", 0) // TV_V2_LEAF_BYTES)
 
     def v2_leaf_hashes(self, pieces, piece_bytes, tree_leaves, release: bool = False) -> bytes:
@@ -727,7 +722,7 @@ class Context:
         then SHA-1 against the digests (set_digests) and the merkle roots against the table's hashes (v2_set_pieces)
         over the same bytes; bitfield = v1 AND v2."""
         n = self._nbits()
-        out, v1, v2 = (ctypes.create_string_buffer(max(1, n)) for _ in range(3))
+        out, v1, v2 = (self._bits_out() for _ in range(3))
         a, keep = _addr(avail_bits)
         self._check(self._L.tv_hybrid_verify(self._h, a, v1, v2, out))
         del keep

@@ -961,9 +961,8 @@ bool is_pinned(const void* p) {
 
 // Clip the LINEAR range [off, off + len) to this ctx's shard: [*a, *b) (empty when *a >= *b).
 void clip_to_whole_shard(const tv_ctx* c, uint64_t off, uint64_t len, uint64_t* a, uint64_t* b) {
-    const uint64_t lo = c->first * c->L;
-    const uint64_t last = c->first + c->count - 1;
-    const uint64_t hi = last * c->L + piece_len(c, last);
+    uint64_t lo, hi;
+    shard_bytes(c, /*clamp_total=*/false, &lo, &hi);
     *a = std::max(off, lo);
     *b = std::min(off + len, hi);
 }
@@ -991,10 +990,7 @@ void clear_bad(tv_ctx* c, uint64_t a, uint64_t b) {
     if (b <= lo) return;
     uint64_t i = std::max(a, lo);
     i = (i + c->L - 1) / c->L;  // the first piece starting at or after a
-    for (; i < c->first + c->count && i * c->L + piece_len(c, i) <= b; i++) {
-        const uint64_t j = i - c->first;
-        c->file_bad[j >> 3] &= (uint8_t)~(0x80u >> (j & 7));
-    }
+    for (; i < c->first + c->count && i * c->L + piece_len(c, i) <= b; i++) clear_bit(c->file_bad.data(), i - c->first);
 }
 
 // Queue the copies of LINEAR bytes [a, b) (inside the shard) on the copy stream; byte `pos` is read

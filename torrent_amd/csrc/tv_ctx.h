@@ -395,7 +395,15 @@ extern thread_local std::string g_thread_error;
 
 uint64_t piece_len(const tv_ctx* c, uint64_t i);  // piece.ts:16-19
 inline void set_bit(uint8_t* bf, uint64_t i) { bf[i >> 3] |= (uint8_t)(0x80u >> (i & 7)); }
+inline void clear_bit(uint8_t* bf, uint64_t j) { bf[j >> 3] &= (uint8_t)~(0x80u >> (j & 7)); }
 inline bool get_bit(const uint8_t* bf, uint64_t i) { return (bf[i >> 3] >> (7 - (i & 7))) & 1; }
+// The shard's LINEAR bytes [*lo, *hi): from its first piece to the end of its last one; clamp_total: at most the
+// torrent's bytes (a layout may hold more pieces than data; mark_bad marks by piece and does not clamp).
+inline void shard_bytes(const tv_ctx* c, bool clamp_total, uint64_t* lo, uint64_t* hi) {
+    const uint64_t last = c->first + c->count - 1, end = last * c->L + piece_len(c, last);
+    *lo = c->first * c->L;
+    *hi = clamp_total ? std::min(c->total, end) : end;
+}
 // Clip the LINEAR range [off, off + len) to this ctx's shard / to the pieces the payload can take now.
 void clip_to_whole_shard(const tv_ctx* c, uint64_t off, uint64_t len, uint64_t* a, uint64_t* b);
 void clip_to_shard(const tv_ctx* c, uint64_t off, uint64_t len, uint64_t* a, uint64_t* b);
@@ -407,6 +415,19 @@ int access_ok(const char* path, bool rw);
 int open_file(const char* path, bool rw, int* err);
 double cached_fraction(int fd, uint64_t fo, uint64_t n);   // page-cache residency of file bytes, sampled (tv_files.hip)
 int fs_openable(const char* path, bool rw);
+inline int path_error(tv_ctx* c, uint64_t k, uint64_t paths_bytes, uint64_t n) {
+    return fail(c, TV_ERR_ARG, "paths holds %llu NUL-terminated paths in %llu bytes, the table %llu files",
+                (unsigned long long)k, (unsigned long long)paths_bytes, (unsigned long long)n);
+}
+// "cold": a sampled range (cached_fraction) that is mostly not in the page cache (-1, unknown, is not cold)
+inline bool is_cold(double cached) { return cached >= 0 && cached < 0.5; }
+// An O_DIRECT read the filesystem refused (EINVAL: alignment it does not take, a tmpfs) is not the file's failure: the
+// caller reads it buffered from there on.  Counted, first errno kept, so a systematic refusal shows.
+inline void odirect_refused(tv_ctx* c, int err) {
+    c->file_ns[TV_FILE_ODIRECT_FALLBACKS].fetch_add(1, std::memory_order_relaxed);
+    uint64_t none = 0;
+    c->file_ns[TV_FILE_ODIRECT_ERRNO].compare_exchange_strong(none, (uint64_t)err);
+}
 
 // ---- NUMA placement and the host worker pools --------------------------------------------------------------------
 

@@ -1,6 +1,6 @@
-// tv_files.hip -- staging from files (tv_stage_file, tv_stage_files): the reference's fsStorage.get reads
-// (storage.ts:149-172) done by the library's own threads, segment by segment as Storage.get's walk maps them
-// (storage.ts:89-137), with the reference's failure rules (a null piece, never an error) decided here.
+// tv_files.hip -- staging from files (tv_stage_file, tv_stage_files, tv_stage_file_table): the reference's
+// fsStorage.get reads (storage.ts:149-172) done by the library's own threads, segment by segment as Storage.get's walk
+// maps them (storage.ts:89-137), with the reference's failure rules (a null piece, never an error) decided here.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -11,8 +11,31 @@
 #include <cstring>
 
 #include "tv_ctx.h"
+#include "tv_fileio.h"
 
 using namespace tvi;
+
+// Fraction of file bytes [fo, fo + n) in the page cache, sampled: the range is mapped (no page is touched) and
+// mincore asks for 64 pages spread evenly over it; -1 when it cannot be mapped.  (cachestat(2) would be one call,
+// but on an overlay filesystem -- the test boxes' temp dir -- it reports the overlay inode, which caches nothing,
+// while mincore sees the pages of the real file the mapping is redirected to: a warm file read as cold there and
+// took the O_DIRECT path at disk speed.  A full mincore of a 256 MiB unit costs ~0.9 ms; 64 samples, microseconds.)
+double tvi::cached_fraction(int fd, uint64_t fo, uint64_t n) {
+    if (n == 0) return 1.0;
+    const uint64_t page = (uint64_t)sysconf(_SC_PAGESIZE);
+    const uint64_t off = fo / page * page, len = (fo - off + n + page - 1) / page * page, npages = len / page;
+    void* m = mmap(nullptr, len, PROT_READ, MAP_SHARED, fd, (off_t)off);
+    if (m == MAP_FAILED) return -1.0;
+    const uint64_t samples = std::min<uint64_t>(64, npages);
+    uint64_t hit = 0;
+    for (uint64_t s = 0; s < samples; s++) {
+        const uint64_t pg = (2 * s + 1) * npages / (2 * samples);
+        unsigned char v = 0;
+        if (mincore((uint8_t*)m + pg * page, page, &v) == 0) hit += v & 1;
+    }
+    munmap(m, len);
+    return (double)hit / (double)samples;
+}
 
 namespace {
 
@@ -40,64 +63,24 @@ double resident_fraction(void* m, uint64_t n, uint64_t page) {
 }
 
 // Read file bytes [fo, fo + n) into dst with parallel preads on the lane's persistent workers (`threads` of
-// them; parts of 1-4 MiB, at least two per thread so the slowest part ends the slot early).  The first `need`
-// bytes must all be read (n - need: an O_DIRECT read's rounding past the end of the file, which may come back
-// short).  Returns 0 or an errno value (EIO for a short read).  The round-1..4 form spawned `threads` std::threads
-// per 64 MiB slot.
+// them; parts of pread_part bytes).  The first `need` bytes must all be read (n - need: an O_DIRECT read's rounding
+// past the end of the file, which may come back short; a part at or past `need` is not continued, read_at).
+// Returns 0 or an errno value (EIO for a short read).  (Rounds 1-4 spawned `threads` std::threads per 64 MiB slot.)
 int pread_pool(Pool& pool, int threads, int fd, uint8_t* dst, uint64_t fo, uint64_t n, uint64_t need) {
     threads = std::max(1, threads);
-    uint64_t part = n / (2 * (uint64_t)threads);
-    part = std::min<uint64_t>(4ull << 20, std::max<uint64_t>(1ull << 20, (part + 65535) / 65536 * 65536));
-    const uint64_t nparts = (n + part - 1) / part;
+    const uint64_t part = pread_part(n, threads), nparts = (n + part - 1) / part;
     std::atomic<int> err{0};
     pool.run(threads, nparts, [&](uint64_t q) {
-        uint64_t o = q * part;
-        const uint64_t e = std::min(n, o + part);
-        // (o >= need: the bytes asked for are in -- an O_DIRECT read that came back short at the end of the file
-        // must not be continued, as its next request would start off a 4 KiB boundary and be refused)
-        while (o < e && o < need && !err.load(std::memory_order_relaxed)) {
-            const ssize_t got = pread(fd, dst + o, e - o, (off_t)(fo + o));
-            if (got < 0 && errno == EINTR) continue;
-            if (got <= 0) {
-                int expect = 0;
-                err.compare_exchange_strong(expect, got < 0 ? errno : EIO);
-                return;
-            }
-            o += (uint64_t)got;
+        const uint64_t o = q * part, e = std::min(n, o + part), must = std::min(e, need);
+        if (o >= must || err.load(std::memory_order_relaxed)) return;
+        const int64_t got = read_at(fd, dst + o, fo + o, must - o, e - o);
+        if (got < (int64_t)(must - o)) {
+            int expect = 0;
+            err.compare_exchange_strong(expect, got < 0 ? (int)-got : EIO);
         }
     });
     return err.load();
 }
-
-}  // namespace
-
-namespace tvi {
-
-// Fraction of file bytes [fo, fo + n) in the page cache, sampled: the range is mapped (no page is touched) and
-// mincore asks for 64 pages spread evenly over it; -1 when it cannot be mapped.  (cachestat(2) would be one call,
-// but on an overlay filesystem -- the gpurun boxes' /tmp -- it reports the overlay inode, which caches nothing,
-// while mincore sees the pages of the real file the mapping is redirected to: a warm file read as cold there and
-// took the O_DIRECT path at disk speed.  A full mincore of a 256 MiB unit costs ~0.9 ms; 64 samples, microseconds.)
-double cached_fraction(int fd, uint64_t fo, uint64_t n) {
-    if (n == 0) return 1.0;
-    const uint64_t page = (uint64_t)sysconf(_SC_PAGESIZE);
-    const uint64_t off = fo / page * page, len = (fo - off + n + page - 1) / page * page, npages = len / page;
-    void* m = mmap(nullptr, len, PROT_READ, MAP_SHARED, fd, (off_t)off);
-    if (m == MAP_FAILED) return -1.0;
-    const uint64_t samples = std::min<uint64_t>(64, npages);
-    uint64_t hit = 0;
-    for (uint64_t s = 0; s < samples; s++) {
-        const uint64_t pg = (2 * s + 1) * npages / (2 * samples);
-        unsigned char v = 0;
-        if (mincore((uint8_t*)m + pg * page, page, &v) == 0) hit += v & 1;
-    }
-    munmap(m, len);
-    return (double)hit / (double)samples;
-}
-
-}  // namespace tvi
-
-namespace {
 
 // The phase clock of file staging (internal counters TV_COUNTER_FILE_NS_*, tv_options_internal.h): nanoseconds a
 // scope spent, added to the ctx's total for its phase (both lanes add; a lane's phases do not overlap each other).
@@ -150,7 +133,7 @@ struct FileWindows {
     }
     int direct_fd(bool rw) {
         if (fd_direct == -1) {
-            fd_direct = open(path, (rw ? O_RDWR : O_RDONLY) | O_DIRECT | O_CLOEXEC);
+            fd_direct = open_direct(path, rw);
             if (fd_direct < 0) fd_direct = -2;
         }
         return fd_direct >= 0 ? fd_direct : -1;
@@ -222,7 +205,7 @@ int ensure_bounce(tv_ctx* c, int lane, int want) {
 // the errno of a failed O_DIRECT read (0: none; the caller then reads the chunk again buffered).
 int read_cold_bounce(tv_ctx* c, int lane, int readers, int dfd, uint64_t fo, uint64_t n, uint64_t p, int* read_err) {
     *read_err = 0;
-    const uint64_t al0 = fo / 4096 * 4096, end = fo + n;
+    const uint64_t al0 = direct_request(fo, n).al, end = fo + n;
     const uint64_t nparts = (end - al0 + kBounceBytes - 1) / kBounceBytes;
     int rc = ensure_bounce(c, lane, 2 * readers);
     if (rc) return rc;
@@ -255,18 +238,13 @@ int read_cold_bounce(tv_ctx* c, int lane, int readers, int dfd, uint64_t fo, uin
         }
         const uint64_t s0 = al0 + q * kBounceBytes;                     // the file byte at b.ptr[0]
         const uint64_t a = std::max(s0, fo), e = std::min(s0 + kBounceBytes, end);
-        const uint64_t want = e - s0, ask = (want + 4095) / 4096 * 4096;   // (the file's end may come back short)
-        uint64_t o = 0;
-        while (o < want) {
-            const ssize_t got = c->file_odirect == 2 ? (errno = EINVAL, -1)   // (fault injection, as the ring path)
-                                                     : pread(dfd, b.ptr + o, ask - o, (off_t)(s0 + o));
-            if (got < 0 && errno == EINTR) continue;
-            if (got <= 0) {
-                int none = 0;
-                err.compare_exchange_strong(none, got < 0 ? errno : EIO);
-                return;
-            }
-            o += (uint64_t)got;
+        const DirectReq rq = direct_request(s0, e - s0);                // (s0 is aligned; the file's end may come back short)
+        const int64_t got = c->file_odirect == 2 ? -EINVAL              // (fault injection, as the ring path)
+                                                 : read_at(dfd, b.ptr, s0, e - s0, rq.ask);
+        if (got < (int64_t)(e - s0)) {
+            int none = 0;
+            err.compare_exchange_strong(none, got < 0 ? (int)-got : EIO);
+            return;
         }
         int r = stage_range(c, p + (a - fo), p + (e - fo), b.ptr + (a - s0), p + (a - fo), true, lane,
                             /*src_in_ring=*/true);
@@ -310,8 +288,7 @@ int stage_units(tv_ctx* c, const std::vector<FileUnit>& units, int lane, int thr
         bool unit_cold = false;   // the unit's bytes are mostly not in the page cache: O_DIRECT reads
         if (!c->file_direct && c->file_odirect) {
             FileClock t(c, TV_FILE_PHASE_MAP);
-            const double f = cached_fraction(win.fd, u.fo, u.len);
-            unit_cold = f >= 0 && f < 0.5;
+            unit_cold = is_cold(cached_fraction(win.fd, u.fo, u.len));
         }
         bool unit_ok = true;
         for (uint64_t p = u.a; p < u.a + u.len && unit_ok; p += chunk, idx++) {
@@ -363,13 +340,16 @@ int stage_units(tv_ctx* c, const std::vector<FileUnit>& units, int lane, int thr
             } else {
                 // parallel preads into the pinned ring, then DMA.  A chunk whose bytes are mostly not in the page
                 // cache is read with O_DIRECT (TV_OPT_FILE_ODIRECT): cold reads ran 35 % faster that way on the
-                // gpurun boxes (tools/read_ceiling.c: 14.5-18.6 against 10.3-14.0 GB/s buffered, profiles/r05), and
+                // test boxes (tools/read_ceiling.c: 14.5-18.6 against 10.3-14.0 GB/s buffered, profiles/r05), and
                 // the page cache keeps nothing the verify will not read again.  Its requests are whole 4 KiB blocks
                 // into the slot's page-aligned start, so the chunk's bytes sit at slot + (fo % 4096): aligned for the
                 // DMA when the file offset and the linear offset agree mod 4 (else the buffered read, placed at the
                 // linear offset's alignment, is used).
                 win.release(k);
                 int dfd = (unit_cold && ((fo ^ p) & 3) == 0) ? win.direct_fd(c->open_rw) : -1;
+                // an O_DIRECT read refused: this file reads buffered from here on, this chunk included
+                const auto refused = [&](int e) { odirect_refused(c, e); win.no_direct(); dfd = -1; };
+                bool done = false;   // the bounce buffers took the chunk
                 if (dfd >= 0 && c->file_bounce > 0) {
                     int e = 0;
                     {
@@ -377,19 +357,11 @@ int stage_units(tv_ctx* c, const std::vector<FileUnit>& units, int lane, int thr
                         rc = read_cold_bounce(c, lane, std::min(threads, c->file_bounce), dfd, fo, n, p, &e);
                     }
                     if (rc) return rc;
-                    if (!e) {
-                        if (c->file_direct) TV_HIP(c, hipEventRecord(drain.ev[k], cs));
-                        continue;
-                    }
-                    // an O_DIRECT read refused: as in the ring path below, this file reads buffered from here on
-                    c->file_ns[TV_FILE_ODIRECT_FALLBACKS].fetch_add(1, std::memory_order_relaxed);
-                    uint64_t none = 0;
-                    c->file_ns[TV_FILE_ODIRECT_ERRNO].compare_exchange_strong(none, (uint64_t)e);
-                    win.no_direct();
-                    dfd = -1;
+                    if (e) refused(e);
+                    done = !e;
                 }
                 const uint64_t step = dfd >= 0 ? (uint64_t)kRingSlotBytes - 8192 : (uint64_t)kRingSlotBytes - 4;
-                for (uint64_t q = 0; q < n; q += step) {
+                for (uint64_t q = 0; q < n && !done; q += step) {
                     const uint64_t kq = std::min<uint64_t>(step, n - q);
                     SlotLease slot(c, lane);  // lent until every copy out of it is queued
                     {
@@ -397,32 +369,20 @@ int stage_units(tv_ctx* c, const std::vector<FileUnit>& units, int lane, int thr
                         rc = slot.take();
                         if (rc) return rc;
                     }
-                    uint8_t* at;
-                    int e;
-                    if (dfd >= 0) {
-                        const uint64_t al = (fo + q) / 4096 * 4096, lead = fo + q - al;
-                        at = slot.ptr() + lead;
+                    uint8_t* at = nullptr;
+                    int e = 0;
+                    if (dfd >= 0) {   // the O_DIRECT attempt
+                        const DirectReq rq = direct_request(fo + q, kq);
+                        at = slot.ptr() + rq.lead;
                         FileClock t(c, TV_FILE_PHASE_READ);
                         e = c->file_odirect == 2 ? EINVAL  // (fault injection: the filesystem refusing O_DIRECT reads)
-                                                 : pread_pool(c->pool[lane], threads, dfd, slot.ptr(), al,
-                                                              (lead + kq + 4095) / 4096 * 4096, lead + kq);
+                                                 : pread_pool(c->pool[lane], threads, dfd, slot.ptr(), rq.al, rq.ask,
+                                                              rq.lead + kq);
                         if (!e) c->file_ns[TV_FILE_BYTES_ODIRECT].fetch_add(kq, std::memory_order_relaxed);
-                        if (e) {
-                            // an O_DIRECT read the filesystem refuses (EINVAL: alignment it does not take, a tmpfs)
-                            // is not the file's failure: this file reads buffered from here on, this chunk included,
-                            // and only a buffered failure counts (it is what fsStorage.get's read would see).  The
-                            // fallback is counted and its first errno kept, so a systematic one (a ring slot the
-                            // kernel cannot pin for direct I/O) shows (TV_FILE_ODIRECT_FALLBACKS / _ERRNO)
-                            c->file_ns[TV_FILE_ODIRECT_FALLBACKS].fetch_add(1, std::memory_order_relaxed);
-                            uint64_t none = 0;
-                            c->file_ns[TV_FILE_ODIRECT_ERRNO].compare_exchange_strong(none, (uint64_t)e);
-                            win.no_direct();
-                            dfd = -1;
-                            at = slot.ptr() + ((p + q) & 3);
-                            e = pread_pool(c->pool[lane], threads, win.fd, at, fo + q, kq, kq);
-                        }
-                    } else {
-                        at = slot.ptr() + ((p + q) & 3);  // at the resident bytes' alignment mod 4
+                        else refused(e);
+                    }
+                    if (dfd < 0) {   // buffered (no direct descriptor, or refused): at the resident bytes' alignment mod 4
+                        at = slot.ptr() + ((p + q) & 3);
                         FileClock t(c, TV_FILE_PHASE_READ);
                         e = pread_pool(c->pool[lane], threads, win.fd, at, fo + q, kq, kq);
                     }
@@ -472,12 +432,8 @@ int stage_file_locked(tv_ctx* c, const char* path, uint64_t file_offset, uint64_
     return rc ? rc : st;
 }
 
-// Read every segment of `segs` into slot memory at its packed offset, on `threads` threads (each
-// segment: open, pread loop, close).  A missing, unreadable or short file sets its status to TV_ERR_IO.
-struct SmallSeg {
-    uint64_t k, file_offset, linear, len, packed;
-};
-
+// Read segments [lo, hi) of `segs` into slot memory at their packed offsets, on `threads` threads (each
+// segment: open, read, close).  A missing, unreadable or short file sets its status to TV_ERR_IO.
 void read_segments(Pool& pool, const std::vector<SmallSeg>& segs, size_t lo, size_t hi, const char* const* paths,
                    uint8_t* slot, int32_t* status, int threads, bool rw, std::string* first_err, std::mutex* err_mu) {
     // work items: (segment, part) with parts of at most 4 MiB, so one long segment is read by many threads;
@@ -493,16 +449,8 @@ void read_segments(Pool& pool, const std::vector<SmallSeg>& segs, size_t lo, siz
         int e = 0;
         const int fd = open_file(path, rw, &e);  // as fsStorage.get opens it, read + write (storage.ts:28-32)
         if (fd >= 0) {
-            uint64_t o = part0;
-            while (o < part1) {
-                const ssize_t got = pread(fd, slot + sg.packed + o, part1 - o, (off_t)(sg.file_offset + o));
-                if (got < 0 && errno == EINTR) continue;
-                if (got <= 0) {
-                    e = got < 0 ? errno : EIO;  // 0 bytes: the file is shorter than the segment
-                    break;
-                }
-                o += (uint64_t)got;
-            }
+            const int64_t got = read_at(fd, slot + sg.packed + part0, sg.file_offset + part0, part1 - part0, part1 - part0);
+            if (got < (int64_t)(part1 - part0)) e = got < 0 ? (int)-got : EIO;  // short: the file ends inside the segment
             close(fd);
         }
         if (e) {
@@ -514,24 +462,16 @@ void read_segments(Pool& pool, const std::vector<SmallSeg>& segs, size_t lo, siz
 }
 
 // Short segments (one part each, in linear order) packed into lane `lane`'s 64 MiB ring slots at their linear
-// offsets' alignment mod 4, read by the lane's pool (open, pread, close each: read_segments), one DMA per run of
-// readable linear-contiguous segments while the next slot is read.  A failed read sets status[k] = TV_ERR_IO.
+// offsets' alignment mod 4 (tv_plan.h pack_slot), read by the lane's pool (open, read, close each: read_segments),
+// one DMA per run of readable linear-contiguous segments (for_copy_runs) while the next slot is read.  A failed read
+// sets status[k] = TV_ERR_IO.
 int stage_small(tv_ctx* c, std::vector<SmallSeg>& small, int lane, int threads, const char* const* paths,
                 int32_t* status, std::string* first_err, std::mutex* err_mu, bool final_pass = true) {
     int rc = TV_OK;
     DrainGuard drain(c, lane, /*sync_compute=*/false);
-    size_t i = 0;
-    while (i < small.size()) {
-        size_t j = i;
-        uint64_t used = 0;
-        while (j < small.size()) {
-            // each byte sits in the slot at its linear offset's alignment mod 4 (dword-aligned DMA)
-            const uint64_t at = used + ((small[j].linear - used) & 3);
-            if (at + small[j].len > kRingSlotBytes) break;
-            small[j].packed = at;
-            used = at + small[j].len;
-            j++;
-        }
+    const auto readable = [&](size_t q) { return __atomic_load_n(&status[small[q].k], __ATOMIC_RELAXED) == TV_OK; };
+    for (size_t i = 0; i < small.size();) {
+        const size_t j = pack_slot(small, i, kRingSlotBytes);
         SlotLease slot(c, lane);  // lent until every copy out of it is queued
         {
             FileClock t(c, TV_FILE_PHASE_WAIT);
@@ -543,18 +483,11 @@ int stage_small(tv_ctx* c, std::vector<SmallSeg>& small, int lane, int threads, 
             read_segments(c->pool[lane], small, i, j, paths, slot.ptr(), status, threads, c->open_rw, first_err, err_mu);
         }
         FileClock t(c, TV_FILE_PHASE_QUEUE);
-        for (size_t q = i; q < j;) {  // one copy per run of readable, linear-contiguous segments
-            if (__atomic_load_n(&status[small[q].k], __ATOMIC_RELAXED) != TV_OK) { q++; continue; }
-            size_t r = q + 1;
-            while (r < j && __atomic_load_n(&status[small[r].k], __ATOMIC_RELAXED) == TV_OK &&
-                   small[r].linear == small[r - 1].linear + small[r - 1].len)
-                r++;
+        rc = for_copy_runs(small, i, j, readable, [&](size_t q, size_t r) {
             const uint64_t lin_a = small[q].linear, lin_b = small[r - 1].linear + small[r - 1].len;
-            rc = stage_range(c, lin_a, lin_b, slot.ptr() + small[q].packed, lin_a, true, lane, /*src_in_ring=*/true);
-            if (rc) return rc;
-            q = r;
-        }
-        rc = slot.release();
+            return stage_range(c, lin_a, lin_b, slot.ptr() + small[q].packed, lin_a, true, lane, /*src_in_ring=*/true);
+        });
+        if (!rc) rc = slot.release();
         if (rc) return rc;
         i = j;
     }
@@ -569,9 +502,8 @@ int stage_small(tv_ctx* c, std::vector<SmallSeg>& small, int lane, int threads, 
 
 // Mark the shard pieces holding linear bytes [a, b) unreadable (tv_verify reports them 0).
 void mark_bad(tv_ctx* c, uint64_t a, uint64_t b) {
-    const uint64_t lo = c->first * c->L;
-    const uint64_t last = c->first + c->count - 1;
-    const uint64_t hi = last * c->L + piece_len(c, last);
+    uint64_t lo, hi;
+    shard_bytes(c, /*clamp_total=*/false, &lo, &hi);
     if (a == b) {  // a zero-length segment: the piece it sits in
         if (a < lo || a >= hi) return;
         b = a + 1;
@@ -614,62 +546,6 @@ int recover_segment(tv_ctx* c, const char* path, uint64_t file_offset, uint64_t 
     mark_bad(c, linear_offset + r, linear_offset + len);
     return TV_OK;
 }
-
-}  // namespace
-
-extern "C" {
-
-int tv_stage_file(tv_ctx* c, const char* path, uint64_t file_offset, uint64_t linear_offset, uint64_t len) {
-    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
-    std::lock_guard<std::mutex> g(c->mu);
-    FileClock call_clock(c, TV_FILE_PHASE_CALL);
-    int rc = require_layout(c, false, true);
-    if (rc) return rc;
-    if (!path) return fail(c, TV_ERR_ARG, "path is NULL");
-    if (linear_offset + len < linear_offset || file_offset + len < file_offset)
-        return fail(c, TV_ERR_ARG, "offset + len overflows");
-    uint64_t a = 0, b = 0;
-    if (c->count) clip_to_whole_shard(c, linear_offset, len, &a, &b);
-    if (!c->win || len == 0 || a >= b) {
-        rc = stage_file_locked(c, path, file_offset, linear_offset, len);
-        if (rc == TV_OK) clear_bad(c, a, b);
-        if (rc != TV_ERR_IO || c->count == 0) return rc;
-        const std::string err = c->err;
-        const int r = recover_segment(c, path, file_offset, linear_offset, len);
-        if (r) return r;
-        fail(c, TV_ERR_IO, "%s", err.c_str());  // the first failure stays the call's message
-        return TV_ERR_IO;
-    }
-    // windowed layout: the segment window by window (each part is checked, staged and recovered on its own, so a
-    // short file still keeps its whole pieces before the first missing byte)
-    TV_HIP(c, hipSetDevice(c->device));
-    std::string first_err;
-    for (uint64_t pos = a; pos < b;) {
-        const uint64_t w = win_of(c, pos / c->L - c->first);
-        rc = win_enter(c, w);
-        if (rc) return rc;
-        const uint64_t e = std::min(b, win_end_linear(c, w));
-        const uint64_t fo = file_offset + (pos - linear_offset);
-        rc = stage_file_locked(c, path, fo, pos, e - pos);
-        if (rc == TV_OK) {
-            clear_bad(c, pos, e);
-        } else if (rc == TV_ERR_IO) {
-            if (first_err.empty()) first_err = c->err;
-            rc = recover_segment(c, path, fo, pos, e - pos);
-            if (rc) return rc;
-        } else {
-            return rc;
-        }
-        pos = e;
-    }
-    if (first_err.empty()) return TV_OK;
-    fail(c, TV_ERR_IO, "%s", first_err.c_str());
-    return TV_ERR_IO;
-}
-
-}  // extern "C"
-
-namespace {
 
 // tv_stage_files with the lock held and the arguments checked: every segment's bytes among the resident pieces
 // (clip_to_shard: the shard, or a windowed layout's open window).  status_out[k] is set to TV_ERR_IO on a
@@ -788,82 +664,6 @@ int stage_files_core(tv_ctx* c, uint64_t n, const char* const* paths, const uint
     return TV_OK;
 }
 
-int stage_files_locked(tv_ctx* c, uint64_t n, const char* const* paths, const uint64_t* file_offsets,
-                       const uint64_t* linear_offsets, const uint64_t* lens, int32_t* status_out);
-
-}  // namespace
-
-extern "C" {
-
-int tv_stage_files(tv_ctx* c, uint64_t n, const char* const* paths, const uint64_t* file_offsets,
-                   const uint64_t* linear_offsets, const uint64_t* lens, int32_t* status_out) {
-    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
-    std::lock_guard<std::mutex> g(c->mu);
-    FileClock call_clock(c, TV_FILE_PHASE_CALL);
-    int rc = require_layout(c, false, true);
-    if (rc) return rc;
-    if (n == 0) return TV_OK;
-    if (!paths || !file_offsets || !linear_offsets || !lens || !status_out)
-        return fail(c, TV_ERR_ARG, "NULL argument");
-    for (uint64_t k = 0; k < n; k++) {
-        if (!paths[k]) return fail(c, TV_ERR_ARG, "paths[%llu] is NULL", (unsigned long long)k);
-        if (linear_offsets[k] + lens[k] < linear_offsets[k] || file_offsets[k] + lens[k] < file_offsets[k])
-            return fail(c, TV_ERR_ARG, "segment %llu: offset + len overflows", (unsigned long long)k);
-        status_out[k] = TV_OK;
-    }
-    return stage_files_locked(c, n, paths, file_offsets, linear_offsets, lens, status_out);
-}
-
-int tv_stage_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const char* paths, uint64_t paths_bytes,
-                        int32_t* status_out) {
-    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
-    std::lock_guard<std::mutex> g(c->mu);
-    FileClock call_clock(c, TV_FILE_PHASE_CALL);
-    int rc = require_layout(c, false, true);
-    if (rc) return rc;
-    if (n == 0) return TV_OK;
-    if (!lengths || !paths || !status_out) return fail(c, TV_ERR_ARG, "NULL argument");
-    // file k's path: the k-th NUL-terminated string of the buffer
-    std::vector<const char*> path(n);
-    uint64_t o = 0;
-    for (uint64_t k = 0; k < n; k++) {
-        const void* z = o < paths_bytes ? memchr(paths + o, 0, paths_bytes - o) : nullptr;
-        if (!z)
-            return fail(c, TV_ERR_ARG, "paths holds %llu NUL-terminated paths in %llu bytes, the table %llu files",
-                        (unsigned long long)k, (unsigned long long)paths_bytes, (unsigned long long)n);
-        path[k] = paths + o;
-        o = (uint64_t)((const char*)z - paths) + 1;
-        status_out[k] = TV_OK;
-    }
-    if (c->count == 0) return TV_OK;
-    // findAndDo's walk over the files in order (storage.ts:98-137), restricted to the shard's bytes (tv_plan.h)
-    const uint64_t last = c->first + c->count - 1;
-    const uint64_t lo = c->first * c->L, hi = std::min(c->total, last * c->L + piece_len(c, last));
-    std::vector<TableSeg> segs;
-    uint64_t bad = 0, reached = 0;
-    if (!walk_file_table(n, lengths, lo, hi, c->L, &segs, &bad, &reached))
-        return fail(c, TV_ERR_ARG, "file %llu: the lengths overflow 64-bit offsets", (unsigned long long)bad);
-    std::vector<const char*> sp;
-    std::vector<uint64_t> sfo, slin, slen;
-    for (const TableSeg& g : segs) {
-        sp.push_back(path[g.file]);
-        sfo.push_back(g.file_offset);
-        slin.push_back(g.linear);
-        slen.push_back(g.len);
-    }
-    std::vector<int32_t> st(sp.size(), TV_OK);
-    if (!sp.empty()) rc = stage_files_locked(c, sp.size(), sp.data(), sfo.data(), slin.data(), slen.data(), st.data());
-    for (size_t q = 0; q < sp.size(); q++)
-        if (st[q] != TV_OK) status_out[segs[q].file] = st[q];
-    // the files end before the shard does: Storage.get's walk for a piece past their end never completes (null)
-    if (!rc && reached < hi) mark_bad(c, reached, hi);
-    return rc;
-}
-
-}  // extern "C"
-
-namespace {
-
 // tv_stage_files' work with the lock held and the segments checked (status_out preset to TV_OK).
 int stage_files_locked(tv_ctx* c, uint64_t n, const char* const* paths, const uint64_t* file_offsets,
                        const uint64_t* linear_offsets, const uint64_t* lens, int32_t* status_out) {
@@ -918,3 +718,112 @@ int stage_files_locked(tv_ctx* c, uint64_t n, const char* const* paths, const ui
 }
 
 }  // namespace
+
+extern "C" {
+
+int tv_stage_file(tv_ctx* c, const char* path, uint64_t file_offset, uint64_t linear_offset, uint64_t len) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    FileClock call_clock(c, TV_FILE_PHASE_CALL);
+    int rc = require_layout(c, false, true);
+    if (rc) return rc;
+    if (!path) return fail(c, TV_ERR_ARG, "path is NULL");
+    if (linear_offset + len < linear_offset || file_offset + len < file_offset)
+        return fail(c, TV_ERR_ARG, "offset + len overflows");
+    uint64_t a = 0, b = 0;
+    if (c->count) clip_to_whole_shard(c, linear_offset, len, &a, &b);
+    if (!c->win || len == 0 || a >= b) {
+        rc = stage_file_locked(c, path, file_offset, linear_offset, len);
+        if (rc == TV_OK) clear_bad(c, a, b);
+        if (rc != TV_ERR_IO || c->count == 0) return rc;
+        const std::string err = c->err;
+        const int r = recover_segment(c, path, file_offset, linear_offset, len);
+        if (r) return r;
+        fail(c, TV_ERR_IO, "%s", err.c_str());  // the first failure stays the call's message
+        return TV_ERR_IO;
+    }
+    // windowed layout: the segment window by window (each part is checked, staged and recovered on its own, so a
+    // short file still keeps its whole pieces before the first missing byte)
+    TV_HIP(c, hipSetDevice(c->device));
+    std::string first_err;
+    for (uint64_t pos = a; pos < b;) {
+        const uint64_t w = win_of(c, pos / c->L - c->first);
+        rc = win_enter(c, w);
+        if (rc) return rc;
+        const uint64_t e = std::min(b, win_end_linear(c, w));
+        const uint64_t fo = file_offset + (pos - linear_offset);
+        rc = stage_file_locked(c, path, fo, pos, e - pos);
+        if (rc == TV_OK) {
+            clear_bad(c, pos, e);
+        } else if (rc == TV_ERR_IO) {
+            if (first_err.empty()) first_err = c->err;
+            rc = recover_segment(c, path, fo, pos, e - pos);
+            if (rc) return rc;
+        } else {
+            return rc;
+        }
+        pos = e;
+    }
+    if (first_err.empty()) return TV_OK;
+    fail(c, TV_ERR_IO, "%s", first_err.c_str());
+    return TV_ERR_IO;
+}
+
+int tv_stage_files(tv_ctx* c, uint64_t n, const char* const* paths, const uint64_t* file_offsets,
+                   const uint64_t* linear_offsets, const uint64_t* lens, int32_t* status_out) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    FileClock call_clock(c, TV_FILE_PHASE_CALL);
+    int rc = require_layout(c, false, true);
+    if (rc) return rc;
+    if (n == 0) return TV_OK;
+    if (!paths || !file_offsets || !linear_offsets || !lens || !status_out)
+        return fail(c, TV_ERR_ARG, "NULL argument");
+    for (uint64_t k = 0; k < n; k++) {
+        if (!paths[k]) return fail(c, TV_ERR_ARG, "paths[%llu] is NULL", (unsigned long long)k);
+        if (linear_offsets[k] + lens[k] < linear_offsets[k] || file_offsets[k] + lens[k] < file_offsets[k])
+            return fail(c, TV_ERR_ARG, "segment %llu: offset + len overflows", (unsigned long long)k);
+        status_out[k] = TV_OK;
+    }
+    return stage_files_locked(c, n, paths, file_offsets, linear_offsets, lens, status_out);
+}
+
+int tv_stage_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const char* paths, uint64_t paths_bytes,
+                        int32_t* status_out) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    FileClock call_clock(c, TV_FILE_PHASE_CALL);
+    int rc = require_layout(c, false, true);
+    if (rc) return rc;
+    if (n == 0) return TV_OK;
+    if (!lengths || !paths || !status_out) return fail(c, TV_ERR_ARG, "NULL argument");
+    std::vector<const char*> path(n);
+    const uint64_t np = parse_path_table(n, paths, paths_bytes, path.data());
+    std::fill(status_out, status_out + np, (int32_t)TV_OK);
+    if (np < n) return path_error(c, np, paths_bytes, n);
+    if (c->count == 0) return TV_OK;
+    // findAndDo's walk over the files in order (storage.ts:98-137), restricted to the shard's bytes (tv_plan.h)
+    uint64_t lo, hi;
+    shard_bytes(c, /*clamp_total=*/true, &lo, &hi);
+    std::vector<TableSeg> segs;
+    uint64_t bad = 0, reached = 0;
+    if (!walk_file_table(n, lengths, lo, hi, c->L, &segs, &bad, &reached))
+        return fail(c, TV_ERR_ARG, "file %llu: the lengths overflow 64-bit offsets", (unsigned long long)bad);
+    std::vector<const char*> sp;
+    std::vector<uint64_t> sfo, slin, slen;
+    for (const TableSeg& g : segs) {
+        sp.push_back(path[g.file]);
+        sfo.push_back(g.file_offset);
+        slin.push_back(g.linear);
+        slen.push_back(g.len);
+    }
+    std::vector<int32_t> st(sp.size(), TV_OK);
+    if (!sp.empty()) rc = stage_files_locked(c, sp.size(), sp.data(), sfo.data(), slin.data(), slen.data(), st.data());
+    for (size_t q = 0; q < sp.size(); q++)
+        if (st[q] != TV_OK) status_out[segs[q].file] = st[q];
+    // the files end before the shard does: Storage.get's walk for a piece past their end never completes (null)
+    if (!rc && reached < hi) mark_bad(c, reached, hi);
+    return rc;
+}
+
+}  // extern "C"

@@ -6,8 +6,11 @@
 // on the CPU (tests/c/plan_test.cpp, tests/c/walk_main.cpp, tests/c/plan_v2_main.cpp, tests/c/plan_v2_blocks_main.cpp,
 // tests/c/plan_codec_main.cpp, tests/c/plan_list_main.cpp, tests/c/plan_hybrid_main.cpp; tests/test_plan.py,
 // test_plan_v2.py, test_plan_v2_blocks.py, test_plan_codec.py, test_plan_list.py, test_plan_hybrid.py).
+// Also the file calls' path table (parse_path_table) and the short segments' slot packing and copy runs (pack_slot,
+// for_copy_runs): tests/c/fileio_main.cpp, tests/test_fileio.py.
 #pragma once
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <vector>
@@ -111,6 +114,53 @@ inline bool walk_file_table(uint64_t n, const uint64_t* lengths, uint64_t lo, ui
     }
     *reached = start;
     return true;
+}
+
+// The path table of the file-table calls: file k's path is the k-th NUL-terminated string of paths[0, paths_bytes)
+// (bytes after the n-th string are ignored).  -> n with out[0..n) set, or the count of whole strings found (< n).
+inline uint64_t parse_path_table(uint64_t n, const char* paths, uint64_t paths_bytes, const char** out) {
+    uint64_t o = 0;
+    for (uint64_t k = 0; k < n; k++) {
+        const void* z = o < paths_bytes ? memchr(paths + o, 0, paths_bytes - o) : nullptr;
+        if (!z) return k;
+        out[k] = paths + o;
+        o = (uint64_t)((const char*)z - paths) + 1;
+    }
+    return n;
+}
+
+// A short file segment of tv_stage_files (segment k of the call): file bytes [file_offset, file_offset + len) are
+// LINEAR bytes [linear, linear + len), read into a ring slot at byte `packed`.
+struct SmallSeg {
+    uint64_t k, file_offset, linear, len, packed;
+};
+
+// Pack segments s[i..] into one slot of slot_bytes: each at the next byte whose offset agrees with its linear offset
+// mod 4 (a dword-aligned DMA), while they fit.  -> j: s[i, j) are packed (their `packed` set).
+inline size_t pack_slot(std::vector<SmallSeg>& s, size_t i, uint64_t slot_bytes) {
+    uint64_t used = 0;
+    size_t j = i;
+    for (; j < s.size(); j++) {
+        const uint64_t at = used + ((s[j].linear - used) & 3);
+        if (at + s[j].len > slot_bytes) break;
+        s[j].packed = at;
+        used = at + s[j].len;
+    }
+    return j;
+}
+
+// One copy per run of readable (ok(q)), linear-contiguous segments of s[i, j) (packed by pack_slot: contiguous in the
+// slot too): copy(q, r) for the run s[q, r); a nonzero return ends the walk and is returned.
+template <class Ok, class Copy>
+int for_copy_runs(const std::vector<SmallSeg>& s, size_t i, size_t j, Ok&& ok, Copy&& copy) {
+    for (size_t q = i; q < j;) {
+        if (!ok(q)) { q++; continue; }
+        size_t r = q + 1;
+        while (r < j && ok(r) && s[r].linear == s[r - 1].linear + s[r - 1].len) r++;
+        if (const int rc = copy(q, r)) return rc;
+        q = r;
+    }
+    return 0;
 }
 
 // ---- a stream's geometry under a device budget (tv_stream.hip: tv_stream_file_table, tv_verify_host) ----------------

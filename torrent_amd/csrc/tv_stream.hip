@@ -11,6 +11,7 @@
 #include <memory>
 
 #include "tv_ctx.h"
+#include "tv_fileio.h"
 
 namespace tvi {
 
@@ -420,8 +421,8 @@ int stream_result(tv_ctx* c, int rc) {
 int stream_files_locked(tv_ctx* c, uint64_t n, const uint64_t* lengths, const std::vector<const char*>& path,
                         const std::vector<uint64_t>& start, RowBytes rule, const std::function<int(bool)>& begin,
                         uint8_t* bitfield_out, int32_t* status_out) {
-    const uint64_t last = c->first + c->count - 1;
-    const uint64_t lo = c->first * c->L, hi = std::min(c->total, last * c->L + piece_len(c, last));
+    uint64_t lo, hi;
+    shard_bytes(c, /*clamp_total=*/true, &lo, &hi);
     // Whether the shard's files are mostly not in the page cache (TV_OPT_FILE_ODIRECT): up to 16 of the files holding
     // >= 1 MiB of its bytes, evenly spread, each sampled as the staging path samples a unit (64 pages), weighted by
     // bytes.  A cold shard is read in longer rows (fewer pieces per window) by more readers: O_DIRECT reads wait on
@@ -498,65 +499,13 @@ int stream_files_locked(tv_ctx* c, uint64_t n, const uint64_t* lengths, const st
             cached++;
             fds[k] = d;
             if (c->file_odirect && lengths[k] >= (1u << 20)) {
-                const double f = cached_fraction(d, 0, lengths[k]);
-                if (f >= 0 && f < 0.5) dfds[k] = open(path[k], (c->open_rw ? O_RDWR : O_RDONLY) | O_DIRECT | O_CLOEXEC);
+                if (is_cold(cached_fraction(d, 0, lengths[k]))) dfds[k] = open_direct(path[k], c->open_rw);
                 if (dfds[k] >= 0) *dfd = dfds[k];
             }
             return d;
         }
         *own = true;
         return d;
-    };
-    // file bytes [fo, fo + len) -> dst through the O_DIRECT descriptor: straight into dst when the file offset, dst
-    // and the length are 4 KiB-aligned (whole-row reads of a one-file torrent), else via a 4 KiB-aligned scratch of
-    // the reader thread's in 4 MiB steps.  -> bytes read (short: the file ended), or -errno.
-    auto read_direct = [&](int dfd, uint64_t fo, uint8_t* dst, uint64_t len) -> int64_t {
-        if (c->file_odirect == 2) return -EINVAL;   // (fault injection: the filesystem refusing O_DIRECT reads)
-        uint64_t o = 0;
-        if (fo % 4096 == 0 && (uintptr_t)dst % 4096 == 0 && len % 4096 == 0) {
-            while (o < len) {
-                const ssize_t got = pread(dfd, dst + o, len - o, (off_t)(fo + o));
-                if (got < 0 && errno == EINTR) continue;
-                if (got < 0) return -errno;
-                if (got == 0) break;
-                o += (uint64_t)got;
-            }
-            return (int64_t)o;
-        }
-        constexpr uint64_t kStep = 4ull << 20;
-        struct Scratch {   // (sized to the longest read the thread has needed: a row, at most kStep + 8 KiB)
-            uint8_t* p = nullptr;
-            uint64_t cap = 0;
-            ~Scratch() { free(p); }
-        };
-        thread_local Scratch scratch;
-        const uint64_t need = std::min(kStep, len) + 8192;
-        if (scratch.cap < need) {
-            free(scratch.p);
-            scratch.cap = 0;
-            if (posix_memalign((void**)&scratch.p, 4096, need)) {
-                scratch.p = nullptr;
-                return -ENOMEM;
-            }
-            scratch.cap = need;
-        }
-        while (o < len) {
-            const uint64_t at = fo + o, al = at / 4096 * 4096, lead = at - al;
-            const uint64_t m = std::min(kStep, len - o), ask = (lead + m + 4095) / 4096 * 4096;
-            uint64_t got_all = 0;
-            while (got_all < ask) {
-                const ssize_t got = pread(dfd, scratch.p + got_all, ask - got_all, (off_t)(al + got_all));
-                if (got < 0 && errno == EINTR) continue;
-                if (got < 0) return -errno;
-                if (got == 0) break;
-                got_all += (uint64_t)got;
-            }
-            const uint64_t have = got_all > lead ? std::min(m, got_all - lead) : 0;
-            memcpy(dst + o, scratch.p + lead, have);
-            o += have;
-            if (have < m) break;   // the file ended
-        }
-        return (int64_t)o;
     };
     const int readers = cold ? (c->stream_cold_readers ? c->stream_cold_readers : 2 * c->file_threads) : c->file_threads;
     DrainGuard drain(c);  // (the ring's copies and the column kernels are done when the call returns)
@@ -593,7 +542,8 @@ int stream_files_locked(tv_ctx* c, uint64_t n, const uint64_t* lengths, const st
                 const int fd = fd_of(k, &own, &dfd);
                 uint64_t o = 0;
                 if (dfd >= 0) {
-                    const int64_t got = read_direct(dfd, pos - start[k], out + (pos - a), e - pos);
+                    const int64_t got = c->file_odirect == 2 ? -EINVAL   // (fault injection: O_DIRECT reads refused)
+                                                             : read_direct(dfd, pos - start[k], out + (pos - a), e - pos);
                     if (got >= 0) {
                         o = (uint64_t)got;
                         c->file_ns[TV_FILE_BYTES_ODIRECT].fetch_add(o, std::memory_order_relaxed);
@@ -601,16 +551,13 @@ int stream_files_locked(tv_ctx* c, uint64_t n, const uint64_t* lengths, const st
                         // an O_DIRECT read the filesystem refuses is not the file's failure: this file reads buffered
                         // from here on, this row included (counted, first errno kept, as the staging path's fallback)
                         no_direct[k].store(true, std::memory_order_relaxed);
-                        c->file_ns[TV_FILE_ODIRECT_FALLBACKS].fetch_add(1, std::memory_order_relaxed);
-                        uint64_t none = 0;
-                        c->file_ns[TV_FILE_ODIRECT_ERRNO].compare_exchange_strong(none, (uint64_t)-got);
+                        odirect_refused(c, (int)-got);
                     }
                 }
-                while (fd >= 0 && o < e - pos) {
-                    const ssize_t got = pread(fd, out + (pos - a) + o, e - pos - o, (off_t)(pos - start[k] + o));
-                    if (got < 0 && errno == EINTR) continue;
-                    if (got <= 0) break;
-                    o += (uint64_t)got;
+                if (fd >= 0 && o < e - pos) {   // (a failed read's bytes so far still count as read)
+                    uint64_t in = 0;
+                    read_at(fd, out + (pos - a) + o, pos - start[k] + o, e - pos - o, e - pos - o, &in);
+                    o += in;
                 }
                 if (own) close(fd);
                 c->file_ns[TV_FILE_BYTES_READ].fetch_add(o, std::memory_order_relaxed);
@@ -622,11 +569,8 @@ int stream_files_locked(tv_ctx* c, uint64_t n, const uint64_t* lengths, const st
                 pos = e;
             }
         });
-        for (uint64_t q = 0; q < req.rows; q++) {
-            if (!row_bad[q]) continue;
-            const uint64_t j = req.piece + q - c->first;
-            c->st.av[j >> 3] &= (uint8_t)~(0x80u >> (j & 7));
-        }
+        for (uint64_t q = 0; q < req.rows; q++)
+            if (row_bad[q]) clear_bit(c->st.av.data(), req.piece + q - c->first);
         rc = stream_commit_locked(c, &req, nullptr, 0, true, req.rows);
         if (rc) break;
     }
@@ -713,13 +657,9 @@ int tv_stream_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const c
     if (n && (!lengths || !paths || !status_out)) return fail(c, TV_ERR_ARG, "NULL argument");
     std::vector<const char*> path(n);
     std::vector<uint64_t> start(n + 1, 0);   // file k's linear bytes: [start[k], start[k + 1])
-    for (uint64_t k = 0, o = 0; k < n; k++) {
-        const void* z = o < paths_bytes ? memchr(paths + o, 0, paths_bytes - o) : nullptr;
-        if (!z)
-            return fail(c, TV_ERR_ARG, "paths holds %llu NUL-terminated paths in %llu bytes, the table %llu files",
-                        (unsigned long long)k, (unsigned long long)paths_bytes, (unsigned long long)n);
-        path[k] = paths + o;
-        o = (uint64_t)((const char*)z - paths) + 1;
+    const uint64_t np = parse_path_table(n, paths, paths_bytes, path.data());
+    for (uint64_t k = 0; k < n; k++) {
+        if (k == np) return path_error(c, np, paths_bytes, n);
         if (lengths[k] > UINT64_MAX - start[k])
             return fail(c, TV_ERR_ARG, "file %llu: the lengths overflow 64-bit offsets", (unsigned long long)k);
         start[k + 1] = start[k] + lengths[k];
@@ -727,8 +667,8 @@ int tv_stream_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const c
     }
     if (!c->count) return TV_OK;
     TV_HIP(c, hipSetDevice(c->device));
-    const uint64_t last = c->first + c->count - 1;
-    const uint64_t lo = c->first * c->L, hi = std::min(c->total, last * c->L + piece_len(c, last));
+    uint64_t lo, hi;
+    shard_bytes(c, /*clamp_total=*/true, &lo, &hi);
     // availability before any read: the caller's bits, pieces past the files' end, and the pieces whose walk has a
     // zero-length segment whose open fails (the same segments tv_stage_file_table checks)
     std::vector<uint8_t> av((c->count + 7) / 8, 0);
@@ -745,8 +685,7 @@ int tv_stream_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const c
             if (sg.len || sg.linear < lo || sg.linear >= hi) continue;
             if (fs_openable(path[sg.file], c->open_rw)) {
                 status_out[sg.file] = TV_ERR_IO;
-                const uint64_t j = sg.linear / c->L - c->first;
-                av[j >> 3] &= (uint8_t)~(0x80u >> (j & 7));
+                clear_bit(av.data(), sg.linear / c->L - c->first);
             }
         }
     }
@@ -804,14 +743,8 @@ int tv_v2_stream_file_table(tv_ctx* c, uint64_t n_pieces, const uint32_t* piece_
     if (!bitfield_out && c->count) return fail(c, TV_ERR_ARG, "bitfield_out is NULL");
     if (n && (!lengths || !paths || !status_out)) return fail(c, TV_ERR_ARG, "NULL argument");
     std::vector<const char*> path(n);
-    for (uint64_t k = 0, o = 0; k < n; k++) {
-        const void* z = o < paths_bytes ? memchr(paths + o, 0, paths_bytes - o) : nullptr;
-        if (!z)
-            return fail(c, TV_ERR_ARG, "paths holds %llu NUL-terminated paths in %llu bytes, the table %llu files",
-                        (unsigned long long)k, (unsigned long long)paths_bytes, (unsigned long long)n);
-        path[k] = paths + o;
-        o = (uint64_t)((const char*)z - paths) + 1;
-    }
+    const uint64_t np = parse_path_table(n, paths, paths_bytes, path.data());
+    if (np < n) return path_error(c, np, paths_bytes, n);
     std::vector<uint64_t> start;   // file k's linear bytes: [start[k], start[k] + lengths[k])
     uint64_t bad = 0;
     if (!v2_file_starts(n, lengths, c->L, &start, &bad))
@@ -868,8 +801,7 @@ int tv_stream_unreadable(tv_ctx* c, uint64_t piece) {
     if (!c->st.active) return fail(c, TV_ERR_STATE, "tv_stream_begin has not been called");
     if (piece < c->first || piece >= c->first + c->count)
         return fail(c, TV_ERR_ARG, "piece %llu is not in this context's shard", (unsigned long long)piece);
-    const uint64_t j = piece - c->first;
-    c->st.av[j >> 3] &= (uint8_t)~(0x80u >> (j & 7));
+    clear_bit(c->st.av.data(), piece - c->first);
     return TV_OK;
 }
 
