@@ -9,7 +9,7 @@ import pytest
 
 from tests import hybrid_util as hu
 from tests import synth, v2_ref, v2_util
-from torrent_amd import hybrid, parse_metainfo, parse_metainfo_hybrid, parse_metainfo_v2
+from torrent_amd import hybrid, parse_metainfo, parse_metainfo_hybrid, parse_metainfo_v2, verify
 
 L = 32 << 10
 LEAF = 16384
@@ -205,7 +205,7 @@ def fake(monkeypatch):
     def run_shards(devs, n_pieces, fn):
         ranges = [(0, 8), (8, n_pieces - 8)] if n_pieces > 8 else [(0, n_pieces)]    # two shards where there are pieces for two
         return ranges, [fn(_HashCtx(), first, count) for first, count in ranges]
-    monkeypatch.setattr(hybrid, "_run_shards", run_shards)
+    monkeypatch.setattr(verify, "_run_shards", run_shards)      # (where the shared shard runners look it up)
 
 
 def _write_tree(root, lengths, seed=70):

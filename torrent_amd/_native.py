@@ -230,6 +230,19 @@ def _path_blob(what: str, paths) -> bytes:
     return blob
 
 
+def _file_table(what: str, lengths, paths) -> tuple:
+    """A file table (file k: lengths[k] bytes at paths[k]) as the arguments the library reads, lengths checked: (n, the
+    lengths, the path blob, the per-file status array); for an empty table the two arrays still hold one element, so
+    the library is given no NULL."""
+    import numpy as np
+
+    n = len(paths)
+    if len(lengths) != n:
+        raise ValueError(f"{what}: lengths and paths differ in length")
+    return (n, np.ascontiguousarray(lengths if n else [0], dtype=np.uint64), _path_blob(what, paths),
+            np.zeros(max(1, n), dtype=np.int32))
+
+
 def _v2_arrays(what: str, piece_bytes, tree_leaves, pieces=None) -> tuple:
     """A v2 piece table's (or, with `pieces`, an entry list's) columns as the arrays the library reads, lengths checked:
     (piece_bytes, tree_leaves) or (pieces, piece_bytes, tree_leaves)."""
@@ -439,35 +452,19 @@ class Context:
     def stage_file_table(self, lengths, paths) -> list:
         """tv_stage_file_table: the shard's bytes from the torrent's file table (file k: lengths[k] bytes at
         paths[k], in info.files order); the library makes Storage.get's walk itself.  One status per FILE."""
-        import numpy as np
-
-        n = len(paths)
-        if len(lengths) != n:
-            raise ValueError("stage_file_table: lengths and paths differ in length")
+        n, ln, blob, st = _file_table("stage_file_table", lengths, paths)
         if n == 0:
             return []
-        blob = _path_blob("stage_file_table", paths)
-        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
-        st = np.zeros(n, dtype=np.int32)
         self._check(self._L.tv_stage_file_table(self._h, n, ln.ctypes.data, blob, len(blob), st.ctypes.data))
         return st.tolist()
 
     def stream_file_table(self, lengths, paths, avail: Optional[bytes] = None) -> tuple:
         """tv_stream_file_table: the resume check from the files through the bounded ring (the library's readers
         fill each column's rows from the file table).  -> (bitfield, per-file statuses)."""
-        import numpy as np
-
-        n = len(paths)
-        if len(lengths) != n:
-            raise ValueError("stream_file_table: lengths and paths differ in length")
-        blob = _path_blob("stream_file_table", paths)
-        ln = np.ascontiguousarray(lengths if n else [0], dtype=np.uint64)
-        st = np.zeros(max(1, n), dtype=np.int32)
-        out = self._bits_out()
-        a, keep = _addr(avail)
-        self._check(self._L.tv_stream_file_table(self._h, n, ln.ctypes.data, blob, len(blob), a, out, st.ctypes.data))
-        del keep
-        return out.raw[: self._nbits()], st[:n].tolist()
+        n, ln, blob, st = _file_table("stream_file_table", lengths, paths)
+        bits = self._bits_call(self._L.tv_stream_file_table, n, ln.ctypes.data, blob, len(blob), avail=avail,
+                               tail=(st.ctypes.data,))
+        return bits, st[:n].tolist()
 
     def stage_files(self, paths, file_offsets, linear_offsets, lens) -> list:
         """tv_stage_files: stage many file segments in one call.  Returns one status per segment:
@@ -509,25 +506,27 @@ class Context:
     def _nbits(self) -> int:
         return (self.shard_count + 7) // 8
 
-    def _bits_out(self):
-        """The output buffer of a shard bitfield (never empty: the library is given a non-NULL pointer)."""
-        return ctypes.create_string_buffer(max(1, self._nbits()))
+    def _bits_call(self, fn, *args, avail=None, takes_avail: bool = True, outs: int = 1, tail: tuple = ()):
+        """fn(handle, *args, the availability bitfield or NULL, `outs` shard bitfields out, *tail): a call with an
+        optional availability bitfield in (takes_avail=False: the call has no such argument) and the shard's bitfield
+        out -> that bitfield, or the tuple of them.  The output buffers are never empty: the library is given a
+        non-NULL pointer."""
+        n = self._nbits()
+        bufs = [ctypes.create_string_buffer(max(1, n)) for _ in range(outs)]
+        a, keep = _addr(avail)
+        self._check(fn(self._h, *args, *((a,) if takes_avail else ()), *bufs, *tail))
+        del keep
+        return bufs[0].raw[:n] if outs == 1 else tuple(b.raw[:n] for b in bufs)
 
     def verify(self, avail_bits=None) -> bytes:
-        out = self._bits_out()
-        a, keep = _addr(avail_bits)
-        self._check(self._L.tv_verify(self._h, a, out))
-        del keep
-        return out.raw[: self._nbits()]
+        return self._bits_call(self._L.tv_verify, avail=avail_bits)
 
     def verify_host(self, src, avail_bits=None) -> bytes:
-        out = self._bits_out()
-        a, k1 = _addr(src)
-        b, k2 = _addr(avail_bits)
+        a, keep = _addr(src)
         n = memoryview(src).nbytes if src is not None else 0
-        self._check(self._L.tv_verify_host(self._h, a, n, b, out))
-        del k1, k2
-        return out.raw[: self._nbits()]
+        bits = self._bits_call(self._L.tv_verify_host, a, n, avail=avail_bits)
+        del keep
+        return bits
 
     def verify_list(self, pieces) -> bytes:
         """tv_verify_list: one byte (0/1) per listed global piece index."""
@@ -565,21 +564,12 @@ class Context:
         """tv_v2_stream_file_table: the v2 resume check from the files through the bounded ring (the piece table as for
         v2_stream_begin; file k: lengths[k] bytes at paths[k], file-tree order, each file at its aligned offset).
         -> (bitfield, per-file statuses)."""
-        import numpy as np
-
         pb, tl, h, keep = self._v2_table("v2_stream_file_table", piece_bytes, tree_leaves, hashes)
-        n = len(paths)
-        if len(lengths) != n:
-            raise ValueError("v2_stream_file_table: lengths and paths differ in length")
-        blob = _path_blob("v2_stream_file_table", paths)
-        ln = np.ascontiguousarray(lengths if n else [0], dtype=np.uint64)
-        st = np.zeros(max(1, n), dtype=np.int32)
-        out = self._bits_out()
-        a, keep2 = _addr(avail)
-        self._check(self._L.tv_v2_stream_file_table(self._h, len(pb), pb.ctypes.data, tl.ctypes.data, h, n,
-                                                    ln.ctypes.data, blob, len(blob), a, out, st.ctypes.data))
-        del keep, keep2
-        return out.raw[: self._nbits()], st[:n].tolist()
+        n, ln, blob, st = _file_table("v2_stream_file_table", lengths, paths)
+        bits = self._bits_call(self._L.tv_v2_stream_file_table, len(pb), pb.ctypes.data, tl.ctypes.data, h, n,
+                               ln.ctypes.data, blob, len(blob), avail=avail, tail=(st.ctypes.data,))
+        del keep
+        return bits, st[:n].tolist()
 
     def stream_next(self) -> StreamReq:
         """The next request (req.rows == 0: every byte has been requested)."""
@@ -626,9 +616,7 @@ class Context:
         self._check(self._L.tv_stream_fill_synthetic(self._h, ctypes.byref(req), seed))
 
     def stream_end(self) -> bytes:
-        out = self._bits_out()
-        self._check(self._L.tv_stream_end(self._h, out))
-        return out.raw[: self._nbits()]
+        return self._bits_call(self._L.tv_stream_end, takes_avail=False)
 
     def stream_abort(self) -> None:
         self._check(self._L.tv_stream_abort(self._h))
@@ -649,11 +637,7 @@ class Context:
 
     def v2_verify(self, avail_bits=None) -> bytes:
         """tv_v2_verify: the shard's have-bits (as verify), piece roots against the table's hashes."""
-        out = self._bits_out()
-        a, keep = _addr(avail_bits)
-        self._check(self._L.tv_v2_verify(self._h, a, out))
-        del keep
-        return out.raw[: self._nbits()]
+        return self._bits_call(self._L.tv_v2_verify, avail=avail_bits)
 
     def v2_hash(self) -> bytes:
         """tv_v2_hash: the 32-byte merkle root of every resident piece, in piece order."""
@@ -721,12 +705,8 @@ class Context:
         """tv_hybrid_verify: (bitfield, v1 bits, v2 bits) of the shard: the pad ranges of the resident rows are zeroed,
         then SHA-1 against the digests (set_digests) and the merkle roots against the table's hashes (v2_set_pieces)
         over the same bytes; bitfield = v1 AND v2."""
-        n = self._nbits()
-        out, v1, v2 = (self._bits_out() for _ in range(3))
-        a, keep = _addr(avail_bits)
-        self._check(self._L.tv_hybrid_verify(self._h, a, v1, v2, out))
-        del keep
-        return out.raw[:n], v1.raw[:n], v2.raw[:n]
+        v1, v2, out = self._bits_call(self._L.tv_hybrid_verify, avail=avail_bits, outs=3)
+        return out, v1, v2
 
     def hybrid_hash(self) -> tuple:
         """tv_hybrid_hash: (20-byte SHA-1 digests, 32-byte merkle roots) of every resident piece, in piece order."""

@@ -20,15 +20,14 @@ from __future__ import annotations
 
 import hashlib
 import os
-import time
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
-from . import _native
-from .bencode import bdecode_raw, bencode
-from .metainfo_v2 import FileV2, MetainfoV2, V2Layout, layer_root, make_layout, parse_metainfo_v2, valid_piece_length
-from .v2 import (FileHashV2, _file_paths, _stage_files_v2, collect_files_v2, piece_length_for_v2)
-from .verify import _concat, _devices, _run_shards, _set_bit
+from .bencode import bdecode_raw
+from .metainfo_v2 import FileV2, MetainfoV2, V2Layout, parse_metainfo_v2
+from .v2 import (_creation_layout, _file_hashes, _file_paths, _file_tree, _resident_layout, _source_files,
+                 _stage_file_buffers, _stage_files_v2, _torrent, piece_length_for_v2)
+from .verify import _bits_shards, _hash_shards
 
 CREATED_BY = "torrent_amd make_torrent_hybrid"
 
@@ -142,19 +141,9 @@ def parse_metainfo_hybrid(data) -> Optional[MetainfoHybrid]:
 def _hybrid_layout(ctx, lay: V2Layout, total: int, first: int, count: int, hashes: Optional[bytes],
                    pieces: Optional[bytes], budget: Optional[int]) -> None:
     """set_layout over the v1 space (= the aligned space), the v2 piece table and, for a verify, the v1 digests."""
-    ctx.set_option(_native.TV_OPT_RESIDENT_BUDGET, int(budget or 0))
-    ctx.set_layout(total, lay.piece_length, lay.n_pieces, first, count)
-    if ctx.counter(_native.TV_COUNTER_WINDOW_PIECES):
-        held = ctx.counter(_native.TV_COUNTER_BUDGET)
-        raise MemoryError(f"a hybrid verify needs its shard resident: {count} pieces of {lay.piece_length} bytes exceed "
-                          f"the device budget of {held} bytes (use more devices)")
-    ctx.v2_set_pieces(lay.piece_bytes, lay.tree_leaves, hashes)
+    _resident_layout(ctx, lay, first, count, hashes, budget, total, "a hybrid verify", "use more devices")
     if pieces is not None:
         ctx.set_digests(pieces)
-
-
-def _result(P: int, ranges, slices) -> HybridResult:
-    return HybridResult(*(_concat([s[q] for s in slices], ranges, P) for q in range(3)))
 
 
 def verify_payload_hybrid(meta: MetainfoHybrid, files_bytes: Sequence, devices=None,
@@ -163,31 +152,16 @@ def verify_payload_hybrid(meta: MetainfoHybrid, files_bytes: Sequence, devices=N
     file tree's order; pad files have no buffer).  None, or a buffer shorter than the file, makes exactly the pieces it
     cannot supply unreadable (0 in all three bitfields)."""
     lay = meta.layout
-    P, L = lay.n_pieces, lay.piece_length
     if len(files_bytes) != len(meta.files):
         raise ValueError("verify_payload_hybrid: one buffer per file")
     views = [None if b is None else memoryview(b).cast("B") for b in files_bytes]
+    lengths = [f.length for f in meta.files]
 
     def shard(ctx, first: int, count: int) -> tuple:
         _hybrid_layout(ctx, lay, meta.total_length, first, count, lay.hashes, meta.pieces, budget)
-        avail = bytearray((count + 7) // 8)
-        for j in range(count):
-            i = first + j
-            mv = views[lay.piece_file[i]]
-            if mv is not None and mv.nbytes >= lay.piece_offset[i] + lay.piece_bytes[i]:
-                _set_bit(avail, j)
-        parts = []
-        for k, mv in enumerate(views):
-            n = 0 if mv is None else min(mv.nbytes, meta.files[k].length)
-            if n and lay.file_offset[k] < (first + count) * L and lay.file_offset[k] + n > first * L:
-                parts.append((lay.file_offset[k], mv[:n]))
-        ctx.stage_many(parts)
-        return ctx.hybrid_verify(avail)
+        return ctx.hybrid_verify(_stage_file_buffers(ctx, lay, views, lengths, first, count))
 
-    if P == 0:
-        return HybridResult(bytearray(), bytearray(), bytearray())
-    ranges, slices = _run_shards(_devices(devices), P, shard)
-    return _result(P, ranges, slices)
+    return HybridResult(*_bits_shards(devices, lay.n_pieces, shard, fields=3))
 
 
 def verify_files_hybrid(meta: MetainfoHybrid, dir_path: str, devices=None, threads: Optional[int] = None,
@@ -195,7 +169,6 @@ def verify_files_hybrid(meta: MetainfoHybrid, dir_path: str, devices=None, threa
     """Resume check of a hybrid torrent from disk.  Each real file is staged at its aligned offset (opened read-only);
     pad files are never looked for.  A missing or short file gives 0 bits for exactly the pieces it cannot supply."""
     lay = meta.layout
-    P = lay.n_pieces
     paths = _file_paths(meta.name, meta.files, dir_path)
     lengths = [f.length for f in meta.files]
 
@@ -204,10 +177,7 @@ def verify_files_hybrid(meta: MetainfoHybrid, dir_path: str, devices=None, threa
         _stage_files_v2(ctx, lay, lengths, paths, first, count, threads or ctx.thread_budget)
         return ctx.hybrid_verify()
 
-    if P == 0:
-        return HybridResult(bytearray(), bytearray(), bytearray())
-    ranges, slices = _run_shards(_devices(devices), P, shard)
-    return _result(P, ranges, slices)
+    return HybridResult(*_bits_shards(devices, lay.n_pieces, shard, fields=3))
 
 
 def hash_files_hybrid(dir_path: str, piece_length: int, files: Optional[Sequence[tuple]] = None, devices=None,
@@ -215,37 +185,15 @@ def hash_files_hybrid(dir_path: str, piece_length: int, files: Optional[Sequence
     """Creation mode from disk, both hash sets from one staging (tv_hybrid_hash): (the v1 `pieces` string over the
     padded linear space -- no pad after the last file --, [FileHashV2] as hash_files_v2 returns them).  files:
     [(path components, length)] in file-tree order (default: collect_files_v2).  Raises if a file is missing or short."""
-    if not valid_piece_length(piece_length):
-        raise ValueError("a v2 piece length is a power of two >= 16 KiB")
-    files = collect_files_v2(dir_path) if files is None else list(files)
-    lengths = [n for _, n in files]
-    lay = make_layout(lengths, piece_length)
-    paths = [os.path.join(dir_path, *comps) for comps, _ in files]
-    P = lay.n_pieces
+    files, lengths, lay, paths = _creation_layout(dir_path, piece_length, files)
 
     def shard(ctx, first: int, count: int) -> tuple:
         _hybrid_layout(ctx, lay, lay.total_length, first, count, None, None, budget)
-        status = _stage_files_v2(ctx, lay, lengths, paths, first, count, threads or ctx.thread_budget)
-        if any(st != _native.TV_OK for st in status):
-            raise FileNotFoundError("hash_files_hybrid: a file is missing or shorter than its declared length")
+        _stage_files_v2(ctx, lay, lengths, paths, first, count, threads or ctx.thread_budget, must="hash_files_hybrid")
         return ctx.hybrid_hash()
 
-    pieces = roots = b""
-    if P:
-        _, slices = _run_shards(_devices(devices), P, shard)
-        pieces = b"".join(s[0] for s in slices)
-        roots = b"".join(s[1] for s in slices)
-    out = []
-    for k, (comps, n) in enumerate(files):
-        p0 = lay.file_first_piece[k]
-        layer = roots[32 * p0:32 * (p0 + -(-n // piece_length))]
-        if n == 0:
-            out.append(FileHashV2(list(comps), 0, None, b""))
-        elif n <= piece_length:
-            out.append(FileHashV2(list(comps), n, layer, b""))
-        else:
-            out.append(FileHashV2(list(comps), n, layer_root(layer, piece_length), layer))
-    return pieces, out
+    pieces, roots = _hash_shards(devices, lay.n_pieces, shard, fields=2)
+    return pieces, _file_hashes(files, lay, roots)
 
 
 def make_torrent_hybrid(path: str, tracker: str, comment: Optional[str] = None, creation_date: Optional[int] = None,
@@ -255,23 +203,10 @@ def make_torrent_hybrid(path: str, tracker: str, comment: Optional[str] = None, 
     holds bytes; `length`
     for a single file; `pieces`) and the v2 keys (`meta version` 2, `file tree`), and the top-level `piece layers`.
     Both hash sets come from one staging on the GPU.  Dictionary keys are written sorted (canonical bencoding)."""
-    path = os.path.abspath(path)
-    name = os.path.basename(path)
-    single = not os.path.isdir(path)
-    if single:
-        base, files = os.path.dirname(path), [([name], os.stat(path).st_size)]
-    else:
-        base, files = path, collect_files_v2(path)
+    name, base, files, single = _source_files(path)
     L = piece_length or piece_length_for_v2(sum(n for _, n in files))
     pieces, hashed = hash_files_hybrid(base, L, files=files, devices=devices)
-    tree: dict = {}
-    for fh in hashed:
-        node = tree
-        for comp in fh.path:
-            node = node.setdefault(os.fsencode(comp), {})
-        node[b""] = {"length": fh.length, "pieces root": fh.pieces_root}   # (a None value is not written)
-    layers = {fh.pieces_root: fh.layer for fh in hashed if fh.layer}
-    info: dict = {"file tree": tree}
+    info: dict = {"file tree": _file_tree(hashed)}          # (bencode writes keys in insertion order: keep them sorted)
     if single:
         info["length"] = hashed[0].length
     else:
@@ -283,11 +218,4 @@ def make_torrent_hybrid(path: str, tracker: str, comment: Optional[str] = None, 
                 v1_files.append({"attr": "p", "length": pad, "path": [".pad", str(pad)]})
         info["files"] = v1_files
     info.update({"meta version": 2, "name": name, "piece length": L, "pieces": pieces})
-    return bencode({
-        "announce": tracker,
-        "comment": comment,
-        "created by": CREATED_BY,
-        "creation date": int(time.time()) if creation_date is None else creation_date,
-        "info": info,
-        "piece layers": {k: layers[k] for k in sorted(layers)},
-    })
+    return _torrent(tracker, comment, creation_date, CREATED_BY, info, hashed)

@@ -23,28 +23,24 @@ from __future__ import annotations
 import hashlib
 import os
 import time
-from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional, Sequence
 
 from . import _native
 from .bencode import bencode
 from .metainfo_v2 import LEAF_BYTES, MetainfoV2, V2Layout, layer_root, make_layout, valid_piece_length
-from .storage import copy_bytes
-from .verify import (_PIECE_SLOT, _chunked_map, _concat, _context, _devices, _run_shards, _set_bit, _shard_avail,
-                     _storage_threads)
+from .verify import (_PIECE_SLOT, _bits_shards, _context, _file_options, _hash_shards, _layout, _require_resident,
+                     _safe_paths, _set_bit, _shard_avail, _stream_rows)
 
 CREATED_BY = "torrent_amd make_torrent_v2"
 
 
-def _v2_layout(ctx, lay: V2Layout, first: int, count: int, hashes: Optional[bytes], budget: Optional[int]) -> None:
-    """set_layout over the aligned space + the piece table; raises when the shard does not fit the resident budget."""
-    ctx.set_option(_native.TV_OPT_RESIDENT_BUDGET, int(budget or 0))
-    ctx.set_layout(lay.total_length, lay.piece_length, lay.n_pieces, first, count)
-    if ctx.counter(_native.TV_COUNTER_WINDOW_PIECES):
-        held = ctx.counter(_native.TV_COUNTER_BUDGET)
-        raise MemoryError(f"v2 verify needs its shard resident: {count} pieces of {lay.piece_length} bytes exceed the "
-                          f"device budget of {held} bytes (use more devices, or stream=True to verify through the "
-                          f"bounded ring)")
+def _resident_layout(ctx, lay: V2Layout, first: int, count: int, hashes: Optional[bytes], budget: Optional[int],
+                     total: Optional[int] = None, what: str = "v2 verify",
+                     remedy: str = "use more devices, or stream=True to verify through the bounded ring") -> None:
+    """set_layout over the aligned space (total: a hybrid torrent's v1 length instead) + the piece table; raises when the
+    shard does not fit the resident budget."""
+    _layout(ctx, lay.total_length if total is None else total, lay.piece_length, lay.n_pieces, first, count, budget)
+    _require_resident(ctx, what, count, lay.piece_length, remedy)
     ctx.v2_set_pieces(lay.piece_bytes, lay.tree_leaves, hashes)
 
 
@@ -54,17 +50,6 @@ def _file_paths(meta_name: str, files: Sequence, dir_path: str) -> List[str]:
     if len(files) == 1 and list(files[0].path) == [meta_name]:
         return [os.path.join(dir_path, meta_name)]
     return [os.path.join(dir_path, *f.path) for f in files]
-
-
-def _v2_stream_layout(ctx, lay: V2Layout, first: int, count: int, budget: Optional[int], chunk: int) -> None:
-    """The layout of a streamed v2 check: no resident payload; the geometry comes from the budget or the chunk."""
-    ctx.set_option(_native.TV_OPT_RESIDENT, 0)
-    try:
-        ctx.set_option(_native.TV_OPT_RESIDENT_BUDGET, int(budget or 0))
-        ctx.set_option(_native.TV_OPT_STREAM_CHUNK, int(chunk or 0))
-        ctx.set_layout(lay.total_length, lay.piece_length, lay.n_pieces, first, count)
-    finally:
-        ctx.set_option(_native.TV_OPT_RESIDENT, 1)
 
 
 def verify_stream_v2(meta: MetainfoV2, read, devices=None, avail: Optional[bytes] = None, chunk: int = 0,
@@ -78,48 +63,36 @@ def verify_stream_v2(meta: MetainfoV2, read, devices=None, avail: Optional[bytes
     for columns of C bytes (a power of two >= 16 KiB) across the whole shard.  The reads of a request are in flight
     together on `threads` threads, each writing its own row of the slot (as verify_stream)."""
     lay = meta.layout
-    P = lay.n_pieces
 
     def shard(ctx, first: int, count: int) -> bytes:
-        _v2_stream_layout(ctx, lay, first, count, budget, chunk)
-        nthr = _storage_threads(ctx, threads)
-        pool = ThreadPoolExecutor(nthr) if nthr > 1 else None
-        try:
-            ctx.v2_stream_begin(lay.piece_bytes, lay.tree_leaves, lay.hashes, _shard_avail(avail, first, count))
-            while True:
-                req = ctx.stream_next()
-                if not req.rows:
-                    break
+        # no resident payload; the geometry comes from the budget or the chunk
+        _layout(ctx, lay.total_length, lay.piece_length, lay.n_pieces, first, count, budget, resident=False, chunk=chunk)
+        return _stream_rows(
+            ctx, threads, lambda i, offset, n: read(lay.piece_file[i], lay.piece_offset[i] + offset, n),
+            lambda: ctx.v2_stream_begin(lay.piece_bytes, lay.tree_leaves, lay.hashes, _shard_avail(avail, first, count)))
 
-                def fill(q: int, req=req):
-                    """Row q into the slot; returns the piece index when it is unreadable."""
-                    n = ctx.row_bytes(req, q)
-                    if n == 0:
-                        return None
-                    i = req.piece + q
-                    data = read(lay.piece_file[i], lay.piece_offset[i] + req.offset, n)
-                    if data is None or len(data) != n:
-                        return i
-                    copy_bytes(req.slot + q * req.width, data, n)
-                    return None
+    return _bits_shards(devices, lay.n_pieces, shard)
 
-                for i in _chunked_map(pool, fill, req.rows, nthr):
-                    if i is not None:
-                        ctx.stream_unreadable(i)
-                ctx.stream_commit(req)
-            return ctx.stream_end()
-        except BaseException:
-            ctx.stream_abort()
-            raise
-        finally:
-            if pool is not None:
-                pool.shutdown()
-            ctx.set_option(_native.TV_OPT_STREAM_CHUNK, 0)
 
-    if P == 0:
-        return bytearray()
-    ranges, slices = _run_shards(_devices(devices), P, shard)
-    return _concat(slices, ranges, P)
+def _stage_file_buffers(ctx, lay: V2Layout, views: Sequence, lengths: Sequence[int], first: int,
+                        count: int) -> bytearray:
+    """Stage the files held in host memory (views[k]: file k's bytes, or None) that meet the shard, each at its aligned
+    offset (the library keeps the shard's part); bytes past a file's declared length are not staged.  -> the shard's
+    availability bits: the pieces whose bytes are all there."""
+    L = lay.piece_length
+    avail = bytearray((count + 7) // 8)
+    for j in range(count):
+        i = first + j
+        mv = views[lay.piece_file[i]]
+        if mv is not None and mv.nbytes >= lay.piece_offset[i] + lay.piece_bytes[i]:
+            _set_bit(avail, j)
+    parts = []
+    for k, mv in enumerate(views):
+        n = 0 if mv is None else min(mv.nbytes, lengths[k])
+        if n and lay.file_offset[k] < (first + count) * L and lay.file_offset[k] + n > first * L:
+            parts.append((lay.file_offset[k], mv[:n]))
+    ctx.stage_many(parts)
+    return avail
 
 
 def verify_payload_v2(meta: MetainfoV2, files_bytes: Sequence, devices=None, budget: Optional[int] = None,
@@ -129,7 +102,6 @@ def verify_payload_v2(meta: MetainfoV2, files_bytes: Sequence, devices=None, bud
     stream=True verifies through the bounded ring (verify_stream_v2 reading the buffers) and never raises for size;
     the default needs every shard resident within the budget."""
     lay = meta.layout
-    P, L = lay.n_pieces, lay.piece_length
     if len(files_bytes) != len(meta.files):
         raise ValueError("verify_payload_v2: one buffer per file")
     views = [None if b is None else memoryview(b).cast("B") for b in files_bytes]
@@ -139,51 +111,37 @@ def verify_payload_v2(meta: MetainfoV2, files_bytes: Sequence, devices=None, bud
             return None if mv is None or mv.nbytes < offset + n else mv[offset:offset + n]
 
         return verify_stream_v2(meta, read, devices=devices, budget=budget)
+    lengths = [f.length for f in meta.files]
 
     def shard(ctx, first: int, count: int) -> bytes:
-        _v2_layout(ctx, lay, first, count, lay.hashes, budget)
-        avail = bytearray((count + 7) // 8)
-        for j in range(count):
-            i = first + j
-            mv = views[lay.piece_file[i]]
-            if mv is not None and mv.nbytes >= lay.piece_offset[i] + lay.piece_bytes[i]:
-                _set_bit(avail, j)
-        # each file at its aligned offset (the library keeps the shard's part); bytes past a file's declared length
-        # are not staged
-        parts = []
-        for k, mv in enumerate(views):
-            n = 0 if mv is None else min(mv.nbytes, meta.files[k].length)
-            if n and lay.file_offset[k] < (first + count) * L and lay.file_offset[k] + n > first * L:
-                parts.append((lay.file_offset[k], mv[:n]))
-        ctx.stage_many(parts)
-        return ctx.v2_verify(avail)
+        _resident_layout(ctx, lay, first, count, lay.hashes, budget)
+        return ctx.v2_verify(_stage_file_buffers(ctx, lay, views, lengths, first, count))
 
-    if P == 0:
-        return bytearray()
-    ranges, slices = _run_shards(_devices(devices), P, shard)
-    return _concat(slices, ranges, P)
+    return _bits_shards(devices, lay.n_pieces, shard)
 
 
 def _stage_files_v2(ctx, lay: V2Layout, lengths: Sequence[int], paths: Sequence[str], first: int, count: int,
-                    threads: int) -> list:
+                    threads: int, must: Optional[str] = None) -> None:
     """One tv_stage_files segment per file that meets the shard, at its aligned offset, opened read-only.  The library
-    marks the pieces a missing or short file cannot supply.  -> the per-segment statuses."""
+    marks the pieces a missing or short file cannot supply; must="<the caller>": creation mode, where one is an error."""
     L = lay.piece_length
     lo, hi = first * L, (first + count) * L
+    safe = _safe_paths(paths)
     seg_paths, foff, lin, nbytes = [], [], [], []
     for k, n in enumerate(lengths):
         a, b = max(lo, lay.file_offset[k]), min(hi, lay.file_offset[k] + n)
         if b > a:
-            seg_paths.append(paths[k] if "\0" not in paths[k] else "")
+            seg_paths.append(safe[k])
             foff.append(a - lay.file_offset[k])
             lin.append(a)
             nbytes.append(b - a)
-    ctx.set_option(_native.TV_OPT_FILE_THREADS, max(1, threads))
-    ctx.set_option(_native.TV_OPT_OPEN_RW, 0)          # a verify writes nothing: read-only
+    _file_options(ctx, threads, False)          # a verify writes nothing: read-only
     try:
-        return ctx.stage_files(seg_paths, foff, lin, nbytes)
+        status = ctx.stage_files(seg_paths, foff, lin, nbytes)
     finally:
         ctx.set_option(_native.TV_OPT_OPEN_RW, 1)
+    if must and any(st != _native.TV_OK for st in status):
+        raise FileNotFoundError(f"{must}: a file is missing or shorter than its declared length")
 
 
 def verify_files_v2(meta: MetainfoV2, dir_path: str, devices=None, threads: Optional[int] = None,
@@ -193,31 +151,25 @@ def verify_files_v2(meta: MetainfoV2, dir_path: str, devices=None, threads: Opti
     stream=True reads the files through the bounded ring in the library's own threads (tv_v2_stream_file_table, files
     opened read-only) and never raises for size; the default needs every shard resident within the budget."""
     lay = meta.layout
-    P = lay.n_pieces
     paths = _file_paths(meta.name, meta.files, dir_path)
     lengths = [f.length for f in meta.files]
 
     def stream_shard(ctx, first: int, count: int) -> bytes:
-        _v2_stream_layout(ctx, lay, first, count, budget, 0)
-        ctx.set_option(_native.TV_OPT_FILE_THREADS, max(1, threads or ctx.thread_budget))
-        ctx.set_option(_native.TV_OPT_OPEN_RW, 0)          # a verify writes nothing: read-only
+        _layout(ctx, lay.total_length, lay.piece_length, lay.n_pieces, first, count, budget, resident=False)
+        _file_options(ctx, threads or ctx.thread_budget, False)          # a verify writes nothing: read-only
         try:
-            safe = [p if "\0" not in p else "" for p in paths]
-            return ctx.v2_stream_file_table(lay.piece_bytes, lay.tree_leaves, lay.hashes, lengths, safe)[0]
+            return ctx.v2_stream_file_table(lay.piece_bytes, lay.tree_leaves, lay.hashes, lengths, _safe_paths(paths))[0]
         finally:
             ctx.set_option(_native.TV_OPT_OPEN_RW, 1)
 
     def shard(ctx, first: int, count: int) -> bytes:
         if stream:
             return stream_shard(ctx, first, count)
-        _v2_layout(ctx, lay, first, count, lay.hashes, budget)
+        _resident_layout(ctx, lay, first, count, lay.hashes, budget)
         _stage_files_v2(ctx, lay, lengths, paths, first, count, threads or ctx.thread_budget)
         return ctx.v2_verify()
 
-    if P == 0:
-        return bytearray()
-    ranges, slices = _run_shards(_devices(devices), P, shard)
-    return _concat(slices, ranges, P)
+    return _bits_shards(devices, lay.n_pieces, shard)
 
 
 def verify_piece_v2(meta: MetainfoV2, index: int, data) -> bool:
@@ -230,8 +182,7 @@ def verify_piece_v2(meta: MetainfoV2, index: int, data) -> bool:
     if n != lay.piece_bytes[index]:
         return False
     with _context(0, _PIECE_SLOT) as ctx:      # its own context: never evicts a bulk call's payload
-        ctx.set_option(_native.TV_OPT_RESIDENT_BUDGET, 0)
-        ctx.set_layout(n, lay.piece_length, 1, 0, 1)
+        _layout(ctx, n, lay.piece_length, 1, 0, 1, None)
         ctx.v2_set_pieces([n], [lay.tree_leaves[index]], lay.hashes[32 * index:32 * index + 32])
         ctx.stage(0, data)
         return bool(ctx.v2_verify()[0] & 0x80)
@@ -257,43 +208,47 @@ def collect_files_v2(dir_path: str) -> List[tuple]:
     return out
 
 
-def hash_files_v2(dir_path: str, piece_length: int, files: Optional[Sequence[tuple]] = None, devices=None,
-                  threads: Optional[int] = None, budget: Optional[int] = None) -> List[FileHashV2]:
-    """Creation mode from disk: the pieces root and piece layer of every file (files: [(path components, length)] in
-    file-tree order; default: collect_files_v2(dir_path)).  The GPU emits the piece roots (tv_v2_hash); the host
-    reduces each longer file's layer to its pieces root with hashlib (P - 1 small hashes).  Raises if a file is
-    missing or short.  Files are opened read-only."""
+def _creation_layout(dir_path: str, piece_length: int, files: Optional[Sequence[tuple]]) -> tuple:
+    """(files, their lengths, the piece table, their paths under dir_path) of a creation call; files: [(path components,
+    length)] in file-tree order (default: collect_files_v2(dir_path))."""
     if not valid_piece_length(piece_length):
         raise ValueError("a v2 piece length is a power of two >= 16 KiB")
     files = collect_files_v2(dir_path) if files is None else list(files)
     lengths = [n for _, n in files]
-    lay = make_layout(lengths, piece_length)
-    paths = [os.path.join(dir_path, *comps) for comps, _ in files]
-    P = lay.n_pieces
+    return files, lengths, make_layout(lengths, piece_length), [os.path.join(dir_path, *comps) for comps, _ in files]
 
-    def shard(ctx, first: int, count: int) -> bytes:
-        _v2_layout(ctx, lay, first, count, None, budget)
-        status = _stage_files_v2(ctx, lay, lengths, paths, first, count, threads or ctx.thread_budget)
-        if any(st != _native.TV_OK for st in status):
-            raise FileNotFoundError("hash_files_v2: a file is missing or shorter than its declared length")
-        return ctx.v2_hash()
 
-    roots = b""
-    if P:
-        _, slices = _run_shards(_devices(devices), P, shard)
-        roots = b"".join(slices)
+def _file_hashes(files: Sequence[tuple], lay: V2Layout, roots: bytes) -> List[FileHashV2]:
+    """Every file's pieces root and piece layer from the piece roots of the whole layout (32 bytes per piece): the host
+    reduces a longer file's layer to its pieces root with hashlib (P - 1 small hashes)."""
+    L = lay.piece_length
     out = []
     for k, (comps, n) in enumerate(files):
         p0 = lay.file_first_piece[k]
-        count = -(-n // piece_length)
-        layer = roots[32 * p0:32 * (p0 + count)]
+        layer = roots[32 * p0:32 * (p0 + -(-n // L))]
         if n == 0:
             out.append(FileHashV2(list(comps), 0, None, b""))
-        elif n <= piece_length:
+        elif n <= L:
             out.append(FileHashV2(list(comps), n, layer, b""))
         else:
-            out.append(FileHashV2(list(comps), n, layer_root(layer, piece_length), layer))
+            out.append(FileHashV2(list(comps), n, layer_root(layer, L), layer))
     return out
+
+
+def hash_files_v2(dir_path: str, piece_length: int, files: Optional[Sequence[tuple]] = None, devices=None,
+                  threads: Optional[int] = None, budget: Optional[int] = None) -> List[FileHashV2]:
+    """Creation mode from disk: the pieces root and piece layer of every file (files: [(path components, length)] in
+    file-tree order; default: collect_files_v2(dir_path)).  The GPU emits the piece roots (tv_v2_hash); the host
+    reduces each longer file's layer to its pieces root (_file_hashes).  Raises if a file is missing or short.  Files
+    are opened read-only."""
+    files, lengths, lay, paths = _creation_layout(dir_path, piece_length, files)
+
+    def shard(ctx, first: int, count: int) -> bytes:
+        _resident_layout(ctx, lay, first, count, None, budget)
+        _stage_files_v2(ctx, lay, lengths, paths, first, count, threads or ctx.thread_budget, must="hash_files_v2")
+        return ctx.v2_hash()
+
+    return _file_hashes(files, lay, _hash_shards(devices, lay.n_pieces, shard))
 
 
 def piece_length_for_v2(size: int) -> int:
@@ -304,33 +259,48 @@ def piece_length_for_v2(size: int) -> int:
     return L
 
 
-def make_torrent_v2(path: str, tracker: str, comment: Optional[str] = None, creation_date: Optional[int] = None,
-                    piece_length: Optional[int] = None, devices=None) -> bytes:
-    """A v2-only .torrent (meta version 2: `file tree` + `piece layers`) for a file or a directory, piece roots hashed
-    on the GPU.  Dictionary keys are written sorted, so the file is canonical bencoding."""
+def _source_files(path: str) -> tuple:
+    """(name, directory, [(path components, length)], whether it is a single file) of what a .torrent is made for."""
     path = os.path.abspath(path)
     name = os.path.basename(path)
     if os.path.isdir(path):
-        base, files = path, collect_files_v2(path)
-    else:
-        base, files = os.path.dirname(path), [([name], os.stat(path).st_size)]
-    L = piece_length or piece_length_for_v2(sum(n for _, n in files))
-    hashed = hash_files_v2(base, L, files=files, devices=devices)
+        return name, path, collect_files_v2(path), False
+    return name, os.path.dirname(path), [([name], os.stat(path).st_size)], True
+
+
+def _file_tree(hashed: Sequence[FileHashV2]) -> dict:
     tree: dict = {}
     for fh in hashed:
         node = tree
         for comp in fh.path:
             node = node.setdefault(os.fsencode(comp), {})
         node[b""] = {"length": fh.length, "pieces root": fh.pieces_root}   # (a None value is not written)
+    return tree
+
+
+def _torrent(tracker: str, comment: Optional[str], creation_date: Optional[int], created_by: str, info: dict,
+             hashed: Sequence[FileHashV2]) -> bytes:
+    """The bencoded .torrent around `info`, with the `piece layers` of the files longer than a piece."""
     layers = {fh.pieces_root: fh.layer for fh in hashed if fh.layer}
     return bencode({
         "announce": tracker,
         "comment": comment,
-        "created by": CREATED_BY,
+        "created by": created_by,
         "creation date": int(time.time()) if creation_date is None else creation_date,
-        "info": {"file tree": tree, "meta version": 2, "name": name, "piece length": L},
+        "info": info,
         "piece layers": {k: layers[k] for k in sorted(layers)},
     })
+
+
+def make_torrent_v2(path: str, tracker: str, comment: Optional[str] = None, creation_date: Optional[int] = None,
+                    piece_length: Optional[int] = None, devices=None) -> bytes:
+    """A v2-only .torrent (meta version 2: `file tree` + `piece layers`) for a file or a directory, piece roots hashed
+    on the GPU.  Dictionary keys are written sorted, so the file is canonical bencoding."""
+    name, base, files, _ = _source_files(path)
+    L = piece_length or piece_length_for_v2(sum(n for _, n in files))
+    hashed = hash_files_v2(base, L, files=files, devices=devices)
+    info = {"file tree": _file_tree(hashed), "meta version": 2, "name": name, "piece length": L}
+    return _torrent(tracker, comment, creation_date, CREATED_BY, info, hashed)
 
 
 def info_hash_v2(torrent: bytes) -> bytes:

@@ -135,11 +135,57 @@ def _devices(devices) -> List[int]:
     return list(devices)
 
 
-def _layout(ctx, info_or_len, L: int, P: int, first: int, count: int, budget: Optional[int]) -> None:
-    """set_layout with this call's device budget (the contexts are cached: every call sets its own)."""
-    ctx.set_option(_native.TV_OPT_RESIDENT_BUDGET, int(budget or 0))
-    total = info_or_len if isinstance(info_or_len, int) else info_or_len.length
-    ctx.set_layout(total, L, P, first, count)
+def _layout(ctx, total: int, L: int, P: int, first: int, count: int, budget: Optional[int], *, resident: bool = True,
+            chunk: int = 0, rows: int = 0, digests: Optional[bytes] = None) -> None:
+    """set_layout with every option it depends on (the contexts are cached: every call sets its own, never relying on
+    what the call before left).  budget: this call's device budget.  resident=False: a streamed layout, without a
+    resident payload, its geometry from the budget, `chunk` (TV_OPT_STREAM_CHUNK) and `rows` (TV_OPT_STREAM_ROWS); the
+    option is on again when this returns, whatever happens, so a tool that takes the cached context and calls it
+    directly gets a resident payload.  A resident layout reads neither stream option.  digests: the v1 digests of a
+    streamed check, set before the resident option is restored."""
+    ctx.set_option(_native.TV_OPT_RESIDENT, 1 if resident else 0)
+    try:
+        ctx.set_option(_native.TV_OPT_RESIDENT_BUDGET, int(budget or 0))
+        if not resident:
+            ctx.set_option(_native.TV_OPT_STREAM_CHUNK, int(chunk or 0))
+            ctx.set_option(_native.TV_OPT_STREAM_ROWS, rows)
+        ctx.set_layout(total, L, P, first, count)
+        if digests is not None:
+            ctx.set_digests(digests)
+    finally:
+        if not resident:
+            ctx.set_option(_native.TV_OPT_RESIDENT, 1)
+
+
+def _require_resident(ctx, what: str, count: int, L: int, remedy: str = "use more devices") -> None:
+    """Raise unless the layout just set holds its whole shard (the v2 and hybrid calls have no windowed form)."""
+    if ctx.counter(_native.TV_COUNTER_WINDOW_PIECES):
+        held = ctx.counter(_native.TV_COUNTER_BUDGET)
+        raise MemoryError(f"{what} needs its shard resident: {count} pieces of {L} bytes exceed the device budget of "
+                          f"{held} bytes ({remedy})")
+
+
+def _file_options(ctx, threads: int, open_rw: bool, direct_min: Optional[int] = None) -> None:
+    """Every option a file-reading call depends on (as _layout: each call sets its own): the library's reader threads,
+    whether files are opened read + write (as fsStorage.get opens them) or read-only, and the length from which a
+    segment is DMA'd from the page cache (default _DIRECT_MIN_BYTES)."""
+    ctx.set_option(_native.TV_OPT_FILE_THREADS, max(1, threads))
+    ctx.set_option(_native.TV_OPT_OPEN_RW, 1 if open_rw else 0)
+    ctx.set_option(_native.TV_OPT_FILE_DIRECT_MIN, _DIRECT_MIN_BYTES if direct_min is None else direct_min)
+
+
+def _safe_paths(paths) -> List[str]:
+    """A path holding a NUL cannot be opened (Deno.open throws, so fsStorage.get's piece is null, storage.ts:157-170):
+    it goes as "", which the library cannot open either (ts/verify.ts does the same)."""
+    return [p if "\0" not in p else "" for p in paths]
+
+
+def _all_ones(count: int) -> bytearray:
+    """A shard bitfield with every piece's bit set (the spare bits of the last byte 0)."""
+    bits = bytearray(b"\xff" * ((count + 7) // 8))
+    if count % 8:
+        bits[-1] = (0xFF00 >> (count % 8)) & 0xFF
+    return bits
 
 
 def _batch_buffers(ctx, nbytes: int) -> list:
@@ -202,6 +248,21 @@ def _run_shards(devs: List[int], n_pieces: int, fn):
         return ranges, [f.result() for f in futs]
 
 
+def _bits_shards(devices, P: int, shard, fields: int = 1, join=_concat):
+    """The have-bitfield of a bulk call: shard(ctx, first, count) -> the shard's bits, on every shard (_run_shards; none
+    when there are no pieces), each slice at its place.  fields > 1: shard returns that many bitfields (hybrid_verify's
+    three), and so does this; an empty shard (b"" from _run_shards) is empty in each."""
+    ranges, slices = _run_shards(_devices(devices), P, shard) if P else ((), ())
+    if fields == 1:
+        return join(slices, ranges, P)
+    return tuple(join([s and s[q] for s in slices], ranges, P) for q in range(fields))
+
+
+def _hash_shards(devices, P: int, shard, fields: int = 1):
+    """Creation mode: shard(ctx, first, count) -> the shard's digests (hybrid_hash: fields=2), joined in piece order."""
+    return _bits_shards(devices, P, shard, fields, lambda slices, ranges, P: b"".join(slices))
+
+
 # Python reader threads of the Storage paths (verify_pieces, verify_stream): each Storage.get is Python work under
 # the GIL around its open / pread / copy, so past a few threads they contend more than they overlap -- 4 was the
 # fastest or within noise of it on cfg3's 10,000 files and on 16 GiB in one and in 64 files, warm, for both paths
@@ -231,7 +292,7 @@ def verify_pieces(info: InfoDict, storage, devices=None, threads: Optional[int] 
     P, L = info.n_pieces, info.piece_length
 
     def shard(ctx, first: int, count: int) -> bytes:
-        _layout(ctx, info, L, P, first, count, budget)
+        _layout(ctx, info.length, L, P, first, count, budget)
         ctx.set_digests(info.pieces_raw)
         avail = bytearray((count + 7) // 8)
         per_batch = max(1, min(count, _STAGE_BATCH_BYTES // max(1, L)))
@@ -274,10 +335,7 @@ def verify_pieces(info: InfoDict, storage, devices=None, threads: Optional[int] 
                     staging.result()
         return ctx.verify(avail)
 
-    if P == 0:
-        return bytearray()
-    ranges, slices = _run_shards(_devices(devices), P, shard)
-    return _concat(slices, ranges, P)
+    return _bits_shards(devices, P, shard)
 
 
 def verify_payload(info: InfoDict, payload, devices=None, resident: Optional[bool] = None,
@@ -293,12 +351,8 @@ def verify_payload(info: InfoDict, payload, devices=None, resident: Optional[boo
 
     def shard(ctx, first: int, count: int) -> bytes:
         streamed = resident is False or (resident is None and _exceeds(L, count, budget))
-        if streamed:            # the streamed path needs no resident payload (tv_verify_host)
-            ctx.set_option(_native.TV_OPT_RESIDENT, 0)
-        try:
-            _layout(ctx, info, L, P, first, count, budget)
-        finally:
-            ctx.set_option(_native.TV_OPT_RESIDENT, 1)
+        # (the streamed path needs no resident payload: tv_verify_host)
+        _layout(ctx, info.length, L, P, first, count, budget, resident=not streamed)
         ctx.set_digests(info.pieces_raw)
         av = _shard_avail(avail, first, count)
         lo = min(first * L, len(mv))
@@ -317,10 +371,7 @@ def verify_payload(info: InfoDict, payload, devices=None, resident: Optional[boo
             return ctx.verify(have)
         return ctx.verify_host(mv[lo:hi] if hi > lo else b"", av)
 
-    if P == 0:
-        return bytearray()
-    ranges, slices = _run_shards(_devices(devices), P, shard)
-    return _concat(slices, ranges, P)
+    return _bits_shards(devices, P, shard)
 
 
 def _shard_avail(avail: Optional[bytes], first: int, count: int) -> Optional[bytearray]:
@@ -352,56 +403,55 @@ def verify_stream(info: InfoDict, read, devices=None, avail: Optional[bytes] = N
     P, L = info.n_pieces, info.piece_length
 
     def shard(ctx, first: int, count: int) -> bytes:
-        ctx.set_option(_native.TV_OPT_RESIDENT, 0)       # no resident payload for a streamed check
-        try:
-            # (a budget an earlier call left on the cached context would cap the row windows: ADVICE r04)
-            ctx.set_option(_native.TV_OPT_RESIDENT_BUDGET, 0)
-            ctx.set_option(_native.TV_OPT_STREAM_CHUNK, chunk)
-            ctx.set_option(_native.TV_OPT_STREAM_ROWS, 0 if chunk else 1)
-            ctx.set_layout(info.length, L, P, first, count)
-            ctx.set_digests(info.pieces_raw)
-        finally:
-            ctx.set_option(_native.TV_OPT_RESIDENT, 1)
-        ctx.stream_begin(_shard_avail(avail, first, count))
-        nthr = _storage_threads(ctx, threads)
-        pool = ThreadPoolExecutor(nthr) if nthr > 1 else None
-        try:
-            while True:
-                req = ctx.stream_next()
-                if not req.rows:
-                    break
+        # (budget 0: one an earlier call left on the cached context would cap the row windows)
+        _layout(ctx, info.length, L, P, first, count, 0, resident=False, chunk=chunk, rows=0 if chunk else 1,
+                digests=info.pieces_raw)
+        return _stream_rows(ctx, threads, lambda i, offset, n: read(i * L + offset, n),
+                            lambda: ctx.stream_begin(_shard_avail(avail, first, count)))
 
-                def fill(q: int, req=req):
-                    """Row q into the slot (copied by this reader thread, without the GIL); returns the piece
-                    index when it is unreadable."""
-                    n = ctx.row_bytes(req, q)
-                    if n == 0:
-                        return None
-                    i = req.piece + q
-                    data = read(i * L + req.offset, n)
-                    if data is None or len(data) != n:
-                        return i
-                    copy_bytes(req.slot + q * req.width, data, n)
+    return _bits_shards(devices, P, shard)
+
+
+def _stream_rows(ctx, threads: Optional[int], read_row, begin) -> bytes:
+    """The ring loop of a streamed check, after its layout: begin() opens the stream, then every request's rows are
+    read -- read_row(i, offset, n) -> the n bytes of piece i from `offset`, or None -- on `threads` threads
+    (_storage_threads), each copying its row into the slot itself, without the GIL.  A row that is None or short makes
+    its piece unreadable.  -> the shard's bits.  Any exception ends the stream (stream_abort); either way the stream
+    options are back at their defaults afterwards."""
+    nthr = _storage_threads(ctx, threads)
+    pool = ThreadPoolExecutor(nthr) if nthr > 1 else None
+    try:
+        begin()
+        while True:
+            req = ctx.stream_next()
+            if not req.rows:
+                break
+
+            def fill(q: int, req=req):
+                """Row q into the slot; returns the piece index when it is unreadable."""
+                n = ctx.row_bytes(req, q)
+                if n == 0:
                     return None
+                i = req.piece + q
+                data = read_row(i, req.offset, n)
+                if data is None or len(data) != n:
+                    return i
+                copy_bytes(req.slot + q * req.width, data, n)
+                return None
 
-                for i in _chunked_map(pool, fill, req.rows, nthr):
-                    if i is not None:
-                        ctx.stream_unreadable(i)
-                ctx.stream_commit(req)
-            return ctx.stream_end()
-        except BaseException:
-            ctx.stream_abort()
-            raise
-        finally:
-            if pool is not None:
-                pool.shutdown()
-            ctx.set_option(_native.TV_OPT_STREAM_CHUNK, 0)
-            ctx.set_option(_native.TV_OPT_STREAM_ROWS, 0)
-
-    if P == 0:
-        return bytearray()
-    ranges, slices = _run_shards(_devices(devices), P, shard)
-    return _concat(slices, ranges, P)
+            for i in _chunked_map(pool, fill, req.rows, nthr):
+                if i is not None:
+                    ctx.stream_unreadable(i)
+            ctx.stream_commit(req)
+        return ctx.stream_end()
+    except BaseException:
+        ctx.stream_abort()
+        raise
+    finally:
+        if pool is not None:
+            pool.shutdown()
+        ctx.set_option(_native.TV_OPT_STREAM_CHUNK, 0)
+        ctx.set_option(_native.TV_OPT_STREAM_ROWS, 0)
 
 
 def _files_shard(ctx, info: InfoDict, storage, first: int, count: int, threads: int = 16,
@@ -421,9 +471,7 @@ def _files_shard(ctx, info: InfoDict, storage, first: int, count: int, threads: 
     read + write as fsStorage.get opens them (storage.ts:28-32,158); False opens them read-only, as
     make_torrent.ts:78 opens its sources (hash_files)."""
     L = info.piece_length
-    avail = bytearray(b"\xff" * ((count + 7) // 8))
-    if count % 8:
-        avail[-1] = (0xFF00 >> (count % 8)) & 0xFF
+    avail = _all_ones(count)
 
     def clear(j_lo: int, j_hi: int) -> None:   # shard-relative pieces [j_lo, j_hi] unreadable
         for j in range(max(0, j_lo), min(count - 1, j_hi) + 1):
@@ -455,12 +503,8 @@ def _files_shard(ctx, info: InfoDict, storage, first: int, count: int, threads: 
         nbytes = np.concatenate([nbytes, np.zeros(len(zk), np.int64)])
     if len(k) == 0:
         return avail
-    # a path holding a NUL cannot be opened (Deno.open throws, so fsStorage.get's piece is null, storage.ts:157-170):
-    # it goes as "", which the library cannot open either (ts/verify.ts does the same)
-    paths = [p if "\0" not in p else "" for p in storage.file_paths()]
-    ctx.set_option(_native.TV_OPT_FILE_THREADS, max(1, threads))
-    ctx.set_option(_native.TV_OPT_OPEN_RW, 1 if open_rw else 0)
-    ctx.set_option(_native.TV_OPT_FILE_DIRECT_MIN, _DIRECT_MIN_BYTES if direct_min is None else direct_min)
+    paths = _safe_paths(storage.file_paths())
+    _file_options(ctx, threads, open_rw, direct_min)
     # a failed segment's pieces are marked inside the library (tv_verify reports them 0): from the piece
     # holding its first unreadable byte on, as Storage.get reads piece by piece; the statuses are informational
     status = ctx.stage_files([paths[i] for i in k.tolist()], foff, lin, nbytes)
@@ -489,25 +533,12 @@ def _stream_files_shard(ctx, info: InfoDict, storage, first: int, count: int, th
     """A shard's resume check from its files through the bounded ring (tv_stream_file_table): no resident payload,
     two device chunk buffers within the budget (columns of windows of >= 2,048 pieces), the library's readers filling
     each column from the file table."""
-    L, P = info.piece_length, info.n_pieces
-    ctx.set_option(_native.TV_OPT_RESIDENT, 0)
-    try:
-        # the library sizes windows x columns to the budget (tv_stream_file_table)
-        ctx.set_option(_native.TV_OPT_RESIDENT_BUDGET, int(budget or 0))
-        ctx.set_option(_native.TV_OPT_STREAM_CHUNK, 0)
-        ctx.set_option(_native.TV_OPT_STREAM_ROWS, 0)
-        ctx.set_layout(info.length, L, P, first, count)
-        ctx.set_digests(info.pieces_raw)
-    finally:
-        ctx.set_option(_native.TV_OPT_RESIDENT, 1)
-    if count == 0:
-        return b""
-    ctx.set_option(_native.TV_OPT_FILE_THREADS, max(1, threads))
-    ctx.set_option(_native.TV_OPT_OPEN_RW, 1)
+    # the library sizes windows x columns to the budget (tv_stream_file_table)
+    _layout(ctx, info.length, info.piece_length, info.n_pieces, first, count, budget, resident=False,
+            digests=info.pieces_raw)
+    _file_options(ctx, threads, True)
     lengths = [info.length] if info.files is None else [f.length for f in info.files]
-    paths = [p if "\0" not in p else "" for p in storage.file_paths()]
-    bits, _ = ctx.stream_file_table(lengths, paths)
-    return bits
+    return ctx.stream_file_table(lengths, _safe_paths(storage.file_paths()))[0]
 
 
 def verify_files(info: InfoDict, dir_path: str, devices=None, threads: Optional[int] = None,
@@ -532,16 +563,11 @@ def verify_files(info: InfoDict, dir_path: str, devices=None, threads: Optional[
     def shard(ctx, first: int, count: int) -> bytes:
         if stream or (stream is None and _stream_wins(L, count, budget)):
             return _stream_files_shard(ctx, info, storage, first, count, threads or ctx.thread_budget, budget)
-        _layout(ctx, info, L, P, first, count, budget)
+        _layout(ctx, info.length, L, P, first, count, budget)
         ctx.set_digests(info.pieces_raw)
-        if count == 0:
-            return b""
         return ctx.verify(_files_shard(ctx, info, storage, first, count, threads or ctx.thread_budget, direct_min))
 
-    if P == 0:
-        return bytearray()
-    ranges, slices = _run_shards(_devices(devices), P, shard)
-    return _concat(slices, ranges, P)
+    return _bits_shards(devices, P, shard)
 
 
 def hash_files(info: InfoDict, dir_path: str, devices=None, threads: Optional[int] = None,
@@ -556,23 +582,15 @@ def hash_files(info: InfoDict, dir_path: str, devices=None, threads: Optional[in
     storage = Storage(fs_storage, info, dir_path)
 
     def shard(ctx, first: int, count: int) -> bytes:
-        _layout(ctx, info, L, P, first, count, budget)
-        if count == 0:
-            return b""
+        _layout(ctx, info.length, L, P, first, count, budget)
         status: list = []
         avail = _files_shard(ctx, info, storage, first, count, threads or ctx.thread_budget, direct_min, status,
                              open_rw=False)
-        full = bytearray(b"\xff" * ((count + 7) // 8))
-        if count % 8:
-            full[-1] = (0xFF00 >> (count % 8)) & 0xFF
-        if avail != full or any(st != _native.TV_OK for st in status):
+        if avail != _all_ones(count) or any(st != _native.TV_OK for st in status):
             raise FileNotFoundError("hash_files: a file is missing or shorter than its declared length")
         return ctx.hash()
 
-    if P == 0:
-        return b""
-    _, slices = _run_shards(_devices(devices), P, shard)
-    return b"".join(slices)
+    return _hash_shards(devices, P, shard)
 
 
 def verify_piece(info: InfoDict, index: int, data) -> bool:
@@ -604,10 +622,7 @@ def hash_pieces(payload, piece_length_: int, devices=None, budget: Optional[int]
             ctx.stage(lo, mv[lo:hi])
         return ctx.hash()
 
-    if P == 0:
-        return b""
-    _, slices = _run_shards(_devices(devices), P, shard)
-    return b"".join(slices)
+    return _hash_shards(devices, P, shard)
 
 
 async def verify_pieces_async(info: InfoDict, storage, devices=None) -> bytearray:
