@@ -20,6 +20,11 @@ rounds_wave), so the same lengths, counts, short last pieces and checks also run
 (TV_OPT_SPLIT_PAIRS = 2) and with the split kernel forced (TV_OPT_KERNEL = 2) at 1 and 2 pairs per workgroup.  A
 split workgroup covers 64 pieces per pair, so its rows add 65, 128 and 129 pieces: one 1-pair workgroup and a bit,
 exactly two, two and a bit.
+
+The lane kernel (TV_OPT_KERNEL = 1) runs the same matrix with its 3-deep register ring and with its ring of two pairs
+(TV_OPT_LANE_PAIRS = 2 / 1): its workgroup is four waves of 64 pieces, so its rows add 63, 65, 255, 256 and 257
+pieces.  With the lane kernel forced the list call runs tv_list_kernel, whose two-deep A/B ring with clamped prologue
+loads so sees every length and every short last piece here.
 """
 import hashlib
 import random
@@ -28,10 +33,15 @@ import pytest
 
 TWIN = 4
 SPLIT = 2
-# the other kernels on the shared wave bodies: name -> (TV_OPT_KERNEL, TV_OPT_SPLIT_PAIRS)
-VARIANTS = {"twin2": (TWIN, 2), "split1": (SPLIT, 1), "split2": (SPLIT, 2)}
+LANE = 1
+# the other kernels on the shared wave bodies, and the lane kernel's two rings:
+# name -> (TV_OPT_KERNEL, TV_OPT_SPLIT_PAIRS, TV_OPT_LANE_PAIRS)
+VARIANTS = {"twin2": (TWIN, 2, 0), "split1": (SPLIT, 1, 0), "split2": (SPLIT, 2, 0),
+            "lane3": (LANE, 0, 2), "lanepairs": (LANE, 0, 1)}
 COUNTS = [1, 31, 32, 33, 64, 96]
 SPLIT_COUNTS = [65, 128, 129]
+LANE_COUNTS = [63, 65, 255, 256, 257]
+EXTRA_COUNTS = {SPLIT: SPLIT_COUNTS, LANE: LANE_COUNTS}
 # 64 k - 9, 64 k - 8, 64 k, 64 k + 1 for k = 1 .. 6 (k, k + 1, k + 1, k + 1 blocks), and the one-byte piece
 LENGTHS = [1] + [64 * k + d for k in range(1, 7) for d in (-9, -8, 0, 1)]
 
@@ -69,6 +79,7 @@ def _check(native, ctx, L, P, last, seed, kernel=TWIN):
     order = list(range(P))
     rng.shuffle(order)
     assert list(ctx.verify_list(order)) == [want[i] for i in order], (L, P, last)
+    assert ctx.last_kernel()[0] == kernel              # (forced: the list call runs that kernel's list form)
 
 
 def test_lengths_cover_every_block_count_and_padding_class():
@@ -120,19 +131,21 @@ def test_twin_short_last_piece_of_other_parity(native, P, fill):
 
 
 def _variant_cases(counts):
-    """(variant, P): the twin counts for every variant, and for the split rows the split counts too."""
-    return [(v, P) for v, (kernel, _) in VARIANTS.items()
-            for P in counts + ([c for c in SPLIT_COUNTS if c not in counts] if kernel == SPLIT else [])]
+    """(variant, P): the twin counts for every variant, and for the split and lane rows their own counts too."""
+    return [(v, P) for v, (kernel, _, _) in VARIANTS.items()
+            for P in counts + [c for c in EXTRA_COUNTS.get(kernel, []) if c not in counts]]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("variant,P", _variant_cases(COUNTS))
 def test_variant_block_counts(native, variant, P):
-    """As test_twin_block_counts, for the 2-pair twin workgroup and the split kernel at 1 and 2 pairs."""
-    kernel, pairs = VARIANTS[variant]
+    """As test_twin_block_counts, for the 2-pair twin workgroup, the split kernel at 1 and 2 pairs and the lane kernel's
+    two rings."""
+    kernel, pairs, lane_pairs = VARIANTS[variant]
     with native.Context(0) as ctx:
         ctx.set_option(native.TV_OPT_KERNEL, kernel)
         ctx.set_option(native.TV_OPT_SPLIT_PAIRS, pairs)
+        ctx.set_option(native.TV_OPT_LANE_PAIRS, lane_pairs)
         _block_counts(native, ctx, P, kernel)
 
 
@@ -140,9 +153,11 @@ def test_variant_block_counts(native, variant, P):
 @pytest.mark.parametrize("variant,P", _variant_cases([2, 33, 65, 97]))
 def test_variant_short_last_piece_of_other_parity(native, variant, P):
     """As test_twin_short_last_piece_of_other_parity, for the 2-pair twin workgroup and the split kernel at 1 and
-    2 pairs (the short last piece's own workgroup follows 1, 32, 64, 96 and, split, 127 and 128 full pieces)."""
-    kernel, pairs = VARIANTS[variant]
+    2 pairs (the short last piece's own workgroup follows 1, 32, 64, 96 and, split, 127 and 128 full pieces) and the
+    lane kernel's two rings (its own wave follows 62, 64, 254, 255 and 256 full pieces too)."""
+    kernel, pairs, lane_pairs = VARIANTS[variant]
     with native.Context(0) as ctx:
         ctx.set_option(native.TV_OPT_KERNEL, kernel)
         ctx.set_option(native.TV_OPT_SPLIT_PAIRS, pairs)
+        ctx.set_option(native.TV_OPT_LANE_PAIRS, lane_pairs)
         _short_last_piece(native, ctx, P, kernel)
