@@ -394,7 +394,8 @@ int tv_v2_check_blocks(tv_ctx *ctx, uint64_t n, const uint64_t *pieces, const ui
  * a second bitfield and availability (2 x 8 bytes per 64 pieces), allocated by the first call that needs them, counted
  * in TV_COUNTER_DEVICE_BYTES / _ALLOCS and reused by later calls they fit.  tv_verify, tv_hash and the tv_v2_* calls on
  * the same ctx keep their own answers (tv_verify then hashes the zeroed pads, as a v1 client reading pad files would).
- * Not built: a streamed hybrid verify through the bounded ring, and a hybrid list call on a slot pool.
+ * A shard that does not fit the device budget streams instead (tv_hybrid_stream_begin, below).  Not built: a hybrid
+ * list call on a slot pool.
  */
 int tv_hybrid_verify(tv_ctx *ctx, const uint8_t *avail_bits, uint8_t *v1_bits_out, uint8_t *v2_bits_out,
                      uint8_t *bitfield_out);
@@ -494,6 +495,52 @@ int tv_v2_stream_file_table(tv_ctx *ctx, uint64_t n_pieces, const uint32_t *piec
                             const uint8_t *hashes, uint64_t n_files, const uint64_t *lengths, const char *paths,
                             uint64_t paths_bytes, const uint8_t *avail_bits, uint8_t *bitfield_out, int32_t *status_out);
 
+/*
+ * Streamed hybrid verify through the same bounded ring: BOTH hash sets of a hybrid torrent from one pass over its
+ * bytes, without a resident shard (a torrent larger than the device budget, or a GPU shared with other work; two
+ * separate streams would move every byte over PCIe or off the disks twice).
+ *
+ * tv_hybrid_stream_begin is tv_v2_stream_begin (the GLOBAL piece table carried by the call, `hashes` required, the
+ * same ranges and error texts) over a layout that is the v1 space of the table (total_length with the pads, as for
+ * tv_hybrid_verify) and after tv_set_digests (the v1 `pieces` string), as tv_stream_begin needs it.  It works with
+ * TV_OPT_RESIDENT 0 or 1 and leaves a table set with tv_v2_set_pieces alone.  The requests follow the v2 row rule (row
+ * q holds min(width, piece_bytes[piece + q] - offset) FILE bytes; an empty row is neither filled nor copied): pad ranges
+ * are DEFINED as zeros and never cross PCIe.  When a unit's last request is committed the compute stream runs, over the
+ * unit's chunk buffer: a column pad launch that zeroes the part of [piece_bytes, v1_len) inside the column in every row
+ * that has one (each row's range derived on the device from the stream's piece table and the layout; no launch for a
+ * unit without one, so a one-file torrent with no tail pays nothing), the SHA-1 column launch of a v1 stream, and the v2
+ * column launch; after a window's last column the v2 level launches and the finish launch.  tv_stream_next / _commit /
+ * _commit_from / _unreadable / _fill_synthetic / _abort work unchanged.  tv_stream_end returns v1 AND v2;
+ * tv_hybrid_stream_end returns all three bitfields (v1_bits_out and v2_bits_out may be NULL; ceil(shard_count / 8)
+ * bytes each, spare bits 0; an unreadable or unavailable piece is 0 in all three) and is TV_ERR_STATE on a stream that
+ * is not a hybrid one, which then stays active.
+ *
+ * Geometry: C a power of two, 16 KiB <= C <= min(piece_length, 64 MiB), wn a multiple of 64 or the whole shard, as
+ * for a v2 stream.  TV_OPT_STREAM_CHUNK = X > 0: tv_v2_stream_begin's rule, one window across the shard.  Otherwise,
+ * under TV_OPT_RESIDENT_BUDGET (1 GiB when unset): each chunk buffer takes at most min(budget / 2, 256 MiB), and a
+ * window holds at least min(shard_count, 2,048) pieces where the budget allows (SHA-1 is serial per piece: a window of
+ * a few hundred whole pieces hashes slower than it stages): C starts at min(piece_length, 64 MiB) and is halved while
+ * that many rows do not fit, down to 16 KiB; then wn = the largest multiple of 64 whose rows fit, at least 64.
+ * TV_OPT_STREAM_ROWS has no effect.  Device memory beyond a v2 stream's: the second bitfield (16 bytes per 64 pieces,
+ * shared with tv_hybrid_verify), counted in TV_COUNTER_DEVICE_BYTES / _ALLOCS and reused by a later stream it fits.
+ * tv_last_kernel reports kernel id 256 and the launches used: per unit 2, plus 1 where the pad kernel ran, and per
+ * window log2(piece_length / C) + 1.  tv_last_timing and TV_COUNTER_LAST_WORKGROUPS report as for the other streams.
+ * TV_ERR_STATE: before tv_set_layout, before tv_set_digests, while a stream is active.  TV_ERR_ARG: as
+ * tv_v2_stream_begin, and a piece_bytes[i] > v1_len(i) for a shard piece (tv_hybrid_verify's text), piece_length > 2 GiB.
+ * A refused begin leaves no stream.
+ *
+ * tv_hybrid_stream_file_table is that stream with the library's own readers as the producer: tv_v2_stream_file_table's
+ * arguments, checks, open rules (TV_OPT_OPEN_RW) and per-file status over the REAL files in file-tree order, each at
+ * its aligned offset.  Pad files are not in the table: they are never opened or looked for.
+ */
+int tv_hybrid_stream_begin(tv_ctx *ctx, uint64_t n, const uint32_t *piece_bytes, const uint32_t *tree_leaves,
+                           const uint8_t *hashes /* 32*n */, const uint8_t *avail_bits);
+int tv_hybrid_stream_end(tv_ctx *ctx, uint8_t *v1_bits_out, uint8_t *v2_bits_out, uint8_t *bitfield_out);
+int tv_hybrid_stream_file_table(tv_ctx *ctx, uint64_t n_pieces, const uint32_t *piece_bytes, const uint32_t *tree_leaves,
+                                const uint8_t *hashes, uint64_t n_files, const uint64_t *lengths, const char *paths,
+                                uint64_t paths_bytes, const uint8_t *avail_bits, uint8_t *v1_bits_out,
+                                uint8_t *v2_bits_out, uint8_t *bitfield_out, int32_t *status_out);
+
 /* Page-locked host memory for tv_verify_host / tv_stage sources.  A pinned source is read by
  * DMA directly (no staging memcpy); pageable memory goes through the library's pinned ring.
  * tv_host_register pins an existing range (e.g. a caller's buffer), tv_host_unregister undoes it. */
@@ -555,8 +602,8 @@ int tv_get_option(tv_ctx *ctx, int key, int64_t *value);
 int tv_last_timing(tv_ctx *ctx, double *kernel_ms, double *total_ms);
 
 /* Kernel chosen for the last call (1 lane, 2 split, 4 twin; 8 = the v2 SHA-256 merkle kernels, 16 = the v2 list
- * kernel, 32 = a v2 stream's column kernel, 64 = the v2 block kernel, 128 = a hybrid call's pad + SHA-1 + v2 launches)
- * and launches it used. */
+ * kernel, 32 = a v2 stream's column kernel, 64 = the v2 block kernel, 128 = a hybrid call's pad + SHA-1 + v2 launches,
+ * 256 = a hybrid stream's) and launches it used. */
 int tv_last_kernel(tv_ctx *ctx, int *kernel, int *launches);
 
 /* Resource counters of a ctx (tv_get_counter keys): how often tv_set_layout and the calls after it had to

@@ -92,6 +92,7 @@ KERNEL_V2_LIST = 16   # tv_last_kernel after tv_v2_verify_list
 KERNEL_V2_STREAM = 32   # tv_last_kernel after a v2 stream (tv_v2_stream_begin .. tv_stream_end)
 KERNEL_V2_BLOCKS = 64   # tv_last_kernel after tv_v2_leaf_hashes / tv_v2_check_blocks
 KERNEL_HYBRID = 128   # tv_last_kernel after tv_hybrid_verify / tv_hybrid_hash
+KERNEL_HYBRID_STREAM = 256   # tv_last_kernel after a hybrid stream (tv_hybrid_stream_begin .. tv_stream_end)
 
 _u64, _i64, _int, _p = ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
 
@@ -147,6 +148,9 @@ SYMBOLS = [
     ("tv_hybrid_hash", _int, [_p, _p, _p]),
     ("tv_v2_stream_begin", _int, [_p, _u64, _p, _p, _p, _p]),
     ("tv_v2_stream_file_table", _int, [_p, _u64, _p, _p, _p, _u64, _p, _p, _u64, _p, _p, _p]),
+    ("tv_hybrid_stream_begin", _int, [_p, _u64, _p, _p, _p, _p]),
+    ("tv_hybrid_stream_end", _int, [_p, _p, _p, _p]),
+    ("tv_hybrid_stream_file_table", _int, [_p, _u64, _p, _p, _p, _u64, _p, _p, _u64, _p, _p, _p, _p, _p]),
     ("tv_stream_begin", _int, [_p, _p]),
     ("tv_stream_next", _int, [_p, _REQ]),
     ("tv_stream_commit", _int, [_p, _REQ]),
@@ -570,6 +574,34 @@ class Context:
                                ln.ctypes.data, blob, len(blob), avail=avail, tail=(st.ctypes.data,))
         del keep
         return bits, st[:n].tolist()
+
+    def hybrid_stream_begin(self, piece_bytes, tree_leaves, hashes, avail_bits=None) -> None:
+        """tv_hybrid_stream_begin: a v2 stream (the GLOBAL piece table as for v2_stream_begin; row_bytes follows it)
+        whose units are also hashed as v1 pieces, the pad ranges zeroed on the device: needs set_digests, and a layout
+        whose total_length is the v1 length (pads included).  stream_end then returns v1 AND v2, hybrid_stream_end all
+        three bitfields."""
+        pb, tl, a, keep = self._v2_table("hybrid_stream_begin", piece_bytes, tree_leaves, hashes)
+        b, keep2 = _addr(avail_bits)
+        self._check(self._L.tv_hybrid_stream_begin(self._h, len(pb), pb.ctypes.data, tl.ctypes.data, a, b))
+        self._v2_stream_bytes = pb
+        del keep, keep2
+
+    def hybrid_stream_end(self) -> tuple:
+        """tv_hybrid_stream_end: (bitfield, v1 bits, v2 bits) of the shard, as hybrid_verify returns them."""
+        v1, v2, out = self._bits_call(self._L.tv_hybrid_stream_end, takes_avail=False, outs=3)
+        return out, v1, v2
+
+    def hybrid_stream_file_table(self, piece_bytes, tree_leaves, hashes, lengths, paths,
+                                 avail: Optional[bytes] = None) -> tuple:
+        """tv_hybrid_stream_file_table: both hash sets of a hybrid torrent from the REAL files (no pad files) through
+        the bounded ring, the tables as for v2_stream_file_table.  -> ((bitfield, v1 bits, v2 bits), per-file
+        statuses)."""
+        pb, tl, h, keep = self._v2_table("hybrid_stream_file_table", piece_bytes, tree_leaves, hashes)
+        n, ln, blob, st = _file_table("hybrid_stream_file_table", lengths, paths)
+        v1, v2, out = self._bits_call(self._L.tv_hybrid_stream_file_table, len(pb), pb.ctypes.data, tl.ctypes.data, h,
+                                      n, ln.ctypes.data, blob, len(blob), avail=avail, outs=3, tail=(st.ctypes.data,))
+        del keep
+        return (out, v1, v2), st[:n].tolist()
 
     def stream_next(self) -> StreamReq:
         """The next request (req.rows == 0: every byte has been requested)."""

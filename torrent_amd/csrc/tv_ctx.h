@@ -144,6 +144,9 @@ struct StreamState {
     std::vector<uint8_t> av;   // shard-relative availability bits, applied to the bitfield at the end
     // a BitTorrent v2 stream (tv_v2_stream_begin): the units are hashed as merkle pieces by tv_v2_column_kernel
     bool v2 = false;
+    // a hybrid stream (tv_hybrid_stream_begin): a v2 stream (v2 is set too) whose units are also hashed as v1 pieces,
+    // after the column pad kernel; the v2 bits go to d_hy_bits, the v1 bits to d_out
+    bool hybrid = false;
     uint32_t v2_logc = 0, v2_logn = 0;   // log2 of the leaves per column (C / 16 KiB) and of the columns per piece (L / C)
     int launches = 0;                    // kernel launches so far (column, level and finish kernels)
     std::vector<uint32_t> v2_bytes;      // shard-relative valid bytes of every piece: the requests' row lengths
@@ -363,7 +366,7 @@ struct tv_ctx {
     std::vector<tvi::HybridTail> hy_tails_host;   // the table on the host (TV_OPT_HYBRID_PAD_PROBE's memset leg)
     uint64_t hy_probe_ns = 0;          // TV_COUNTER_HYBRID_PAD_NS
     DevBuf d_hy_tails{call_bufs, sizeof(tvi::HybridTail)};   // tail entries
-    DevBuf d_hy_bits{call_bufs, 2 * 8};   // [2][cap] 64-bit words: the v2 bitfield of a hybrid verify, then its v2 availability
+    DevBuf d_hy_bits{call_bufs, 2 * 8};   // [2][cap] 64-bit words: the v2 bitfield of a hybrid verify (or stream), then its v2 availability
 
     bool open_rw = true;               // TV_OPT_OPEN_RW: files opened read + write (fsStorage.get) or read-only
     bool stream_rows = false;          // TV_OPT_STREAM_ROWS: stream requests carry whole pieces (windows of pieces)
@@ -467,6 +470,10 @@ TvV2 v2_launch_args(tv_ctx* c);
 int v2_launch(tv_ctx* c, TvV2& p, bool hash);
 int hybrid_pad_probe(tv_ctx* c, int mode);
 void hybrid_on_layout(tv_ctx* c);   // tv_set_layout: drop the tail table, free what the new geometry does not fit
+// a hybrid stream's unit: zero the pad ranges of its rows in the chunk buffer (tv_hybrid_col_pad_kernel)
+hipError_t hybrid_col_pad_launch(const tv_ctx* c, uint8_t* data, uint64_t pitch, const uint32_t* piece_bytes,
+                                 uint64_t piece0, uint64_t offset, uint64_t C, uint64_t rows, uint64_t chunks,
+                                 hipStream_t s);
 void free_device(tv_ctx* c);
 bool reuse_fits(uint64_t need, uint64_t cap);
 

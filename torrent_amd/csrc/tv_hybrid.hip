@@ -3,7 +3,8 @@
 // piece, so the v1 linear space is the aligned space of the layout: v1 piece i is v2 piece i's piece_bytes[i] file bytes
 // followed by the pad file's zeros out to v1_len(i).  tv_hybrid_pad_kernel writes those zeros into the resident rows
 // (one launch over the shard's tail table, tv_plan.h hybrid_tails); then the SHA-1 launch of tv_verify / tv_hash and
-// the launch set of tv_v2_verify / tv_v2_hash run over the same rows.
+// the launch set of tv_v2_verify / tv_v2_hash run over the same rows.  A hybrid STREAM (tv_stream.hip) zeroes the pad
+// ranges of each unit's chunk buffer with tv_hybrid_col_pad_kernel instead.
 #include <cstring>
 
 #include "tv_ctx.h"
@@ -53,9 +54,55 @@ hipError_t launch_pad(const TvHybridPad& p, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// column pad kernel (a hybrid stream's unit: window rows [j0, j0 + rows) x column [offset, offset + C) of a chunk buffer
+// of row pitch C + 256).  Workgroup (x = row, y = chunk) derives the row's range itself -- its piece bytes from the
+// stream's piece table on the device, its v1 length from the layout (tv_plan.h hybrid_col_chunk) -- so a unit needs no
+// table of its own and no copy.  A row with an empty range, and a chunk outside it, return at once.  The stores are the
+// pad kernel's: bytes, uint4 from the first 16-byte aligned address, bytes; nothing below b, nothing at or past e
+// (e <= C < the pitch), nothing in a row outside the unit.
+// ------------------------------------------------------------------------------------------
+struct TvHybridColPad {
+    uint8_t* data;
+    uint64_t pitch;
+    const uint32_t* piece_bytes;   // of the unit's rows (the stream's table from piece j0 on)
+    uint64_t total, L;             // the layout: v1_len(i) = min(L, total - i * L)
+    uint64_t piece0;               // GLOBAL piece of row 0
+    uint64_t offset, C;            // the column
+    uint32_t rows;
+};
+
+__global__ __launch_bounds__(256) void tv_hybrid_col_pad_kernel(TvHybridColPad p) {
+    const uint32_t r = blockIdx.x;
+    if (r >= p.rows) return;
+    uint64_t b, e;
+    if (!hybrid_col_chunk(p.piece_bytes[r], p.total, p.L, p.piece0 + r, p.offset, p.C, blockIdx.y, &b, &e)) return;
+    const uint64_t row = reinterpret_cast<uint64_t>(p.data) + (uint64_t)r * p.pitch;
+    const uint64_t pb = row + b, pe = row + e;
+    uint64_t va, ve;
+    hybrid_split(pb, pe, &va, &ve);
+    const uint32_t tid = threadIdx.x;
+    if (pb + tid < va) *reinterpret_cast<uint8_t*>(pb + tid) = 0;   // (at most 15 bytes)
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    for (uint64_t q = va + 16ull * tid; q < ve; q += 16ull * 256) *reinterpret_cast<uint4*>(q) = z;
+    if (ve + tid < pe) *reinterpret_cast<uint8_t*>(ve + tid) = 0;   // (at most 15 bytes)
+}
+
 }  // namespace
 
 namespace tvi {
+
+// The column pad launch of one unit of a hybrid stream (tv_stream.hip): `chunks` = the most chunks a row's range has
+// (the caller knows both tables; 0 = no row has a range: nothing is launched).
+hipError_t hybrid_col_pad_launch(const tv_ctx* c, uint8_t* data, uint64_t pitch, const uint32_t* piece_bytes,
+                                 uint64_t piece0, uint64_t offset, uint64_t C, uint64_t rows, uint64_t chunks,
+                                 hipStream_t s) {
+    if (rows == 0 || chunks == 0) return hipSuccess;
+    if (rows > 0xFFFFFFull || chunks > 65535 || C + 256 != pitch) return hipErrorInvalidConfiguration;
+    TvHybridColPad p{data, pitch, piece_bytes, c->total, c->L, piece0, offset, C, (uint32_t)rows};
+    hipLaunchKernelGGL(tv_hybrid_col_pad_kernel, dim3((uint32_t)rows, (uint32_t)chunks), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
 
 // TV_OPT_HYBRID_PAD_PROBE (tools/hybrid_bench.py): zero the tails of the last hybrid call's table once more, timed on
 // the compute stream: mode 1 = the pad kernel's one launch, mode 2 = one hipMemsetAsync per tail (what a host holding

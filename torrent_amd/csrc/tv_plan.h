@@ -2,10 +2,12 @@
 // one (stream_geometry; v2_stream_geometry for a BitTorrent v2 stream), the file table's walk (walk_file_table) and a
 // v2 torrent's aligned file offsets (v2_file_starts) and the item list of a v2 block launch (v2_block_items,
 // v2_block_scatter), the digest-word codec (digest_pack, digest_unpack), the launch order of a v1 list (list_plan)
-// and the tail table of a hybrid call (hybrid_tails), as plain host code with no HIP in it, so they are unit-tested
+// and the tail table of a hybrid call (hybrid_tails) and a hybrid stream's geometry and column pad ranges
+// (hybrid_stream_geometry, hybrid_col_range), as plain host code with no HIP in it, so they are unit-tested
 // on the CPU (tests/c/plan_test.cpp, tests/c/walk_main.cpp, tests/c/plan_v2_main.cpp, tests/c/plan_v2_blocks_main.cpp,
-// tests/c/plan_codec_main.cpp, tests/c/plan_list_main.cpp, tests/c/plan_hybrid_main.cpp; tests/test_plan.py,
-// test_plan_v2.py, test_plan_v2_blocks.py, test_plan_codec.py, test_plan_list.py, test_plan_hybrid.py).
+// tests/c/plan_codec_main.cpp, tests/c/plan_list_main.cpp, tests/c/plan_hybrid_main.cpp,
+// tests/c/plan_hybrid_stream_main.cpp; tests/test_plan.py, test_plan_v2.py, test_plan_v2_blocks.py, test_plan_codec.py,
+// test_plan_list.py, test_plan_hybrid.py, test_plan_hybrid_stream.py).
 // Also the file calls' path table (parse_path_table) and the short segments' slot packing and copy runs (pack_slot,
 // for_copy_runs): tests/c/fileio_main.cpp, tests/test_fileio.py.
 #pragma once
@@ -360,8 +362,14 @@ struct HybridTail {
 constexpr uint64_t kHybridChunk = 64ull << 10;
 constexpr uint64_t kHybridMaxL = 1ull << 31;
 
-inline uint64_t hybrid_v1_len(uint64_t total, uint64_t L, uint64_t i) {
-    return (i > UINT64_MAX / L || i * L >= total) ? 0 : std::min<uint64_t>(L, total - i * L);
+#if defined(__HIPCC__)
+#define TV_PLAN_HD __host__ __device__
+#else
+#define TV_PLAN_HD
+#endif
+TV_PLAN_HD inline uint64_t hybrid_v1_len(uint64_t total, uint64_t L, uint64_t i) {
+    if (i > UINT64_MAX / L || i * L >= total) return 0;
+    return total - i * L < L ? total - i * L : L;
 }
 
 inline bool hybrid_tails(uint64_t total, uint64_t L, uint64_t first, uint64_t count, const uint32_t* piece_bytes,
@@ -390,11 +398,6 @@ inline bool hybrid_tails(uint64_t total, uint64_t L, uint64_t first, uint64_t co
 // (tests/c/plan_hybrid_main.cpp).  hybrid_chunk_entry: the entry whose chunks hold g (the last with chunk0 <= g; n > 0).
 // hybrid_chunk_range: the row bytes [*b, *e) of chunk g of entry t; false = none.  hybrid_split: byte ADDRESSES
 // [pb, pe) as byte stores [pb, *va), 16-byte vector stores [*va, *ve) (both 16-byte aligned) and byte stores [*ve, pe).
-#if defined(__HIPCC__)
-#define TV_PLAN_HD __host__ __device__
-#else
-#define TV_PLAN_HD
-#endif
 TV_PLAN_HD inline uint32_t hybrid_chunk_entry(const HybridTail* tails, uint32_t n, uint32_t g) {
     uint32_t lo = 0, hi = n;   // tails[lo].chunk0 <= g, and hi == n or tails[hi].chunk0 > g
     while (hi - lo > 1) {
@@ -415,6 +418,63 @@ TV_PLAN_HD inline void hybrid_split(uint64_t pb, uint64_t pe, uint64_t* va, uint
     const uint64_t a = (pb + 15) & ~15ull;
     *va = a < pe ? a : pe;
     *ve = *va + ((pe - *va) & ~15ull);
+}
+
+// ---- a hybrid stream (tv_stream.hip: tv_hybrid_stream_begin, tv_hybrid_stream_file_table) ---------------------------
+//
+// Both hash sets over the chunk buffers of ONE stream, so the geometry satisfies both sides.  The v2 side: C a power
+// of two, 16 KiB <= C <= min(L, 64 MiB), wn a multiple of 64 or the whole shard (a column of a piece is an aligned
+// subtree; C is a multiple of 64, so the SHA-1 column launches take it as it is).
+//   chunk > 0 (TV_OPT_STREAM_CHUNK): v2_stream_geometry's rule, one window across the shard.
+//   chunk == 0: v2_stream_geometry's whole pieces, as many as fit, are wrong here: SHA-1 is serial per piece, and a
+//     window of a few hundred pieces hashes slower than it stages (stream_geometry above).  So each chunk buffer is at
+//     most half = min(budget / 2, kStreamChunkMax) and a window has at least w0 = min(count, kHybridStreamWin) pieces:
+//     start from C = min(L, 64 MiB), halve C while C > 16 KiB and w0 rows of pitch C + 256 (+ slack) do not fit half;
+//     wn = the largest multiple of 64 whose rows fit half, at least 64, at most count.  (kHybridStreamWin is v1's
+//     floor; tools/hybrid_bench.py --stream measures the combined launch set against the two separate streams.)
+constexpr uint64_t kHybridStreamWin = 2048;
+inline void hybrid_stream_geometry(uint64_t L, uint64_t count, uint64_t budget, uint64_t chunk, uint64_t slack,
+                                   uint64_t* col, uint64_t* win) {
+    if (chunk) {
+        v2_stream_geometry(L, count, budget, chunk, slack, col, win);
+        return;
+    }
+    const uint64_t half = std::min<uint64_t>(budget / 2, kStreamChunkMax);
+    const uint64_t w0 = std::min<uint64_t>(count, kHybridStreamWin);
+    auto fits = [&](uint64_t C, uint64_t rows) { return half >= slack && rows <= (half - slack) / (C + 256); };
+    uint64_t C = std::min<uint64_t>(L, kV2StreamColMax);
+    while (C > kV2Leaf && !fits(C, w0)) C /= 2;
+    uint64_t wn = half > slack ? (half - slack) / (C + 256) / 64 * 64 : 0;
+    wn = std::max<uint64_t>(64, wn);
+    *col = C;
+    *win = std::min<uint64_t>(wn, count);
+}
+
+// The bytes of a row of column [offset, offset + C) that must read as zeros, column-relative: the piece's pad range
+// [piece_bytes, v1_len) (v1_len: hybrid_v1_len) cut to the column.  Empty when *b >= *e.
+TV_PLAN_HD inline void hybrid_col_range(uint64_t piece_bytes, uint64_t v1_len, uint64_t offset, uint64_t C, uint64_t* b,
+                                        uint64_t* e) {
+    const uint64_t lo = piece_bytes > offset ? piece_bytes - offset : 0;
+    const uint64_t hi = v1_len > offset ? v1_len - offset : 0;
+    *b = lo < C ? lo : C;
+    *e = hi < C ? hi : C;
+}
+
+// The column pad launch (tv_hybrid_col_pad_kernel) is rows x chunks workgroups: workgroup (row, k) stores chunk k of
+// the row's range, cut exactly as a tail entry's chunks are (hybrid_chunk_range on {row, b, e, chunk0 = 0}).
+// hybrid_col_chunks: the chunks of a range (0: empty).  hybrid_col_chunk: the column-relative bytes [*cb, *ce) of chunk
+// k of a row with piece_bytes valid bytes in a torrent of `total` v1 bytes; false = none.  Shared by the kernel and the
+// CPU test that replays it (tests/c/plan_hybrid_stream_main.cpp).
+TV_PLAN_HD inline uint64_t hybrid_col_chunks(uint64_t b, uint64_t e) {
+    return b < e ? (e - (b & ~15ull) + kHybridChunk - 1) / kHybridChunk : 0;
+}
+TV_PLAN_HD inline bool hybrid_col_chunk(uint64_t piece_bytes, uint64_t total, uint64_t L, uint64_t piece,
+                                        uint64_t offset, uint64_t C, uint32_t k, uint64_t* cb, uint64_t* ce) {
+    uint64_t b, e;
+    hybrid_col_range(piece_bytes, hybrid_v1_len(total, L, piece), offset, C, &b, &e);
+    if (b >= e) return false;
+    const HybridTail t{0, (uint32_t)b, (uint32_t)e, 0};
+    return hybrid_chunk_range(t, k, cb, ce);
 }
 
 }  // namespace tvi

@@ -1,7 +1,9 @@
 // tv_stream.hip -- the streamed verify engine (tv_stream_*; tv_verify_host runs on it): a bounded pinned ring
 // between the caller's bytes and two device chunk buffers, one kernel launch per column / window of pieces.
 // tv_v2_stream_begin / tv_v2_stream_file_table run BitTorrent v2 pieces through the same engine: one column-kernel
-// launch per unit and the window's top tree after its last column.
+// launch per unit and the window's top tree after its last column.  tv_hybrid_stream_begin /
+// tv_hybrid_stream_file_table run both hash sets of a hybrid torrent over each unit's chunk buffer: the column pad
+// kernel, the SHA-1 column launch, the v2 column launch.
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -147,15 +149,22 @@ int stream_begin_locked(tv_ctx* c, const uint8_t* avail_bits, uint64_t col_overr
 // carry each piece's SHA-1 chaining value in d_state); the window's last column is followed by the top tree over the
 // L / C nodes of each piece: log2(L / C) level launches and the finish launch, on a table derived for the window.
 // The geometry: tv_plan.h v2_stream_geometry.  The caller has checked the state and the table (v2_check_table).
+//
+// hybrid (tv_hybrid_stream_begin): the same stream under tv_plan.h hybrid_stream_geometry, whose units are also hashed
+// as v1 pieces (hybrid_unit_launch): the SHA-1 column launches use the state of a v1 stream (the digests, d_state,
+// d_base_avail; bits into d_out), the v2 launches write a second bitfield, the first half of d_hy_bits (its sizing
+// rule: bit_words), cleared here so it fails closed.  The caller has also checked the digests and piece_bytes <= v1_len.
 int v2_stream_begin_locked(tv_ctx* c, const uint32_t* piece_bytes, const uint32_t* tree_leaves, const uint8_t* hashes,
-                           const uint8_t* avail_bits, uint64_t req_bytes = 0) {
+                           const uint8_t* avail_bits, uint64_t req_bytes = 0, bool hybrid = false) {
     StreamState& st = c->st;
     const bool hashes_any = begin_state(c, avail_bits);
     st.v2 = true;
-    st.kernel = TV_KERNEL_V2_STREAM;
+    st.hybrid = hybrid;
+    st.kernel = hybrid ? TV_KERNEL_HYBRID_STREAM : TV_KERNEL_V2_STREAM;
     if (!hashes_any) return TV_OK;
     uint64_t C = 0, wn = 0;
-    v2_stream_geometry(c->L, c->count, c->budget_opt ? c->budget_opt : (1ull << 30), c->stream_chunk, kSlack, &C, &wn);
+    (hybrid ? hybrid_stream_geometry : v2_stream_geometry)(c->L, c->count, c->budget_opt ? c->budget_opt : (1ull << 30),
+                                                           c->stream_chunk, kSlack, &C, &wn);
     st.C = C;
     st.wn = wn;
     st.row_pitch = C + 256;
@@ -171,6 +180,7 @@ int v2_stream_begin_locked(tv_ctx* c, const uint32_t* piece_bytes, const uint32_
     int rc = grow_chunks(c, st.row_pitch * wn + kSlack);
     if (!rc) rc = grow_buf(c, c->d_v2s_tab, need_tab, true, need_tab);
     if (!rc) rc = grow_buf(c, c->d_v2s_nodes, need_nodes, true, need_nodes);
+    if (!rc && hybrid) rc = grow_buf(c, c->d_hy_bits, c->bit_words, false, c->bit_words);
     if (rc) return rc;
     // the shard's rows: bytes, leaves, the width of each piece's top tree over its column nodes, and the expected root
     // words (big-endian values), SoA [8][pieces of the window] window after window: a window's launches see a table
@@ -186,6 +196,7 @@ int v2_stream_begin_locked(tv_ctx* c, const uint32_t* piece_bytes, const uint32_
     }
     TV_HIP(c, hipMemcpyAsync(c->d_v2s_tab.ptr, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
     TV_HIP(c, hipStreamSynchronize(c->stream));   // (tab is the call's own)
+    if (hybrid) TV_HIP(c, hipMemsetAsync(c->d_hy_bits.ptr, 0, c->bit_words * 8, c->stream));
     return begin_done(c);
 }
 
@@ -219,7 +230,8 @@ int v2_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount) {
     p.nodes_a = k.nodes;
     p.nodes_b = k.nodes + 8 * wcount * st.ncol;
     p.expect = tab + 3 * c->count + 8 * j0;
-    p.out64 = c->d_out + j0 / 64;   // (availability: st.av, applied at the end with the unreadable pieces)
+    // (availability: st.av, applied at the end with the unreadable pieces; a hybrid stream's v2 bits: d_hy_bits)
+    p.out64 = (st.hybrid ? c->d_hy_bits.get<uint64_t>() : c->d_out) + j0 / 64;
     p.out_words = (uint32_t)((wcount + 63) / 64);
     for (uint32_t l = 0; l < st.v2_logn; l++) {
         TV_HIP(c, tv_v2_launch_level(p, l, st.v2_logn, c->stream));
@@ -228,6 +240,50 @@ int v2_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount) {
     TV_HIP(c, tv_v2_launch_finish(p, false, c->stream));
     st.launches++;
     return TV_OK;
+}
+
+// A completed unit's SHA-1 column launch: the window's pieces (the shard's digest / state rows from j0; bitfield words
+// from j0 / 64: a window of a multi-window stream is a multiple of 64 pieces) over bytes [offset, offset + C) of each,
+// the chaining values carried in d_state; the window's last column pads, compares and writes the bits.
+int v1_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount, uint64_t offset, int* kernel) {
+    StreamState& st = c->st;
+    const bool last = st.unit % st.ncol + 1 == st.ncol;
+    TvPieces p = window_launch(c, j0, wcount, c->d_chunk[buf].get<uint8_t>());
+    p.stride = st.row_pitch;
+    p.avail64 = c->d_base_avail + j0 / 64;
+    p.out64 = c->d_out + j0 / 64;
+    p.data_off = offset;
+    p.blk_begin = offset / 64;
+    p.blk_end = last ? UINT64_MAX : (offset + st.C) / 64;
+    p.finalize = last ? 1 : 0;
+    *kernel = choose_kernel_n(c, wcount, p.n_main < p.n);
+    p.lane_pairs = lane_pairs_for(c, p.n);
+    TV_HIP(c, tv_launch_verify(p, *kernel, false, c->stream, c->split_pairs, &c->last_workgroups));
+    return TV_OK;
+}
+
+// A completed unit of a hybrid stream, on the compute stream after col_ev: the column pad launch when a row of the unit
+// has a pad range inside the column (the host knows both tables: a unit without one pays nothing), the SHA-1 column
+// launch, then the v2 unit (its column launch is the last reader of the buffer: done_ev[buf] follows it).
+int hybrid_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount, uint64_t offset) {
+    StreamState& st = c->st;
+    uint64_t chunks = 0;   // the most a row's range has
+    for (uint64_t q = 0; q < wcount; q++) {
+        uint64_t b, e;
+        hybrid_col_range(st.v2_bytes[j0 + q], hybrid_v1_len(c->total, c->L, c->first + j0 + q), offset, st.C, &b, &e);
+        chunks = std::max(chunks, hybrid_col_chunks(b, e));
+    }
+    if (chunks) {
+        TV_HIP(c, hybrid_col_pad_launch(c, c->d_chunk[buf].get<uint8_t>(), st.row_pitch,
+                                        c->d_v2s_tab.get<uint32_t>() + j0, c->first + j0, offset, st.C, wcount, chunks,
+                                        c->stream));
+        st.launches++;
+    }
+    int kernel = 0;   // (tv_last_kernel reports the stream's own id)
+    const int rc = v1_unit_launch(c, buf, j0, wcount, offset, &kernel);
+    if (rc) return rc;
+    st.launches++;
+    return v2_unit_launch(c, buf, j0, wcount);
 }
 
 int stream_next_locked(tv_ctx* c, tv_stream_req* req) {
@@ -313,7 +369,7 @@ int stream_commit_locked(tv_ctx* c, const tv_stream_req* req, const uint8_t* src
             TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
             st.k0 = true;
         }
-        rc = v2_unit_launch(c, buf, j0, wcount);
+        rc = st.hybrid ? hybrid_unit_launch(c, buf, j0, wcount, r.offset) : v2_unit_launch(c, buf, j0, wcount);
         if (rc) return rc;
         st.unit++;
         st.row = 0;
@@ -353,27 +409,16 @@ int stream_commit_locked(tv_ctx* c, const tv_stream_req* req, const uint8_t* src
         TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
         st.k0 = true;
     }
-    const bool last = st.unit % st.ncol + 1 == st.ncol;
-    // the window's pieces (the shard's digest / state rows from j0; bitfield words from j0 / 64: a window of a
-    // multi-window stream is a multiple of 64 pieces)
-    TvPieces p = window_launch(c, j0, wcount, c->d_chunk[buf].get<uint8_t>());
-    p.stride = st.row_pitch;
-    p.avail64 = c->d_base_avail + j0 / 64;
-    p.out64 = c->d_out + j0 / 64;
-    p.data_off = r.offset;
-    p.blk_begin = r.offset / 64;
-    p.blk_end = last ? UINT64_MAX : (r.offset + st.C) / 64;
-    p.finalize = last ? 1 : 0;
-    st.kernel = choose_kernel_n(c, wcount, p.n_main < p.n);
-    p.lane_pairs = lane_pairs_for(c, p.n);
-    TV_HIP(c, tv_launch_verify(p, st.kernel, false, c->stream, c->split_pairs, &c->last_workgroups));
+    rc = v1_unit_launch(c, buf, j0, wcount, r.offset, &st.kernel);
+    if (rc) return rc;
     TV_HIP(c, hipEventRecord(c->done_ev[buf], c->stream));
     st.unit++;
     st.row = 0;
     return TV_OK;
 }
 
-int stream_end_locked(tv_ctx* c, uint8_t* bitfield_out) {
+// v1_out / v2_out (optional; tv_hybrid_stream_end): a hybrid stream's own two bitfields; bitfield_out is their AND.
+int stream_end_locked(tv_ctx* c, uint8_t* bitfield_out, uint8_t* v1_out = nullptr, uint8_t* v2_out = nullptr) {
     StreamState& st = c->st;
     if (!st.active) return fail(c, TV_ERR_STATE, "tv_stream_begin has not been called");
     if (st.outstanding || st.unit < st.nunits) {
@@ -387,12 +432,26 @@ int stream_end_locked(tv_ctx* c, uint8_t* bitfield_out) {
             return fail(c, TV_ERR_ARG, "bitfield_out is NULL");
         }
         TV_HIP(c, hipEventRecord(c->ev_k1, c->stream));
-        int rc = read_bits(c, bitfield_out);
+        const size_t wbytes = c->bit_words * 8;
+        int rc = TV_OK;
+        if (st.hybrid) {   // the v2 bits ride behind the v1 bits in h_bits (read_bits waits for both copies)
+            rc = ensure_hbits(c, 2 * wbytes);
+            if (!rc && hipMemcpyAsync(c->h_bits + wbytes, c->d_hy_bits.ptr, wbytes, hipMemcpyDeviceToHost, c->stream))
+                rc = fail(c, TV_ERR_HIP, "tv_stream_end: the copy of the v2 bitfield failed");
+        }
+        if (!rc) rc = read_bits(c, bitfield_out);
         if (rc) {
             stream_abort_locked(c);
             return rc;
         }
-        for (size_t k = 0; k < st.av.size(); k++) bitfield_out[k] &= st.av[k];  // unreadable pieces: bit 0
+        for (size_t k = 0; k < st.av.size(); k++) {
+            bitfield_out[k] &= st.av[k];  // unreadable pieces: bit 0 (in every bitfield of a hybrid stream)
+            if (!st.hybrid) continue;
+            const uint8_t b2 = c->h_bits[wbytes + k] & st.av[k];   // (spare bits: 0 in the v1 bits, so in the AND)
+            if (v1_out) v1_out[k] = bitfield_out[k];
+            if (v2_out) v2_out[k] = k + 1 == st.av.size() && c->count % 8 ? b2 & (uint8_t)(0xFF00u >> (c->count % 8)) : b2;
+            bitfield_out[k] &= b2;
+        }
         c->last_kernel = st.kernel;
         c->last_launches = st.v2 ? st.launches : (int)st.nunits;
         rc = finish_timing(c);
@@ -420,7 +479,8 @@ int stream_result(tv_ctx* c, int rc) {
 // and the file's status TV_ERR_IO.
 int stream_files_locked(tv_ctx* c, uint64_t n, const uint64_t* lengths, const std::vector<const char*>& path,
                         const std::vector<uint64_t>& start, RowBytes rule, const std::function<int(bool)>& begin,
-                        uint8_t* bitfield_out, int32_t* status_out) {
+                        uint8_t* bitfield_out, int32_t* status_out, uint8_t* v1_out = nullptr,
+                        uint8_t* v2_out = nullptr) {
     uint64_t lo, hi;
     shard_bytes(c, /*clamp_total=*/true, &lo, &hi);
     // Whether the shard's files are mostly not in the page cache (TV_OPT_FILE_ODIRECT): up to 16 of the files holding
@@ -580,7 +640,84 @@ int stream_files_locked(tv_ctx* c, uint64_t n, const uint64_t* lengths, const st
         stream_abort_locked(c);
         return rc;
     }
-    return stream_end_locked(c, bitfield_out);
+    return stream_end_locked(c, bitfield_out, v1_out, v2_out);
+}
+
+// What tv_v2_stream_begin and tv_hybrid_stream_begin (and their file-table forms) check before anything changes: the
+// layout, the GLOBAL piece table and its hashes; a hybrid stream also needs the digests (TV_ERR_STATE) and a layout that
+// is the v1 space of the table: piece_bytes <= v1_len for every shard piece (tv_hybrid_verify's rule and text).
+int v2_stream_check(tv_ctx* c, bool hybrid, uint64_t n, const uint32_t* piece_bytes, const uint32_t* tree_leaves,
+                    const uint8_t* hashes) {
+    const char* what = hybrid ? "tv_hybrid_stream_begin" : "tv_v2_stream_begin";
+    int rc = require_layout(c, hybrid);
+    if (rc) return rc;
+    rc = v2_check_table(c, n, piece_bytes, tree_leaves);
+    if (rc) return rc;
+    if (n && !hashes) return fail(c, TV_ERR_ARG, "NULL argument");
+    if (!hybrid) return TV_OK;
+    if (c->L > kHybridMaxL)
+        return fail(c, TV_ERR_ARG, "%s takes piece lengths up to %llu bytes (the layout has %llu)", what,
+                    (unsigned long long)kHybridMaxL, (unsigned long long)c->L);
+    for (uint64_t i = c->first; i < c->first + c->count; i++)
+        if (piece_bytes[i] > hybrid_v1_len(c->total, c->L, i))
+            return fail(c, TV_ERR_ARG, "%s: piece_bytes[%llu] = %llu exceeds the piece's v1 length %llu (total_length "
+                                       "%llu): the layout is not the v1 space of these pieces", what,
+                        (unsigned long long)i, (unsigned long long)piece_bytes[i],
+                        (unsigned long long)hybrid_v1_len(c->total, c->L, i), (unsigned long long)c->total);
+    return TV_OK;
+}
+
+int v2_stream_begin_call(tv_ctx* c, bool hybrid, uint64_t n, const uint32_t* piece_bytes, const uint32_t* tree_leaves,
+                         const uint8_t* hashes, const uint8_t* avail_bits) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = v2_stream_check(c, hybrid, n, piece_bytes, tree_leaves, hashes);
+    if (rc) return rc;
+    TV_HIP(c, hipSetDevice(c->device));
+    rc = v2_stream_begin_locked(c, piece_bytes, tree_leaves, hashes, avail_bits, 0, hybrid);
+    if (rc) c->st = StreamState{};   // (a failed begin leaves no stream, v2 or other)
+    return rc;
+}
+
+// tv_v2_stream_file_table / tv_hybrid_stream_file_table: tv_stream_file_table's reader loop over the ALIGNED file table
+// (every file starts a piece), the rows ending with their piece's bytes.  A v2 piece lies in one file, so it is
+// unreadable exactly when that file cannot supply its bytes; there are no zero-length segments to open, and a hybrid
+// torrent's pad files are not in the table: they are never opened or looked for.
+int v2_stream_files_call(tv_ctx* c, bool hybrid, uint64_t n_pieces, const uint32_t* piece_bytes,
+                         const uint32_t* tree_leaves, const uint8_t* hashes, uint64_t n, const uint64_t* lengths,
+                         const char* paths, uint64_t paths_bytes, const uint8_t* avail_bits, uint8_t* v1_out,
+                         uint8_t* v2_out, uint8_t* bitfield_out, int32_t* status_out) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = v2_stream_check(c, hybrid, n_pieces, piece_bytes, tree_leaves, hashes);
+    if (rc) return rc;
+    if (!bitfield_out && c->count) return fail(c, TV_ERR_ARG, "bitfield_out is NULL");
+    if (n && (!lengths || !paths || !status_out)) return fail(c, TV_ERR_ARG, "NULL argument");
+    std::vector<const char*> path(n);
+    const uint64_t np = parse_path_table(n, paths, paths_bytes, path.data());
+    if (np < n) return path_error(c, np, paths_bytes, n);
+    std::vector<uint64_t> start;   // file k's linear bytes: [start[k], start[k] + lengths[k])
+    uint64_t bad = 0;
+    if (!v2_file_starts(n, lengths, c->L, &start, &bad))
+        return fail(c, TV_ERR_ARG, "file %llu: the lengths overflow 64-bit offsets", (unsigned long long)bad);
+    if (start[n] / c->L != n_pieces)
+        return fail(c, TV_ERR_ARG, "the files hold %llu pieces, the piece table %llu", (unsigned long long)(start[n] / c->L),
+                    (unsigned long long)n_pieces);
+    // every piece's bytes are its file's (so a row never reaches past its file into the gap before the next one)
+    for (uint64_t k = 0; k < n; k++)
+        for (uint64_t p = start[k] / c->L, o = 0; o < lengths[k]; p++, o += c->L)
+            if (piece_bytes[p] != std::min<uint64_t>(c->L, lengths[k] - o))
+                return fail(c, TV_ERR_ARG, "piece_bytes[%llu] = %llu, but file %llu holds %llu bytes of that piece",
+                            (unsigned long long)p, (unsigned long long)piece_bytes[p], (unsigned long long)k,
+                            (unsigned long long)std::min<uint64_t>(c->L, lengths[k] - o));
+    for (uint64_t k = 0; k < n; k++) status_out[k] = TV_OK;
+    if (!c->count) return TV_OK;
+    TV_HIP(c, hipSetDevice(c->device));
+    rc = stream_files_locked(c, n, lengths, path, start, v2_row_bytes, [&](bool cold) {
+        return v2_stream_begin_locked(c, piece_bytes, tree_leaves, hashes, avail_bits, cold ? c->stream_cold_req : 0, hybrid);
+    }, bitfield_out, status_out, v1_out, v2_out);
+    if (rc && !c->st.active) c->st = StreamState{};
+    return rc;
 }
 
 }  // namespace tvi
@@ -713,60 +850,28 @@ int tv_stream_begin(tv_ctx* c, const uint8_t* avail_bits) {
 
 int tv_v2_stream_begin(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const uint32_t* tree_leaves,
                        const uint8_t* hashes, const uint8_t* avail_bits) {
-    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
-    std::lock_guard<std::mutex> g(c->mu);
-    int rc = require_layout(c, false);
-    if (rc) return rc;
-    rc = v2_check_table(c, n, piece_bytes, tree_leaves);
-    if (rc) return rc;
-    if (n && !hashes) return fail(c, TV_ERR_ARG, "NULL argument");
-    TV_HIP(c, hipSetDevice(c->device));
-    rc = v2_stream_begin_locked(c, piece_bytes, tree_leaves, hashes, avail_bits);
-    if (rc) c->st = StreamState{};   // (a failed begin leaves no stream, v2 or other)
-    return rc;
+    return v2_stream_begin_call(c, false, n, piece_bytes, tree_leaves, hashes, avail_bits);
 }
 
-// The v2 resume check from FILES through the bounded ring: tv_stream_file_table's reader loop over the ALIGNED file
-// table (every file starts a piece), the rows ending with their piece's bytes.  A v2 piece lies in one file, so it is
-// unreadable exactly when that file cannot supply its bytes; there are no zero-length segments to open.
+int tv_hybrid_stream_begin(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const uint32_t* tree_leaves,
+                           const uint8_t* hashes, const uint8_t* avail_bits) {
+    return v2_stream_begin_call(c, true, n, piece_bytes, tree_leaves, hashes, avail_bits);
+}
+
 int tv_v2_stream_file_table(tv_ctx* c, uint64_t n_pieces, const uint32_t* piece_bytes, const uint32_t* tree_leaves,
                             const uint8_t* hashes, uint64_t n, const uint64_t* lengths, const char* paths,
                             uint64_t paths_bytes, const uint8_t* avail_bits, uint8_t* bitfield_out,
                             int32_t* status_out) {
-    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
-    std::lock_guard<std::mutex> g(c->mu);
-    int rc = require_layout(c, false);
-    if (rc) return rc;
-    rc = v2_check_table(c, n_pieces, piece_bytes, tree_leaves);
-    if (rc) return rc;
-    if (n_pieces && !hashes) return fail(c, TV_ERR_ARG, "NULL argument");
-    if (!bitfield_out && c->count) return fail(c, TV_ERR_ARG, "bitfield_out is NULL");
-    if (n && (!lengths || !paths || !status_out)) return fail(c, TV_ERR_ARG, "NULL argument");
-    std::vector<const char*> path(n);
-    const uint64_t np = parse_path_table(n, paths, paths_bytes, path.data());
-    if (np < n) return path_error(c, np, paths_bytes, n);
-    std::vector<uint64_t> start;   // file k's linear bytes: [start[k], start[k] + lengths[k])
-    uint64_t bad = 0;
-    if (!v2_file_starts(n, lengths, c->L, &start, &bad))
-        return fail(c, TV_ERR_ARG, "file %llu: the lengths overflow 64-bit offsets", (unsigned long long)bad);
-    if (start[n] / c->L != n_pieces)
-        return fail(c, TV_ERR_ARG, "the files hold %llu pieces, the piece table %llu", (unsigned long long)(start[n] / c->L),
-                    (unsigned long long)n_pieces);
-    // every piece's bytes are its file's (so a row never reaches past its file into the gap before the next one)
-    for (uint64_t k = 0; k < n; k++)
-        for (uint64_t p = start[k] / c->L, o = 0; o < lengths[k]; p++, o += c->L)
-            if (piece_bytes[p] != std::min<uint64_t>(c->L, lengths[k] - o))
-                return fail(c, TV_ERR_ARG, "piece_bytes[%llu] = %llu, but file %llu holds %llu bytes of that piece",
-                            (unsigned long long)p, (unsigned long long)piece_bytes[p], (unsigned long long)k,
-                            (unsigned long long)std::min<uint64_t>(c->L, lengths[k] - o));
-    for (uint64_t k = 0; k < n; k++) status_out[k] = TV_OK;
-    if (!c->count) return TV_OK;
-    TV_HIP(c, hipSetDevice(c->device));
-    rc = stream_files_locked(c, n, lengths, path, start, v2_row_bytes, [&](bool cold) {
-        return v2_stream_begin_locked(c, piece_bytes, tree_leaves, hashes, avail_bits, cold ? c->stream_cold_req : 0);
-    }, bitfield_out, status_out);
-    if (rc && !c->st.active) c->st = StreamState{};
-    return rc;
+    return v2_stream_files_call(c, false, n_pieces, piece_bytes, tree_leaves, hashes, n, lengths, paths, paths_bytes,
+                                avail_bits, nullptr, nullptr, bitfield_out, status_out);
+}
+
+int tv_hybrid_stream_file_table(tv_ctx* c, uint64_t n_pieces, const uint32_t* piece_bytes, const uint32_t* tree_leaves,
+                                const uint8_t* hashes, uint64_t n, const uint64_t* lengths, const char* paths,
+                                uint64_t paths_bytes, const uint8_t* avail_bits, uint8_t* v1_bits_out,
+                                uint8_t* v2_bits_out, uint8_t* bitfield_out, int32_t* status_out) {
+    return v2_stream_files_call(c, true, n_pieces, piece_bytes, tree_leaves, hashes, n, lengths, paths, paths_bytes,
+                                avail_bits, v1_bits_out, v2_bits_out, bitfield_out, status_out);
 }
 
 int tv_stream_next(tv_ctx* c, tv_stream_req* req) {
@@ -810,6 +915,15 @@ int tv_stream_end(tv_ctx* c, uint8_t* bitfield_out) {
     std::lock_guard<std::mutex> g(c->mu);
     TV_HIP(c, hipSetDevice(c->device));
     return stream_end_locked(c, bitfield_out);
+}
+
+int tv_hybrid_stream_end(tv_ctx* c, uint8_t* v1_bits_out, uint8_t* v2_bits_out, uint8_t* bitfield_out) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    if (c->st.active && !c->st.hybrid)   // (the stream stays active: tv_stream_end ends it)
+        return fail(c, TV_ERR_STATE, "tv_hybrid_stream_end: the active stream is not a hybrid stream");
+    TV_HIP(c, hipSetDevice(c->device));
+    return stream_end_locked(c, bitfield_out, v1_bits_out, v2_bits_out);
 }
 
 int tv_stream_abort(tv_ctx* c) {

@@ -8,13 +8,16 @@ and v2 peers, and BEP 52 tells clients to refuse it.  The library zeroes the pad
 files are never looked for on disk, staged or read) and runs the SHA-1 kernel and the v2 kernels over the same bytes.
 
     parse_metainfo_hybrid(data) -> MetainfoHybrid | None          None unless v2 with v1 keys AND the two are consistent
-    verify_payload_hybrid(meta, files_bytes, devices=None) -> HybridResult     one buffer per (real) file
-    verify_files_hybrid(meta, dir_path, devices=None, threads=None) -> HybridResult
+    verify_payload_hybrid(meta, files_bytes, devices=None, stream=False) -> HybridResult     one buffer per (real) file
+    verify_files_hybrid(meta, dir_path, devices=None, threads=None, stream=False) -> HybridResult
+    verify_stream_hybrid(meta, read, devices=None, ...) -> HybridResult      through the bounded ring, any size
     hash_files_hybrid(dir_path, piece_length, ...) -> (v1 `pieces`, per-file v2 hashes)      creation mode
     make_torrent_hybrid(path, tracker, ...) -> bytes of a hybrid .torrent
 
-They shard over `devices` as the v2 calls do and need every shard resident within the device budget.  Not built: a
-streamed hybrid verify through the bounded ring, and a hybrid list call for incremental verify on a slot pool.
+They shard over `devices` as the v2 calls do.  The resident forms need every shard within the device budget;
+verify_stream_hybrid and stream=True run both hash sets over the chunk buffers of one stream instead
+(tv_hybrid_stream_begin / tv_hybrid_stream_file_table) and verify any size.  Not built: a hybrid list call for
+incremental verify on a slot pool.
 """
 from __future__ import annotations
 
@@ -25,9 +28,10 @@ from typing import List, Optional, Sequence
 
 from .bencode import bdecode_raw
 from .metainfo_v2 import FileV2, MetainfoV2, V2Layout, parse_metainfo_v2
+from . import _native
 from .v2 import (_creation_layout, _file_hashes, _file_paths, _file_tree, _resident_layout, _source_files,
                  _stage_file_buffers, _stage_files_v2, _torrent, piece_length_for_v2)
-from .verify import _bits_shards, _hash_shards
+from .verify import _bits_shards, _file_options, _hash_shards, _layout, _safe_paths, _shard_avail, _stream_rows
 
 CREATED_BY = "torrent_amd make_torrent_hybrid"
 
@@ -146,15 +150,45 @@ def _hybrid_layout(ctx, lay: V2Layout, total: int, first: int, count: int, hashe
         ctx.set_digests(pieces)
 
 
+def verify_stream_hybrid(meta: MetainfoHybrid, read, devices=None, avail: Optional[bytes] = None, chunk: int = 0,
+                         threads: Optional[int] = None, budget: Optional[int] = None) -> HybridResult:
+    """Both have-bitfields of a hybrid torrent through the library's BOUNDED pinned ring (tv_hybrid_stream_begin,
+    tv_stream_*): one pass over the bytes, no resident shard, so a torrent of any size verifies within `budget` bytes of
+    device memory (default 1 GiB).  read(file_index, offset, length) -> bytes | None is verify_stream_v2's: one row of
+    a request, `length` bytes of REAL file `file_index` (file-tree order) from `offset`; None or a short result makes
+    that piece unreadable (0 in all three bitfields).  Pad ranges are never asked for: the library writes their zeros
+    on the device.  chunk=C > 0 asks for columns of C bytes (a power of two >= 16 KiB) across the whole shard."""
+    lay = meta.layout
+
+    def shard(ctx, first: int, count: int) -> tuple:
+        _layout(ctx, meta.total_length, lay.piece_length, lay.n_pieces, first, count, budget, resident=False,
+                chunk=chunk, digests=meta.pieces)
+        return _stream_rows(
+            ctx, threads, lambda i, offset, n: read(lay.piece_file[i], lay.piece_offset[i] + offset, n),
+            lambda: ctx.hybrid_stream_begin(lay.piece_bytes, lay.tree_leaves, lay.hashes,
+                                            _shard_avail(avail, first, count)),
+            end=ctx.hybrid_stream_end)
+
+    return HybridResult(*_bits_shards(devices, lay.n_pieces, shard, fields=3))
+
+
 def verify_payload_hybrid(meta: MetainfoHybrid, files_bytes: Sequence, devices=None,
-                          budget: Optional[int] = None) -> HybridResult:
+                          budget: Optional[int] = None, stream: bool = False) -> HybridResult:
     """Both have-bitfields of a hybrid torrent whose files are in host memory: files_bytes[k] is file k's bytes (the
     file tree's order; pad files have no buffer).  None, or a buffer shorter than the file, makes exactly the pieces it
-    cannot supply unreadable (0 in all three bitfields)."""
+    cannot supply unreadable (0 in all three bitfields).  stream=True verifies through the bounded ring
+    (verify_stream_hybrid reading the buffers) and never raises for size; the default needs every shard resident within
+    the budget."""
     lay = meta.layout
     if len(files_bytes) != len(meta.files):
         raise ValueError("verify_payload_hybrid: one buffer per file")
     views = [None if b is None else memoryview(b).cast("B") for b in files_bytes]
+    if stream:
+        def read(k: int, offset: int, n: int):
+            mv = views[k]
+            return None if mv is None or mv.nbytes < offset + n else mv[offset:offset + n]
+
+        return verify_stream_hybrid(meta, read, devices=devices, budget=budget)
     lengths = [f.length for f in meta.files]
 
     def shard(ctx, first: int, count: int) -> tuple:
@@ -165,14 +199,28 @@ def verify_payload_hybrid(meta: MetainfoHybrid, files_bytes: Sequence, devices=N
 
 
 def verify_files_hybrid(meta: MetainfoHybrid, dir_path: str, devices=None, threads: Optional[int] = None,
-                        budget: Optional[int] = None) -> HybridResult:
+                        budget: Optional[int] = None, stream: bool = False) -> HybridResult:
     """Resume check of a hybrid torrent from disk.  Each real file is staged at its aligned offset (opened read-only);
-    pad files are never looked for.  A missing or short file gives 0 bits for exactly the pieces it cannot supply."""
+    pad files are never looked for.  A missing or short file gives 0 bits for exactly the pieces it cannot supply.
+    stream=True reads the files through the bounded ring in the library's own threads (tv_hybrid_stream_file_table) and
+    never raises for size; the default needs every shard resident within the budget."""
     lay = meta.layout
     paths = _file_paths(meta.name, meta.files, dir_path)
     lengths = [f.length for f in meta.files]
 
+    def stream_shard(ctx, first: int, count: int) -> tuple:
+        _layout(ctx, meta.total_length, lay.piece_length, lay.n_pieces, first, count, budget, resident=False,
+                digests=meta.pieces)
+        _file_options(ctx, threads or ctx.thread_budget, False)          # a verify writes nothing: read-only
+        try:
+            return ctx.hybrid_stream_file_table(lay.piece_bytes, lay.tree_leaves, lay.hashes, lengths,
+                                                _safe_paths(paths))[0]
+        finally:
+            ctx.set_option(_native.TV_OPT_OPEN_RW, 1)
+
     def shard(ctx, first: int, count: int) -> tuple:
+        if stream:
+            return stream_shard(ctx, first, count)
         _hybrid_layout(ctx, lay, meta.total_length, first, count, lay.hashes, meta.pieces, budget)
         _stage_files_v2(ctx, lay, lengths, paths, first, count, threads or ctx.thread_budget)
         return ctx.hybrid_verify()

@@ -412,11 +412,12 @@ def verify_stream(info: InfoDict, read, devices=None, avail: Optional[bytes] = N
     return _bits_shards(devices, P, shard)
 
 
-def _stream_rows(ctx, threads: Optional[int], read_row, begin) -> bytes:
+def _stream_rows(ctx, threads: Optional[int], read_row, begin, end=None):
     """The ring loop of a streamed check, after its layout: begin() opens the stream, then every request's rows are
     read -- read_row(i, offset, n) -> the n bytes of piece i from `offset`, or None -- on `threads` threads
     (_storage_threads), each copying its row into the slot itself, without the GIL.  A row that is None or short makes
-    its piece unreadable.  -> the shard's bits.  Any exception ends the stream (stream_abort); either way the stream
+    its piece unreadable.  -> the shard's bits: end() (default ctx.stream_end; a hybrid stream's three bitfields come
+    from ctx.hybrid_stream_end).  Any exception ends the stream (stream_abort); either way the stream
     options are back at their defaults afterwards."""
     nthr = _storage_threads(ctx, threads)
     pool = ThreadPoolExecutor(nthr) if nthr > 1 else None
@@ -443,7 +444,7 @@ def _stream_rows(ctx, threads: Optional[int], read_row, begin) -> bytes:
                 if i is not None:
                     ctx.stream_unreadable(i)
             ctx.stream_commit(req)
-        return ctx.stream_end()
+        return (end or ctx.stream_end)()
     except BaseException:
         ctx.stream_abort()
         raise

@@ -82,6 +82,18 @@ const SYMBOLS = {
     nonblocking: true,
   },
   tv_hybrid_hash: { parameters: ["pointer", "pointer", "pointer"], result: "i32", nonblocking: true },
+  tv_hybrid_stream_begin: {
+    parameters: ["pointer", "u64", "pointer", "pointer", "pointer", "pointer"],
+    result: "i32",
+    nonblocking: true,
+  },
+  tv_hybrid_stream_end: { parameters: ["pointer", "pointer", "pointer", "pointer"], result: "i32", nonblocking: true },
+  tv_hybrid_stream_file_table: {
+    parameters: ["pointer", "u64", "pointer", "pointer", "pointer", "u64", "pointer", "pointer", "u64", "pointer",
+                 "pointer", "pointer", "pointer", "pointer"],
+    result: "i32",
+    nonblocking: true,
+  },
   tv_v2_stream_begin: {
     parameters: ["pointer", "u64", "pointer", "pointer", "pointer", "pointer"],
     result: "i32",
