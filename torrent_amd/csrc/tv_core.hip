@@ -848,17 +848,6 @@ void copy_into_ring(Pool& pool, uint8_t* dst, const uint8_t* src, uint64_t n, in
     });
 }
 
-// Gather k rows of `width` bytes at pitch `pitch` from src into dst (packed at pitch width), on up to
-// `threads` threads.
-void gather_rows(Pool& pool, uint8_t* dst, const uint8_t* src, uint64_t width, uint64_t pitch, uint64_t k,
-                 int threads) {
-    const uint64_t per = std::max<uint64_t>(1, (4ull << 20) / std::max<uint64_t>(1, width));  // rows per task
-    const uint64_t tasks = (k + per - 1) / per;
-    pool.run(threads, tasks, [&](uint64_t q) {
-        for (uint64_t r = q * per; r < std::min(k, (q + 1) * per); r++) tv_copy_host(dst + r * width, src + r * pitch, width);
-    });
-}
-
 // One host -> device copy on the lane's copy stream, dword-aligned.  The DMA engine moves 1-byte-aligned
 // data ~10x slower than dword-aligned data (57 vs 5.7 GB/s, tools/dma_align_probe.py): when src and
 // dst agree mod 4, the 0-3 byte head and tail go as separate tiny copies and the body is aligned.

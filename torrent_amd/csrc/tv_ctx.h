@@ -148,7 +148,7 @@ struct StreamState {
     // after the column pad kernel; the v2 bits go to d_hy_bits, the v1 bits to d_out
     bool hybrid = false;
     uint32_t v2_logc = 0, v2_logn = 0;   // log2 of the leaves per column (C / 16 KiB) and of the columns per piece (L / C)
-    int launches = 0;                    // kernel launches so far (column, level and finish kernels)
+    int launches = 0;                    // kernel launches so far, every kind of stream (tv_stream.hip unit_launch)
     std::vector<uint32_t> v2_bytes;      // shard-relative valid bytes of every piece: the requests' row lengths
 };
 
@@ -555,7 +555,6 @@ struct DrainGuard {
 
 bool is_pinned(const void* p);
 void copy_into_ring(Pool& pool, uint8_t* dst, const uint8_t* src, uint64_t n, int threads);
-void gather_rows(Pool& pool, uint8_t* dst, const uint8_t* src, uint64_t width, uint64_t pitch, uint64_t k, int threads);
 int dma_h2d(tv_ctx* c, uint8_t* dst, const uint8_t* src, uint64_t n, int lane = 0);
 int stage_copy(tv_ctx* c, uint64_t pos, const uint8_t* src, uint64_t n, bool pinned, int lane = 0,
                bool src_in_ring = false);

@@ -3,11 +3,13 @@
 // v2 torrent's aligned file offsets (v2_file_starts) and the item list of a v2 block launch (v2_block_items,
 // v2_block_scatter), the digest-word codec (digest_pack, digest_unpack), the launch order of a v1 list (list_plan)
 // and the tail table of a hybrid call (hybrid_tails) and a hybrid stream's geometry and column pad ranges
-// (hybrid_stream_geometry, hybrid_col_range), as plain host code with no HIP in it, so they are unit-tested
+// (hybrid_stream_geometry, hybrid_col_range) and the stream engine's copy plan and row walk (for_row_copies,
+// walk_row_files), as plain host code with no HIP in it, so they are unit-tested
 // on the CPU (tests/c/plan_test.cpp, tests/c/walk_main.cpp, tests/c/plan_v2_main.cpp, tests/c/plan_v2_blocks_main.cpp,
 // tests/c/plan_codec_main.cpp, tests/c/plan_list_main.cpp, tests/c/plan_hybrid_main.cpp,
-// tests/c/plan_hybrid_stream_main.cpp; tests/test_plan.py, test_plan_v2.py, test_plan_v2_blocks.py, test_plan_codec.py,
-// test_plan_list.py, test_plan_hybrid.py, test_plan_hybrid_stream.py).
+// tests/c/plan_hybrid_stream_main.cpp, tests/c/plan_stream_rows_main.cpp; tests/test_plan.py, test_plan_v2.py,
+// test_plan_v2_blocks.py, test_plan_codec.py, test_plan_list.py, test_plan_hybrid.py, test_plan_hybrid_stream.py,
+// test_plan_stream_rows.py).
 // Also the file calls' path table (parse_path_table) and the short segments' slot packing and copy runs (pack_slot,
 // for_copy_runs): tests/c/fileio_main.cpp, tests/test_fileio.py.
 #pragma once
@@ -163,6 +165,46 @@ int for_copy_runs(const std::vector<SmallSeg>& s, size_t i, size_t j, Ok&& ok, C
         q = r;
     }
     return 0;
+}
+
+// ---- a stream request's copies and a row's files (tv_stream.hip: stream_commit_locked, stream_files_locked) ---------
+//
+// The copy plan of a request of n rows of `width` bytes, row q holding bytes(q) <= width valid ones: emit(first_row,
+// rows, bytes_per_row) once per maximal run of full-width rows (one 2D copy), once per short row (a copy of its own),
+// never for an empty row; a nonzero return ends the walk and is returned.  (A v1 request: at most a run and a tail.)
+template <class Bytes, class Emit>
+int for_row_copies(uint64_t n, uint64_t width, Bytes&& bytes, Emit&& emit) {
+    for (uint64_t q = 0; q < n;) {
+        const uint64_t nb = bytes(q);
+        uint64_t e = q + 1;
+        if (nb == width)
+            while (e < n && bytes(e) == width) e++;
+        if (nb)
+            if (const int rc = emit(q, e - q, nb)) return rc;
+        q = e;
+    }
+    return 0;
+}
+
+// A row's LINEAR bytes [a, b) over the file table: file k holds [start[k], start[k] + lengths[k]), start ascending with
+// n + 1 entries (v1: the files back to back; v2: v2_file_starts, a gap after a file that does not end a piece).
+// seg(file, file_offset, dst_offset, len) for each file segment in order; false from it stops the walk (kRowShort).
+// Starts at the last k with start[k] <= a, skips the files that end at or before the position (zero-length ones among
+// them), stops with kRowGap where the position lies before file k (the table and the rows disagree) and quietly where
+// the table ends before b (the callers dealt with those pieces beforehand).
+enum RowWalk { kRowWalked = 0, kRowGap = 1, kRowShort = 2 };
+template <class Seg>
+RowWalk walk_row_files(const uint64_t* start, const uint64_t* lengths, uint64_t n, uint64_t a, uint64_t b, Seg&& seg) {
+    const uint64_t at = (uint64_t)(std::upper_bound(start, start + n + 1, a) - start);
+    uint64_t k = at ? at - 1 : 0;
+    for (uint64_t pos = a; pos < b && k < n; k++) {
+        if (start[k] + lengths[k] <= pos) continue;
+        if (pos < start[k]) return kRowGap;
+        const uint64_t e = std::min(b, start[k] + lengths[k]);
+        if (!seg(k, pos - start[k], pos - a, e - pos)) return kRowShort;
+        pos = e;
+    }
+    return kRowWalked;
 }
 
 // ---- a stream's geometry under a device budget (tv_stream.hip: tv_stream_file_table, tv_verify_host) ----------------

@@ -4,10 +4,15 @@
 // launch per unit and the window's top tree after its last column.  tv_hybrid_stream_begin /
 // tv_hybrid_stream_file_table run both hash sets of a hybrid torrent over each unit's chunk buffer: the column pad
 // kernel, the SHA-1 column launch, the v2 column launch.
+//
+// The kinds share one row rule (stream_row_bytes), one geometry setter (set_geometry), one commit path
+// (stream_commit_locked over tv_plan.h for_row_copies) and one unit dispatch (unit_launch); the library's own reader
+// (stream_files_locked) is shard_is_cold, FdCache, tv_plan.h walk_row_files and read_segment.
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <cassert>
 #include <cerrno>
 #include <cstring>
 #include <memory>
@@ -21,25 +26,18 @@ namespace tvi {
 //
 // Column `col` carries bytes [col*C, col*C + C) of every shard piece.  Its rows arrive as requests of up to
 // one ring slot (64 MiB) each, filled by the caller, and are DMA'd from the slot into device chunk buffer
-// col & 1 (row pitch C + 256).  When a column's last request is committed, one kernel launch hashes it on the
-// compute stream (chaining values persist in d_state; the last column pads, compares and writes the
-// bitfield) while the next column's requests fill the other buffer.  Host memory in flight: the ring.
+// unit & 1 (row pitch C + 256; a unit is one column of one window of pieces).  When a unit's last request is
+// committed, its launch set (unit_launch) hashes it on the compute stream while the next unit's requests fill the
+// other buffer: for v1 pieces one SHA-1 launch (chaining values persist in d_state; the last column pads, compares
+// and writes the bitfield).  Host memory in flight: the ring.
 
-uint64_t row_bytes(const tv_ctx* c, uint64_t piece, uint64_t offset, uint64_t width) {  // piece.ts:16-19
-    const uint64_t plen = piece_len(c, piece);
+// The row rule of the begun stream: the piece's valid bytes inside the column, 0 when the piece ends before it.  A v1
+// piece has piece_len bytes (piece.ts:16-19: only the torrent's last piece is short); a v2 or hybrid piece has its
+// table's (st.v2_bytes), so any row may be short or empty: every file ends a piece.
+uint64_t stream_row_bytes(const tv_ctx* c, uint64_t piece, uint64_t offset, uint64_t width) {
+    const uint64_t plen = c->st.v2 ? c->st.v2_bytes[piece - c->first] : piece_len(c, piece);
     return plen > offset ? std::min(width, plen - offset) : 0;
 }
-
-// A v2 stream's row: the piece's valid bytes inside the column (0 when the piece ends before it).  Any row may be
-// short, not only the torrent's last piece's: every file ends a piece.
-uint64_t v2_row_bytes(const tv_ctx* c, uint64_t piece, uint64_t offset, uint64_t width) {
-    const uint64_t plen = c->st.v2_bytes[piece - c->first];
-    return plen > offset ? std::min(width, plen - offset) : 0;
-}
-
-// The row length rule of the active stream.
-using RowBytes = uint64_t (*)(const tv_ctx*, uint64_t, uint64_t, uint64_t);
-RowBytes stream_row_rule(const tv_ctx* c) { return c->st.v2 ? v2_row_bytes : row_bytes; }
 
 // Drop an active stream: give its lent slot back and let the queued copies and kernels drain.
 void stream_abort_locked(tv_ctx* c) {
@@ -122,25 +120,31 @@ static int begin_done(tv_ctx* c) {
     return TV_OK;
 }
 
+// The units of a stream of columns of C bytes over windows of wn pieces, and the rows of a request (req_bytes, or one
+// ring slot).  A v2 or hybrid stream's C divides L.
+static void set_geometry(tv_ctx* c, uint64_t C, uint64_t wn, uint64_t req_bytes) {
+    StreamState& st = c->st;
+    st.C = C;
+    st.wn = wn;
+    st.row_pitch = C + 256;  // (tail over-read slack per row)
+    st.ncol = (c->L + C - 1) / C;
+    st.nwin = (c->count + wn - 1) / wn;
+    st.nunits = st.nwin * st.ncol;
+    st.rows_per_req = std::max<uint64_t>(1, (req_bytes ? std::min<uint64_t>(req_bytes, kRingSlotBytes) : kRingSlotBytes) / C);
+}
+
+// (The begin functions share begin_state, set_geometry, grow_chunks and begin_done; the HIP calls between them stay per
+// kind: a v2 begin synchronises the compute stream before it replaces buffers and after its table copy, v1 never.)
 int stream_begin_locked(tv_ctx* c, const uint8_t* avail_bits, uint64_t col_override = 0, uint64_t win_override = 0,
                         uint64_t req_bytes = 0) {
-    StreamState& st = c->st;
     if (!begin_state(c, avail_bits)) return TV_OK;
-    if (stream_rows(c)) {  // whole pieces per row, windows of wn pieces
-        st.C = (c->L + 63) / 64 * 64;
-        st.wn = stream_row_window(c);
-    } else {               // columns across the whole shard (or across windows of win_override pieces)
-        st.C = col_override ? col_override : stream_column(c);
-        st.wn = win_override ? std::min(win_override, c->count) : c->count;
-    }
-    st.row_pitch = st.C + 256;  // (tail over-read slack per row)
-    const int rc = grow_chunks(c, st.row_pitch * st.wn + kSlack);
-    if (rc) return rc;
-    st.ncol = (c->L + st.C - 1) / st.C;
-    st.nwin = (c->count + st.wn - 1) / st.wn;
-    st.nunits = st.nwin * st.ncol;
-    st.rows_per_req = std::max<uint64_t>(1, (req_bytes ? std::min<uint64_t>(req_bytes, kRingSlotBytes) : kRingSlotBytes) / st.C);
-    return begin_done(c);
+    if (stream_rows(c))  // whole pieces per row, windows of stream_row_window pieces
+        set_geometry(c, (c->L + 63) / 64 * 64, stream_row_window(c), req_bytes);
+    else                 // columns across the whole shard (or across windows of win_override pieces)
+        set_geometry(c, col_override ? col_override : stream_column(c),
+                     win_override ? std::min(win_override, c->count) : c->count, req_bytes);
+    const int rc = grow_chunks(c, c->st.row_pitch * c->st.wn + kSlack);
+    return rc ? rc : begin_done(c);
 }
 
 // A BitTorrent v2 stream (tv_v2_stream_begin): the same ring, requests and chunk buffers, the units hashed as merkle
@@ -151,7 +155,7 @@ int stream_begin_locked(tv_ctx* c, const uint8_t* avail_bits, uint64_t col_overr
 // The geometry: tv_plan.h v2_stream_geometry.  The caller has checked the state and the table (v2_check_table).
 //
 // hybrid (tv_hybrid_stream_begin): the same stream under tv_plan.h hybrid_stream_geometry, whose units are also hashed
-// as v1 pieces (hybrid_unit_launch): the SHA-1 column launches use the state of a v1 stream (the digests, d_state,
+// as v1 pieces (unit_launch): the SHA-1 column launches use the state of a v1 stream (the digests, d_state,
 // d_base_avail; bits into d_out), the v2 launches write a second bitfield, the first half of d_hy_bits (its sizing
 // rule: bit_words), cleared here so it fails closed.  The caller has also checked the digests and piece_bytes <= v1_len.
 int v2_stream_begin_locked(tv_ctx* c, const uint32_t* piece_bytes, const uint32_t* tree_leaves, const uint8_t* hashes,
@@ -165,15 +169,10 @@ int v2_stream_begin_locked(tv_ctx* c, const uint32_t* piece_bytes, const uint32_
     uint64_t C = 0, wn = 0;
     (hybrid ? hybrid_stream_geometry : v2_stream_geometry)(c->L, c->count, c->budget_opt ? c->budget_opt : (1ull << 30),
                                                            c->stream_chunk, kSlack, &C, &wn);
-    st.C = C;
-    st.wn = wn;
-    st.row_pitch = C + 256;
-    st.ncol = c->L / C;
-    st.nwin = (c->count + wn - 1) / wn;
-    st.nunits = st.nwin * st.ncol;
+    assert(C && c->L % C == 0);   // (both powers of two, C <= L: set_geometry's rounded-up column count is exact)
+    set_geometry(c, C, wn, req_bytes);
     while ((kV2Leaf << st.v2_logc) < C) st.v2_logc++;
     while ((1ull << st.v2_logn) < st.ncol) st.v2_logn++;
-    st.rows_per_req = std::max<uint64_t>(1, (req_bytes ? std::min<uint64_t>(req_bytes, kRingSlotBytes) : kRingSlotBytes) / C);
     TV_HIP(c, hipStreamSynchronize(c->stream));   // (nothing queued still reads the buffers replaced below)
     // (whole-piece columns run no level: the finish launch reads the column nodes themselves, level buffer A alone)
     const uint64_t need_tab = 11 * c->count, need_nodes = st.ncol > 1 ? v2_node_words(wn, st.ncol) : 8 * wn;
@@ -200,12 +199,10 @@ int v2_stream_begin_locked(tv_ctx* c, const uint32_t* piece_bytes, const uint32_
     return begin_done(c);
 }
 
-// A completed unit of a v2 stream: the column kernel on the chunk buffer, and after a window's last column its top
-// tree (one level launch per doubling of the columns, none when a column is a whole piece) and the finish launch into
-// the window's bitfield words.  done_ev[buf] follows the column kernel, the only launch that reads the buffer.
-int v2_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount) {
+// ---- a completed unit's launches (unit_launch), on the compute stream after col_ev; each counts st.launches ----------
+// A v2 unit's column kernel on the chunk buffer: the only v2 launch that reads it.
+static int v2_column_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount) {
     StreamState& st = c->st;
-    const uint64_t col = st.unit % st.ncol;
     uint32_t* tab = c->d_v2s_tab.get<uint32_t>();
     TvV2Col k{};
     k.data = c->d_chunk[buf].get<uint8_t>();
@@ -213,22 +210,28 @@ int v2_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount) {
     k.n = (uint32_t)wcount;
     k.logc = st.v2_logc;
     k.logn = st.v2_logn;
-    k.col = (uint32_t)col;
+    k.col = (uint32_t)(st.unit % st.ncol);
     k.piece_bytes = tab + j0;
     k.tree_leaves = tab + c->count + j0;
     k.nodes = c->d_v2s_nodes.get<uint32_t>();
     k.clock = c->clock_probe ? c->d_clock : nullptr;
     TV_HIP(c, tv_v2_launch_column(k, c->stream, &c->last_workgroups));
     st.launches++;
-    TV_HIP(c, hipEventRecord(c->done_ev[buf], c->stream));
-    if (col + 1 < st.ncol) return TV_OK;
+    return TV_OK;
+}
+
+// After a v2 window's last column, its top tree over the column nodes (one level launch per doubling of the columns,
+// none when a column is a whole piece) and the finish launch into the window's bitfield words.
+static int v2_top_launch(tv_ctx* c, uint64_t j0, uint64_t wcount) {
+    StreamState& st = c->st;
+    uint32_t* tab = c->d_v2s_tab.get<uint32_t>();
     TvV2 p{};
     p.n = (uint32_t)wcount;
     p.logW = st.v2_logn;
     p.piece_bytes = tab + j0;
     p.tree_leaves = tab + 2 * c->count + j0;
-    p.nodes_a = k.nodes;
-    p.nodes_b = k.nodes + 8 * wcount * st.ncol;
+    p.nodes_a = c->d_v2s_nodes.get<uint32_t>();
+    p.nodes_b = p.nodes_a + 8 * wcount * st.ncol;
     p.expect = tab + 3 * c->count + 8 * j0;
     // (availability: st.av, applied at the end with the unreadable pieces; a hybrid stream's v2 bits: d_hy_bits)
     p.out64 = (st.hybrid ? c->d_hy_bits.get<uint64_t>() : c->d_out) + j0 / 64;
@@ -245,7 +248,7 @@ int v2_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount) {
 // A completed unit's SHA-1 column launch: the window's pieces (the shard's digest / state rows from j0; bitfield words
 // from j0 / 64: a window of a multi-window stream is a multiple of 64 pieces) over bytes [offset, offset + C) of each,
 // the chaining values carried in d_state; the window's last column pads, compares and writes the bits.
-int v1_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount, uint64_t offset, int* kernel) {
+static int v1_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount, uint64_t offset) {
     StreamState& st = c->st;
     const bool last = st.unit % st.ncol + 1 == st.ncol;
     TvPieces p = window_launch(c, j0, wcount, c->d_chunk[buf].get<uint8_t>());
@@ -256,16 +259,17 @@ int v1_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount, uint64_t of
     p.blk_begin = offset / 64;
     p.blk_end = last ? UINT64_MAX : (offset + st.C) / 64;
     p.finalize = last ? 1 : 0;
-    *kernel = choose_kernel_n(c, wcount, p.n_main < p.n);
+    const int kernel = choose_kernel_n(c, wcount, p.n_main < p.n);
+    if (!st.v2) st.kernel = kernel;   // (tv_last_kernel: a hybrid stream reports its own id)
     p.lane_pairs = lane_pairs_for(c, p.n);
-    TV_HIP(c, tv_launch_verify(p, *kernel, false, c->stream, c->split_pairs, &c->last_workgroups));
+    TV_HIP(c, tv_launch_verify(p, kernel, false, c->stream, c->split_pairs, &c->last_workgroups));
+    st.launches++;
     return TV_OK;
 }
 
-// A completed unit of a hybrid stream, on the compute stream after col_ev: the column pad launch when a row of the unit
-// has a pad range inside the column (the host knows both tables: a unit without one pays nothing), the SHA-1 column
-// launch, then the v2 unit (its column launch is the last reader of the buffer: done_ev[buf] follows it).
-int hybrid_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount, uint64_t offset) {
+// A hybrid unit's column pad launch, when a row of the unit has a pad range inside the column (the host knows both
+// tables: a unit without one pays nothing).
+static int hybrid_pad_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount, uint64_t offset) {
     StreamState& st = c->st;
     uint64_t chunks = 0;   // the most a row's range has
     for (uint64_t q = 0; q < wcount; q++) {
@@ -273,17 +277,24 @@ int hybrid_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount, uint64_
         hybrid_col_range(st.v2_bytes[j0 + q], hybrid_v1_len(c->total, c->L, c->first + j0 + q), offset, st.C, &b, &e);
         chunks = std::max(chunks, hybrid_col_chunks(b, e));
     }
-    if (chunks) {
-        TV_HIP(c, hybrid_col_pad_launch(c, c->d_chunk[buf].get<uint8_t>(), st.row_pitch,
-                                        c->d_v2s_tab.get<uint32_t>() + j0, c->first + j0, offset, st.C, wcount, chunks,
-                                        c->stream));
-        st.launches++;
-    }
-    int kernel = 0;   // (tv_last_kernel reports the stream's own id)
-    const int rc = v1_unit_launch(c, buf, j0, wcount, offset, &kernel);
-    if (rc) return rc;
+    if (!chunks) return TV_OK;
+    TV_HIP(c, hybrid_col_pad_launch(c, c->d_chunk[buf].get<uint8_t>(), st.row_pitch, c->d_v2s_tab.get<uint32_t>() + j0,
+                                    c->first + j0, offset, st.C, wcount, chunks, c->stream));
     st.launches++;
-    return v2_unit_launch(c, buf, j0, wcount);
+    return TV_OK;
+}
+
+// The launch set of the completed unit in chunk buffer `buf` (pieces [j0, j0 + wcount) of the shard, column bytes from
+// `offset`).  v1: the SHA-1 column launch.  v2: the column kernel, then the window's top tree.  hybrid: the pad launch,
+// the SHA-1 column launch, then the v2 set.  done_ev[buf] follows the last launch that reads the buffer.
+static int unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount, uint64_t offset) {
+    StreamState& st = c->st;
+    int rc = st.hybrid ? hybrid_pad_launch(c, buf, j0, wcount, offset) : TV_OK;
+    if (!rc && (st.hybrid || !st.v2)) rc = v1_unit_launch(c, buf, j0, wcount, offset);
+    if (!rc && st.v2) rc = v2_column_launch(c, buf, j0, wcount);
+    if (rc) return rc;
+    TV_HIP(c, hipEventRecord(c->done_ev[buf], c->stream));
+    return st.v2 && st.unit % st.ncol + 1 == st.ncol ? v2_top_launch(c, j0, wcount) : TV_OK;
 }
 
 int stream_next_locked(tv_ctx* c, tv_stream_req* req) {
@@ -312,7 +323,7 @@ int stream_next_locked(tv_ctx* c, tv_stream_req* req) {
 
 // Queue the outstanding request's rows [0, rows_copy) (the others are unreadable and not copied).  Source:
 // the request's slot (src == nullptr), or caller memory at src (row q at src + q*pitch), DMA'd directly when
-// page-locked and gathered into the slot otherwise.  Completes the column: one kernel launch.
+// page-locked and gathered into the slot by the lane-0 pool otherwise.  One body for every kind of stream.
 int stream_commit_locked(tv_ctx* c, const tv_stream_req* req, const uint8_t* src, uint64_t pitch, bool pinned,
                          uint64_t rows_copy) {
     StreamState& st = c->st;
@@ -326,79 +337,34 @@ int stream_commit_locked(tv_ctx* c, const tv_stream_req* req, const uint8_t* src
     uint8_t* dst = c->d_chunk[buf].get<uint8_t>() + st.row * st.row_pitch;
     uint8_t* slot = c->ring[st.slot];
     const uint64_t n = std::min(rows_copy, r.rows);
-    if (st.v2) {
-        // any row may be short or empty (every file ends a piece): runs of whole rows go as one 2D copy each, a short
-        // row as a copy of its own, an empty row (the piece ends before the column) is neither gathered nor copied
-        const uint8_t* from = slot;
-        uint64_t from_pitch = r.width;
-        if (src && pinned) {
-            from = src;
-            from_pitch = pitch;
-        } else if (src) {
-            const uint64_t per = std::max<uint64_t>(1, (4ull << 20) / r.width);  // rows per task, as gather_rows
-            c->pool[0].run(c->file_threads, (n + per - 1) / per, [&](uint64_t q) {
-                for (uint64_t k = q * per; k < std::min(n, (q + 1) * per); k++) {
-                    const uint64_t nb = v2_row_bytes(c, r.piece + k, r.offset, r.width);
-                    if (nb) tv_copy_host(slot + k * r.width, src + k * pitch, nb);
-                }
-            });
-        }
-        for (uint64_t q = 0; q < n;) {
-            const uint64_t nb = v2_row_bytes(c, r.piece + q, r.offset, r.width);
-            uint64_t e = q + 1;
-            if (nb == r.width) {
-                while (e < n && v2_row_bytes(c, r.piece + e, r.offset, r.width) == r.width) e++;
-                TV_HIP(c, hipMemcpy2DAsync(dst + q * st.row_pitch, st.row_pitch, from + q * from_pitch, from_pitch,
-                                           r.width, e - q, hipMemcpyHostToDevice, c->copy_stream));
-            } else if (nb) {
-                TV_HIP(c, hipMemcpyAsync(dst + q * st.row_pitch, from + q * from_pitch, nb, hipMemcpyHostToDevice,
-                                         c->copy_stream));
-            }
-            q = e;
-        }
-        st.outstanding = false;
-        const int s = st.slot;
-        st.slot = -1;
-        int rc = release_slot(c, s, 0);  // its event follows the copies just queued
-        if (rc) return rc;
-        st.row += r.rows;
-        if (st.row < wcount) return TV_OK;
-        TV_HIP(c, hipEventRecord(c->col_ev[buf], c->copy_stream));
-        TV_HIP(c, hipStreamWaitEvent(c->stream, c->col_ev[buf], 0));
-        if (!st.k0) {
-            TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
-            st.k0 = true;
-        }
-        rc = st.hybrid ? hybrid_unit_launch(c, buf, j0, wcount, r.offset) : v2_unit_launch(c, buf, j0, wcount);
-        if (rc) return rc;
-        st.unit++;
-        st.row = 0;
-        return TV_OK;
-    }
-    uint64_t full = n;  // rows [0, full) carry `width` bytes; only the torrent's short last piece has fewer
-    if (full && row_bytes(c, r.piece + full - 1, r.offset, r.width) < r.width) full--;
-    const uint64_t tail = full < n ? row_bytes(c, r.piece + full, r.offset, r.width) : 0;
+    const auto bytes = [&](uint64_t q) { return stream_row_bytes(c, r.piece + q, r.offset, r.width); };
     const uint8_t* from = slot;
     uint64_t from_pitch = r.width;
-    if (src) {
-        if (pinned) {
-            from = src;
-            from_pitch = pitch;
-        } else {
-            gather_rows(c->pool[0], slot, src, r.width, pitch, full, c->file_threads);
-            if (tail) memcpy(slot + full * r.width, src + full * pitch, tail);
-        }
+    if (src && pinned) {
+        from = src;
+        from_pitch = pitch;
+    } else if (src) {   // each row's valid bytes into the slot, ~4 MiB of rows per task
+        const uint64_t per = std::max<uint64_t>(1, (4ull << 20) / r.width);
+        c->pool[0].run(c->file_threads, (n + per - 1) / per, [&](uint64_t t) {
+            for (uint64_t q = t * per; q < std::min(n, (t + 1) * per); q++)
+                if (const uint64_t nb = bytes(q)) tv_copy_host(slot + q * r.width, src + q * pitch, nb);
+        });
     }
-    if (full)
-        TV_HIP(c, hipMemcpy2DAsync(dst, st.row_pitch, from, from_pitch, r.width, full, hipMemcpyHostToDevice,
-                                   c->copy_stream));
-    if (tail)
-        TV_HIP(c, hipMemcpyAsync(dst + full * st.row_pitch, from + full * from_pitch, tail, hipMemcpyHostToDevice,
-                                 c->copy_stream));
+    // a run of full rows is one 2D copy, a short row a copy of its own, an empty row none (v1: a run, then the tail)
+    int rc = for_row_copies(n, r.width, bytes, [&](uint64_t q, uint64_t rows, uint64_t nb) -> int {
+        if (nb == r.width)
+            TV_HIP(c, hipMemcpy2DAsync(dst + q * st.row_pitch, st.row_pitch, from + q * from_pitch, from_pitch, r.width,
+                                       rows, hipMemcpyHostToDevice, c->copy_stream));
+        else
+            TV_HIP(c, hipMemcpyAsync(dst + q * st.row_pitch, from + q * from_pitch, nb, hipMemcpyHostToDevice,
+                                     c->copy_stream));
+        return TV_OK;
+    });
+    if (rc) return rc;
     st.outstanding = false;
     const int s = st.slot;
     st.slot = -1;
-    int rc = release_slot(c, s, 0);  // its event follows the copies just queued
+    rc = release_slot(c, s, 0);  // its event follows the copies just queued
     if (rc) return rc;
     st.row += r.rows;
     if (st.row < wcount) return TV_OK;
@@ -409,9 +375,8 @@ int stream_commit_locked(tv_ctx* c, const tv_stream_req* req, const uint8_t* src
         TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
         st.k0 = true;
     }
-    rc = v1_unit_launch(c, buf, j0, wcount, r.offset, &st.kernel);
+    rc = unit_launch(c, buf, j0, wcount, r.offset);
     if (rc) return rc;
-    TV_HIP(c, hipEventRecord(c->done_ev[buf], c->stream));
     st.unit++;
     st.row = 0;
     return TV_OK;
@@ -453,7 +418,7 @@ int stream_end_locked(tv_ctx* c, uint8_t* bitfield_out, uint8_t* v1_out = nullpt
             bitfield_out[k] &= b2;
         }
         c->last_kernel = st.kernel;
-        c->last_launches = st.v2 ? st.launches : (int)st.nunits;
+        c->last_launches = st.launches;   // (a v1 stream: one per unit)
         rc = finish_timing(c);
         st = StreamState{};
         return rc;
@@ -462,94 +427,90 @@ int stream_end_locked(tv_ctx* c, uint8_t* bitfield_out, uint8_t* v1_out = nullpt
     return TV_OK;
 }
 
-
 // Public stream calls: a HIP failure leaves the stream unusable, so it is aborted (the ctx stays usable).
 int stream_result(tv_ctx* c, int rc) {
     if (rc == TV_ERR_HIP || rc == TV_ERR_NOMEM) stream_abort_locked(c);
     return rc;
 }
 
+// ---- the library's own readers as the producer (tv_stream_file_table and its v2 and hybrid forms), in parts ----------
+// File k's bytes are the LINEAR bytes [start[k], start[k] + lengths[k]) (v1: the files back to back; v2: every file at
+// the next piece boundary, tv_plan.h v2_file_starts).
 
-// The reader loop of tv_stream_file_table and tv_v2_stream_file_table: the stream engine with the library's own
-// readers as the producer.  File k's bytes are the LINEAR bytes [start[k], start[k] + lengths[k]) (v1: the files back
-// to back; v2: every file at the next piece boundary, tv_plan.h v2_file_starts); `rule` gives a request row's valid
-// bytes; begin(cold) starts the stream (its geometry and availability are the caller's) once the shard's files are
-// known to be mostly in the page cache or not.  Each row's range is walked over the files and read into the request's
-// ring slot by the lane-0 pool; a row that a missing, unopenable or short file cannot fill makes its piece unreadable
-// and the file's status TV_ERR_IO.
-int stream_files_locked(tv_ctx* c, uint64_t n, const uint64_t* lengths, const std::vector<const char*>& path,
-                        const std::vector<uint64_t>& start, RowBytes rule, const std::function<int(bool)>& begin,
-                        uint8_t* bitfield_out, int32_t* status_out, uint8_t* v1_out = nullptr,
-                        uint8_t* v2_out = nullptr) {
+// Whether the shard's files are mostly not in the page cache (TV_OPT_FILE_ODIRECT): up to 16 of the files holding
+// >= 1 MiB of its bytes, evenly spread, each sampled as the staging path samples a unit (64 pages), weighted by
+// bytes.  A cold shard is read in longer rows (fewer pieces per window) by more readers: O_DIRECT reads wait on
+// the disk, which wants long requests and many in flight (profiles/r06/window_bench_cold_cols*.jsonl).
+static bool shard_is_cold(const tv_ctx* c, uint64_t n, const uint64_t* lengths, const std::vector<const char*>& path,
+                          const std::vector<uint64_t>& start) {
+    if (!c->file_odirect) return false;
     uint64_t lo, hi;
     shard_bytes(c, /*clamp_total=*/true, &lo, &hi);
-    // Whether the shard's files are mostly not in the page cache (TV_OPT_FILE_ODIRECT): up to 16 of the files holding
-    // >= 1 MiB of its bytes, evenly spread, each sampled as the staging path samples a unit (64 pages), weighted by
-    // bytes.  A cold shard is read in longer rows (fewer pieces per window) by more readers: O_DIRECT reads wait on
-    // the disk, which wants long requests and many in flight (profiles/r06/window_bench_cold_cols*.jsonl).
-    bool cold = false;
-    if (c->file_odirect) {
-        std::vector<uint64_t> big;
-        for (uint64_t k = 0; k < n; k++) {
-            const uint64_t a = std::max(lo, start[k]), b = std::min(hi, start[k] + lengths[k]);
-            if (b > a && b - a >= (1u << 20) && path[k][0]) big.push_back(k);
-        }
-        double hit = 0, all = 0;
-        const size_t m = std::min<size_t>(16, big.size());
-        for (size_t q = 0; q < m; q++) {
-            const uint64_t k = big[q * big.size() / m];
-            const uint64_t a = std::max(lo, start[k]), b = std::min(hi, start[k] + lengths[k]);
-            // (nonblocking: a FIFO in the table must not hang the sample; only regular files are sampled)
-            const int fd = open(path[k], O_RDONLY | O_NONBLOCK | O_CLOEXEC);
-            if (fd < 0) continue;
-            struct stat sb;
-            const double f = fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) ? cached_fraction(fd, a - start[k], b - a) : -1;
-            close(fd);
-            if (f < 0) continue;
-            hit += f * (double)(b - a);
-            all += (double)(b - a);
-        }
-        cold = all > 0 && hit < 0.5 * all;
+    std::vector<uint64_t> big;
+    for (uint64_t k = 0; k < n; k++) {
+        const uint64_t a = std::max(lo, start[k]), b = std::min(hi, start[k] + lengths[k]);
+        if (b > a && b - a >= (1u << 20) && path[k][0]) big.push_back(k);
     }
-    // the call's open files: the first kCachedFds opened stay open until the end (a one- or few-file torrent opens
-    // each once); past that a reader opens and closes the file around its read (as fsStorage.get does per call), so
-    // a 10,000-file torrent never runs into the descriptor limit.  -2: the open failed.  A cached file whose pages
-    // are mostly not in the page cache at its open (64 sampled pages, TV_OPT_FILE_ODIRECT) is also opened O_DIRECT:
-    // its rows are read past the page cache (dfds; -1 none, and a file whose O_DIRECT read the filesystem refuses
-    // reads buffered from then on: no_direct).
-    constexpr int kCachedFds = 256;
-    std::vector<int> fds(n, -1), dfds(n, -1);
-    std::unique_ptr<std::atomic<bool>[]> no_direct(new std::atomic<bool>[n ? n : 1]());
+    double hit = 0, all = 0;
+    const size_t m = std::min<size_t>(16, big.size());
+    for (size_t q = 0; q < m; q++) {
+        const uint64_t k = big[q * big.size() / m];
+        const uint64_t a = std::max(lo, start[k]), b = std::min(hi, start[k] + lengths[k]);
+        // (nonblocking: a FIFO in the table must not hang the sample; only regular files are sampled)
+        const int fd = open(path[k], O_RDONLY | O_NONBLOCK | O_CLOEXEC);
+        if (fd < 0) continue;
+        struct stat sb;
+        const double f = fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) ? cached_fraction(fd, a - start[k], b - a) : -1;
+        close(fd);
+        if (f < 0) continue;
+        hit += f * (double)(b - a);
+        all += (double)(b - a);
+    }
+    return all > 0 && hit < 0.5 * all;
+}
+
+// The call's open files: the first kCachedFds opened stay open until the end (a one- or few-file torrent opens each
+// once); past that a reader opens and closes the file around its read (as fsStorage.get does per call), so a
+// 10,000-file torrent never runs into the descriptor limit.  -2: the open failed.  A cached file whose pages are mostly
+// not in the page cache at its open (64 sampled pages, TV_OPT_FILE_ODIRECT) is also opened O_DIRECT: its rows are read
+// past the page cache (dfds; -1 none, and a file whose O_DIRECT read the filesystem refuses reads buffered from then
+// on: no_direct).
+struct FdCache {
+    static constexpr int kCachedFds = 256;
+    const tv_ctx* c;
+    const uint64_t* lengths;
+    const std::vector<const char*>& path;
+    std::vector<int> fds, dfds;
+    std::unique_ptr<std::atomic<bool>[]> no_direct;
     int cached = 0;
-    std::mutex fd_mu;
-    struct Closer {
-        std::vector<int>& f;
-        std::vector<int>& d;
-        ~Closer() {
-            for (int x : f)
-                if (x >= 0) close(x);
-            for (int x : d)
-                if (x >= 0) close(x);
-        }
-    } closer{fds, dfds};
-    // -> a descriptor of file k, and whether the caller closes it after its read; *dfd: its O_DIRECT one or -1
-    auto fd_of = [&](uint64_t k, bool* own, int* dfd) -> int {
+    std::mutex mu;
+    FdCache(const tv_ctx* c, uint64_t n, const uint64_t* lengths, const std::vector<const char*>& path)
+        : c(c), lengths(lengths), path(path), fds(n, -1), dfds(n, -1), no_direct(new std::atomic<bool>[n ? n : 1]()) {}
+    ~FdCache() {
+        for (int x : fds)
+            if (x >= 0) close(x);
+        for (int x : dfds)
+            if (x >= 0) close(x);
+    }
+    // (under mu) file k's cached descriptor, -2, or -1 = not opened yet; *dfd: its O_DIRECT one while in use
+    int cached_fd(uint64_t k, int* dfd) const {
+        if (dfds[k] >= 0 && !no_direct[k].load(std::memory_order_relaxed)) *dfd = dfds[k];
+        return fds[k];
+    }
+    // -> a descriptor of file k, and whether the caller closes it after its read (*dfd as above, or -1)
+    int fd_of(uint64_t k, bool* own, int* dfd) {
         *own = false;
         *dfd = -1;
         {
-            std::lock_guard<std::mutex> fg(fd_mu);
-            if (fds[k] != -1) {
-                if (dfds[k] >= 0 && !no_direct[k].load(std::memory_order_relaxed)) *dfd = dfds[k];
-                return fds[k];
-            }
+            std::lock_guard<std::mutex> fg(mu);
+            if (fds[k] != -1) return cached_fd(k, dfd);
         }
         int e = 0;
         const int d = path[k][0] ? open_file(path[k], c->open_rw, &e) : -1;
-        std::lock_guard<std::mutex> fg(fd_mu);
+        std::lock_guard<std::mutex> fg(mu);
         if (fds[k] != -1) {   // another reader opened it meanwhile
             if (d >= 0) close(d);
-            if (dfds[k] >= 0 && !no_direct[k].load(std::memory_order_relaxed)) *dfd = dfds[k];
-            return fds[k];
+            return cached_fd(k, dfd);
         }
         if (d < 0) {
             if (e != EMFILE && e != ENFILE) fds[k] = -2;   // (out of descriptors: not the file's failure, but unread)
@@ -566,7 +527,49 @@ int stream_files_locked(tv_ctx* c, uint64_t n, const uint64_t* lengths, const st
         }
         *own = true;
         return d;
-    };
+    }
+};
+
+// `len` bytes of file k from byte `fo` into dst (a ring slot): O_DIRECT first where the file has such a descriptor, the
+// rest buffered.  -> the bytes read (< len: missing, unopenable or short, as fsStorage.get's read).
+static uint64_t read_segment(tv_ctx* c, FdCache& files, uint64_t k, uint64_t fo, uint8_t* dst, uint64_t len) {
+    bool own = false;
+    int dfd = -1;
+    const int fd = files.fd_of(k, &own, &dfd);
+    uint64_t o = 0;
+    if (dfd >= 0) {
+        const int64_t got = c->file_odirect == 2 ? -EINVAL   // (fault injection: O_DIRECT reads refused)
+                                                 : read_direct(dfd, fo, dst, len);
+        if (got >= 0) {
+            o = (uint64_t)got;
+            c->file_ns[TV_FILE_BYTES_ODIRECT].fetch_add(o, std::memory_order_relaxed);
+        } else {
+            // an O_DIRECT read the filesystem refuses is not the file's failure: this file reads buffered from here
+            // on, this segment included (counted, first errno kept, as the staging path's fallback)
+            files.no_direct[k].store(true, std::memory_order_relaxed);
+            odirect_refused(c, (int)-got);
+        }
+    }
+    if (fd >= 0 && o < len) {   // (a failed read's bytes so far still count as read)
+        uint64_t in = 0;
+        read_at(fd, dst + o, fo + o, len - o, len - o, &in);
+        o += in;
+    }
+    if (own) close(fd);
+    c->file_ns[TV_FILE_BYTES_READ].fetch_add(o, std::memory_order_relaxed);
+    return o;
+}
+
+// The reader loop: begin(cold) starts the stream (its geometry and availability are the caller's) once the shard's files
+// are known to be mostly in the page cache or not.  The lane-0 pool fills each request's ring slot: a row's bytes
+// (stream_row_bytes) are walked over the file table (tv_plan.h walk_row_files) and read segment by segment; a row that
+// a missing, unopenable or short file cannot fill makes its piece unreadable and the file's status TV_ERR_IO.
+int stream_files_locked(tv_ctx* c, uint64_t n, const uint64_t* lengths, const std::vector<const char*>& path,
+                        const std::vector<uint64_t>& start, const std::function<int(bool)>& begin,
+                        uint8_t* bitfield_out, int32_t* status_out, uint8_t* v1_out = nullptr,
+                        uint8_t* v2_out = nullptr) {
+    const bool cold = shard_is_cold(c, n, lengths, path, start);
+    FdCache files(c, n, lengths, path);
     const int readers = cold ? (c->stream_cold_readers ? c->stream_cold_readers : 2 * c->file_threads) : c->file_threads;
     DrainGuard drain(c);  // (the ring's copies and the column kernels are done when the call returns)
     int rc = begin(cold);
@@ -584,50 +587,18 @@ int stream_files_locked(tv_ctx* c, uint64_t n, const uint64_t* lengths, const st
         std::vector<uint8_t> row_bad(req.rows, 0);
         c->pool[0].run(readers, req.rows, [&](uint64_t q) {
             const uint64_t i = req.piece + q, j = i - c->first;
-            const uint64_t nb = rule(c, i, req.offset, req.width);
+            const uint64_t nb = stream_row_bytes(c, i, req.offset, req.width);
             if (!nb || !get_bit(c->st.av.data(), j)) return;
-            const uint64_t a = i * c->L + req.offset, b = a + nb;   // the row's linear bytes
+            const uint64_t a = i * c->L + req.offset;   // the row's linear bytes: [a, a + nb)
             uint8_t* out = slot + q * req.width;
-            // the file holding byte a: the last k with start[k] <= a < start[k + 1] (zero-length files skipped)
-            uint64_t k = (uint64_t)(std::upper_bound(start.begin(), start.end(), a) - start.begin()) - 1;
-            for (uint64_t pos = a; pos < b && k < n; k++) {
-                if (start[k] + lengths[k] <= pos) continue;
-                if (pos < start[k]) {   // (a row reaching into the gap after a file: its table and files disagree)
-                    row_bad[q] = 1;
-                    return;
-                }
-                const uint64_t e = std::min(b, start[k] + lengths[k]);
-                bool own = false;
-                int dfd = -1;
-                const int fd = fd_of(k, &own, &dfd);
-                uint64_t o = 0;
-                if (dfd >= 0) {
-                    const int64_t got = c->file_odirect == 2 ? -EINVAL   // (fault injection: O_DIRECT reads refused)
-                                                             : read_direct(dfd, pos - start[k], out + (pos - a), e - pos);
-                    if (got >= 0) {
-                        o = (uint64_t)got;
-                        c->file_ns[TV_FILE_BYTES_ODIRECT].fetch_add(o, std::memory_order_relaxed);
-                    } else {
-                        // an O_DIRECT read the filesystem refuses is not the file's failure: this file reads buffered
-                        // from here on, this row included (counted, first errno kept, as the staging path's fallback)
-                        no_direct[k].store(true, std::memory_order_relaxed);
-                        odirect_refused(c, (int)-got);
-                    }
-                }
-                if (fd >= 0 && o < e - pos) {   // (a failed read's bytes so far still count as read)
-                    uint64_t in = 0;
-                    read_at(fd, out + (pos - a) + o, pos - start[k] + o, e - pos - o, e - pos - o, &in);
-                    o += in;
-                }
-                if (own) close(fd);
-                c->file_ns[TV_FILE_BYTES_READ].fetch_add(o, std::memory_order_relaxed);
-                if (o < e - pos) {   // missing, unopenable or short: the piece is null, as fsStorage.get's read
-                    row_bad[q] = 1;
-                    file_err[k].store(TV_ERR_IO);
-                    return;
-                }
-                pos = e;
-            }
+            const RowWalk w = walk_row_files(start.data(), lengths, n, a, a + nb,
+                                             [&](uint64_t k, uint64_t fo, uint64_t at, uint64_t len) {
+                if (read_segment(c, files, k, fo, out + at, len) == len) return true;
+                file_err[k].store(TV_ERR_IO);   // missing, unopenable or short: the piece is null, as fsStorage.get's
+                return false;
+            });
+            // (kRowGap: a row reaching into the gap after a file, its table and files disagree; no file's status)
+            if (w != kRowWalked) row_bad[q] = 1;
         });
         for (uint64_t q = 0; q < req.rows; q++)
             if (row_bad[q]) clear_bit(c->st.av.data(), req.piece + q - c->first);
@@ -713,7 +684,7 @@ int v2_stream_files_call(tv_ctx* c, bool hybrid, uint64_t n_pieces, const uint32
     for (uint64_t k = 0; k < n; k++) status_out[k] = TV_OK;
     if (!c->count) return TV_OK;
     TV_HIP(c, hipSetDevice(c->device));
-    rc = stream_files_locked(c, n, lengths, path, start, v2_row_bytes, [&](bool cold) {
+    rc = stream_files_locked(c, n, lengths, path, start, [&](bool cold) {
         return v2_stream_begin_locked(c, piece_bytes, tree_leaves, hashes, avail_bits, cold ? c->stream_cold_req : 0, hybrid);
     }, bitfield_out, status_out, v1_out, v2_out);
     if (rc && !c->st.active) c->st = StreamState{};
@@ -763,7 +734,7 @@ int tv_verify_host(tv_ctx* c, const uint8_t* src, uint64_t src_len, const uint8_
         // rows wholly inside src: a prefix of the request (its rows ascend in linear offset)
         const uint64_t base = (req.piece - c->first) * c->L + req.offset;
         uint64_t k = 0;
-        while (k < req.rows && base + k * c->L + row_bytes(c, req.piece + k, req.offset, req.width) <= src_len) k++;
+        while (k < req.rows && base + k * c->L + stream_row_bytes(c, req.piece + k, req.offset, req.width) <= src_len) k++;
         rc = stream_commit_locked(c, &req, k ? src + base : nullptr, c->L, pinned, k);
         if (rc) break;
     }
@@ -829,7 +800,7 @@ int tv_stream_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const c
     // Geometry: windows x columns within the budget (TV_OPT_RESIDENT_BUDGET, or 1 GiB); a cold shard's windows are
     // 512 pieces (rows 4 x longer; ~44 GB/s of hashing, above what the disk gives).  An explicit TV_OPT_STREAM_CHUNK
     // keeps the engine's columns across the whole shard.
-    return stream_files_locked(c, n, lengths, path, start, row_bytes, [&](bool cold) {
+    return stream_files_locked(c, n, lengths, path, start, [&](bool cold) {
         uint64_t col = 0, win = 0;
         if (!c->stream_chunk) {
             const uint64_t min_win = cold ? (c->stream_cold_window ? c->stream_cold_window : 512) : 2048;
@@ -942,10 +913,9 @@ int tv_stream_fill_synthetic(tv_ctx* c, const tv_stream_req* req, uint64_t seed)
     if (!req || req->seq != st.req.seq) return fail(c, TV_ERR_ARG, "the request does not match the outstanding one");
     const tv_stream_req r = st.req;
     uint8_t* slot = c->ring[st.slot];
-    const RowBytes rule = stream_row_rule(c);   // (a v2 stream's rows end with their piece's bytes)
     c->pool[0].run(c->file_threads, r.rows, [&](uint64_t q) {
         const uint64_t i = r.piece + q;
-        tv_synth_fill_host(seed, i * c->L + r.offset, rule(c, i, r.offset, r.width), slot + q * r.width);
+        tv_synth_fill_host(seed, i * c->L + r.offset, stream_row_bytes(c, i, r.offset, r.width), slot + q * r.width);
     });
     return TV_OK;
 }
