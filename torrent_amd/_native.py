@@ -60,6 +60,7 @@ TV_OPT_V2_MAP = 29
 TV_COUNTER_V2_MAP = 124
 TV_OPT_HYBRID_PAD_PROBE = 31
 TV_COUNTER_HYBRID_PAD_NS = 125
+TV_COUNTER_LAST_STREAM_REQUESTS = 126
 V2_MAP_LEAF, V2_MAP_PIECE = 1, 2   # tv_internal.h TV_V2_MAP_*
 TV_COUNTER_WINDOW_STREAMS = 123
 WIN_BUFS_DEFAULT = 3    # tv_plan.h kWinBufsDefault: window buffers of a windowed layout

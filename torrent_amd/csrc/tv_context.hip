@@ -615,6 +615,7 @@ int tv_get_counter(tv_ctx* c, int key, uint64_t* value) {
         case TV_COUNTER_BUDGET: *value = c->budget; return TV_OK;
         case TV_COUNTER_V2_MAP: *value = (uint64_t)c->v2_last_map; return TV_OK;
         case TV_COUNTER_HYBRID_PAD_NS: *value = c->hy_probe_ns; return TV_OK;
+        case TV_COUNTER_LAST_STREAM_REQUESTS: *value = c->last_stream_requests; return TV_OK;
         case TV_COUNTER_SLOTS_USED: *value = c->slot_of.size(); return TV_OK;
         case TV_COUNTER_FILE_CLOCK + TV_FILE_PHASE_OPEN ... TV_COUNTER_FILE_CLOCK + TV_FILE_CLOCK_N - 1:
             *value = c->file_ns[key - TV_COUNTER_FILE_CLOCK].load();

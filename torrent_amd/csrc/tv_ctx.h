@@ -301,6 +301,7 @@ struct tv_ctx {
     float kernel_ms = 0.f, total_ms = 0.f;
     int last_kernel = 0, last_launches = 0;
     uint32_t last_workgroups = 0;      // grid of the last verify / hash / list launch, companions included
+    uint64_t last_stream_requests = 0; // TV_COUNTER_LAST_STREAM_REQUESTS: st.seq of the last stream that ended
 
     // Device budget (TV_OPT_RESIDENT_BUDGET).  A shard whose padded payload exceeds it gets a WINDOWED layout:
     // the payload allocation holds win_bufs buffers of win_n pieces, each window is hashed (HASH kernels into

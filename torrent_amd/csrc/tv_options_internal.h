@@ -70,6 +70,12 @@
                                       hipMemsetAsync per tail piece; the time is TV_COUNTER_HYBRID_PAD_NS */
 #define TV_COUNTER_HYBRID_PAD_NS 125 /* nanoseconds of the last TV_OPT_HYBRID_PAD_PROBE */
 #define TV_COUNTER_V2_MAP 124 /* the mapping the last tv_v2_verify / tv_v2_hash ran with (1 or 2; 0: none yet) */
+#define TV_COUNTER_LAST_STREAM_REQUESTS 126 /* requests (tv_stream_next calls that returned rows) the last COMPLETED
+                                               stream handed out, whoever drove it: the caller, tv_verify_host or a
+                                               file-table call's own readers.  Saved by tv_stream_end /
+                                               tv_hybrid_stream_end; 0 before any stream, unchanged by an aborted one.
+                                               The tests hold TV_OPT_STREAM_COLD_REQ and the rows-per-request rule
+                                               to it */
 
 /* ---- file staging phase clock (tv_files.hip), for the stamped breakdown of tools/f2_stamps.py ---------------------
  * tv_get_counter(TV_COUNTER_FILE_CLOCK + phase): nanoseconds tv_stage_file(s) spent in that phase since the last

@@ -420,9 +420,11 @@ int stream_end_locked(tv_ctx* c, uint8_t* bitfield_out, uint8_t* v1_out = nullpt
         c->last_kernel = st.kernel;
         c->last_launches = st.launches;   // (a v1 stream: one per unit)
         rc = finish_timing(c);
+        c->last_stream_requests = st.seq;   // (TV_COUNTER_LAST_STREAM_REQUESTS: completed streams only)
         st = StreamState{};
         return rc;
     }
+    c->last_stream_requests = st.seq;   // (an empty shard: 0)
     st = StreamState{};
     return TV_OK;
 }
