@@ -394,12 +394,42 @@ int tv_v2_check_blocks(tv_ctx *ctx, uint64_t n, const uint64_t *pieces, const ui
  * a second bitfield and availability (2 x 8 bytes per 64 pieces), allocated by the first call that needs them, counted
  * in TV_COUNTER_DEVICE_BYTES / _ALLOCS and reused by later calls they fit.  tv_verify, tv_hash and the tv_v2_* calls on
  * the same ctx keep their own answers (tv_verify then hashes the zeroed pads, as a v1 client reading pad files would).
- * A shard that does not fit the device budget streams instead (tv_hybrid_stream_begin, below).  Not built: a hybrid
- * list call on a slot pool.
+ * A shard that does not fit the device budget streams instead (tv_hybrid_stream_begin, below).
+ *
+ * tv_hybrid_verify_list: a LIST of completed pieces of a hybrid torrent, both hashes from one staging (incremental
+ * verify on piece completion, SURVEY 8f row f1, as tv_verify_list for v1 and tv_v2_verify_list for v2).  The layout is
+ * the v1 space (total_length with the pads) and tv_set_digests holds the v1 `pieces` string; the entries describe their
+ * v2 side themselves exactly as tv_v2_verify_list's do (no tv_v2_set_pieces is needed; a table that has been set is
+ * left alone).  On a whole-shard resident layout the piece's row is read, on a slot pool (TV_OPT_LIST_SLOTS) its slot.
+ * Entry k is GLOBAL piece pieces[k] (any order, duplicates allowed) with v1_len = min(piece_length, total_length -
+ * pieces[k] * piece_length).  The call first DEFINES the bytes [piece_bytes[k], v1_len) of the entry's row or slot as
+ * zeros, whatever a previous occupant or a fill left there (a host never stages a pad).  v1_ok_out[k] = 1 iff SHA-1 of
+ * the v1_len bytes equals the piece's `pieces` slice (a ragged or short slice never matches, as tv_verify_list);
+ * v2_ok_out[k] = 1 iff the merkle root of the first piece_bytes[k] bytes under a tree of tree_leaves[k] leaves equals
+ * hashes[32 k ..]; ok_out[k] = v1 AND v2.  v1_ok_out and v2_ok_out may be NULL.  A listed piece without a slot (never
+ * staged), or marked unreadable by tv_stage_file(s), is 0 in all three.  release != 0 frees every listed piece's slot
+ * when the call returns, as the other list calls do; release == 0 keeps them (the host may follow a failed piece with
+ * tv_v2_check_blocks; tv_read then shows the zeros).  A refused call changes nothing: it stores no zero and frees no
+ * slot.  n == 0 is TV_OK.
+ * TV_ERR_STATE, in this order: before tv_set_layout, before tv_set_digests, on a windowed layout, with TV_OPT_RESIDENT
+ * = 0, during a stream.  TV_ERR_ARG: NULL pieces, piece_bytes, tree_leaves, hashes or ok_out with n > 0, a piece
+ * outside the shard, piece_length not a power of two >= 16 KiB or > 1 GiB (the v2 list kernel's limit), a piece_bytes /
+ * tree_leaves entry outside tv_v2_set_pieces' ranges (its texts), a piece_bytes[k] > v1_len (tv_hybrid_verify's text).
+ * Every launch goes onto the compute stream before the call's one wait: the list pad launch (one launch over entries x
+ * chunks, each entry's range derived on the device from its row, its piece_bytes and its piece with the layout; only
+ * when some launched entry has a pad range), the SHA-1 list launch (tv_verify_list's kernel choice and launch order),
+ * the v2 list launch.  tv_last_kernel reports kernel id 512 and 2 launches, 3 with the pad launch, 0 when no listed
+ * piece held a slot; tv_last_timing's kernel_ms spans from the first launch's start to the last one's end;
+ * TV_COUNTER_LAST_WORKGROUPS is the v2 list launch's grid.  Device memory beyond the two list calls' buffers: 8 bytes
+ * per listed entry (at least 1,024 entries), counted in TV_COUNTER_DEVICE_BYTES / _ALLOCS and reused by later calls
+ * that fit.
  */
 int tv_hybrid_verify(tv_ctx *ctx, const uint8_t *avail_bits, uint8_t *v1_bits_out, uint8_t *v2_bits_out,
                      uint8_t *bitfield_out);
 int tv_hybrid_hash(tv_ctx *ctx, uint8_t *digests_out /* 20*shard_count */, uint8_t *roots_out /* 32*shard_count */);
+int tv_hybrid_verify_list(tv_ctx *ctx, uint64_t n, const uint64_t *pieces, const uint32_t *piece_bytes,
+                          const uint32_t *tree_leaves, const uint8_t *hashes /* 32*n */, uint8_t *v1_ok_out,
+                          uint8_t *v2_ok_out, uint8_t *ok_out, int release);
 
 /*
  * Streamed verify through a BOUNDED pinned ring (end-to-end resume check, SURVEY 8d cfg5: the
@@ -603,7 +633,7 @@ int tv_last_timing(tv_ctx *ctx, double *kernel_ms, double *total_ms);
 
 /* Kernel chosen for the last call (1 lane, 2 split, 4 twin; 8 = the v2 SHA-256 merkle kernels, 16 = the v2 list
  * kernel, 32 = a v2 stream's column kernel, 64 = the v2 block kernel, 128 = a hybrid call's pad + SHA-1 + v2 launches,
- * 256 = a hybrid stream's) and launches it used. */
+ * 256 = a hybrid stream's, 512 = a hybrid list call's pad + SHA-1 list + v2 list launches) and launches it used. */
 int tv_last_kernel(tv_ctx *ctx, int *kernel, int *launches);
 
 /* Resource counters of a ctx (tv_get_counter keys): how often tv_set_layout and the calls after it had to

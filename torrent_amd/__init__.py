@@ -12,14 +12,15 @@ from .storage import FsStorage, MemoryStorage, Storage, fs_storage  # noqa: F401
 from .verify import (context_counters, hash_files, hash_pieces, release_contexts, shard_ranges,  # noqa: F401
                      verify_files, verify_payload, verify_piece, verify_piece_async, verify_pieces,
                      verify_pieces_async, verify_stream)
-from .incremental import (IncrementalVerifier, IncrementalVerifierV2, flush_cost_ms_v2,  # noqa: F401
-                          validate_received_block_v2)
+from .incremental import (IncrementalVerifier, IncrementalVerifierHybrid, IncrementalVerifierV2,  # noqa: F401
+                          flush_cost_ms_v2, validate_received_block_v2)
 from .make_torrent import make_torrent  # noqa: F401
 from .metainfo_v2 import FileV2, MetainfoV2, V2Layout, parse_metainfo_v2  # noqa: F401
 from .v2 import (hash_files_v2, make_torrent_v2, verify_files_v2, verify_payload_v2,  # noqa: F401
                  verify_piece_v2, verify_stream_v2)
 from .hybrid import (HybridResult, MetainfoHybrid, hash_files_hybrid, make_torrent_hybrid,  # noqa: F401
-                     parse_metainfo_hybrid, verify_files_hybrid, verify_payload_hybrid, verify_stream_hybrid)
+                     parse_metainfo_hybrid, verify_files_hybrid, verify_payload_hybrid, verify_piece_hybrid,
+                     verify_stream_hybrid)
 from .merkle_v2 import (BlockRepairVerifierV2, check_blocks_v2, check_proof_v2, leaf_hashes_v2,  # noqa: F401
                         leaf_layers_files_v2, proof_v2)
 
@@ -35,6 +36,6 @@ __all__ = [
     "IncrementalVerifierV2", "flush_cost_ms_v2", "validate_received_block_v2",
     "BlockRepairVerifierV2", "check_blocks_v2", "check_proof_v2", "leaf_hashes_v2", "leaf_layers_files_v2", "proof_v2",
     "HybridResult", "MetainfoHybrid", "parse_metainfo_hybrid", "verify_payload_hybrid", "verify_files_hybrid",
-    "verify_stream_hybrid",
+    "verify_stream_hybrid", "verify_piece_hybrid", "IncrementalVerifierHybrid",
     "hash_files_hybrid", "make_torrent_hybrid",
 ]

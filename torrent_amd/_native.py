@@ -94,6 +94,7 @@ KERNEL_V2_STREAM = 32   # tv_last_kernel after a v2 stream (tv_v2_stream_begin .
 KERNEL_V2_BLOCKS = 64   # tv_last_kernel after tv_v2_leaf_hashes / tv_v2_check_blocks
 KERNEL_HYBRID = 128   # tv_last_kernel after tv_hybrid_verify / tv_hybrid_hash
 KERNEL_HYBRID_STREAM = 256   # tv_last_kernel after a hybrid stream (tv_hybrid_stream_begin .. tv_stream_end)
+KERNEL_HYBRID_LIST = 512   # tv_last_kernel after tv_hybrid_verify_list
 
 _u64, _i64, _int, _p = ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
 
@@ -147,6 +148,7 @@ SYMBOLS = [
     ("tv_v2_check_blocks", _int, [_p, _u64, _p, _p, _p, _p, _p, _p, _int]),
     ("tv_hybrid_verify", _int, [_p, _p, _p, _p, _p]),
     ("tv_hybrid_hash", _int, [_p, _p, _p]),
+    ("tv_hybrid_verify_list", _int, [_p, _u64, _p, _p, _p, _p, _p, _p, _p, _int]),
     ("tv_v2_stream_begin", _int, [_p, _u64, _p, _p, _p, _p]),
     ("tv_v2_stream_file_table", _int, [_p, _u64, _p, _p, _p, _u64, _p, _p, _u64, _p, _p, _p]),
     ("tv_hybrid_stream_begin", _int, [_p, _u64, _p, _p, _p, _p]),
@@ -747,6 +749,25 @@ class Context:
         r = ctypes.create_string_buffer(max(1, 32 * self.shard_count))
         self._check(self._L.tv_hybrid_hash(self._h, d, r))
         return d.raw[: 20 * self.shard_count], r.raw[: 32 * self.shard_count]
+
+    def hybrid_verify_list(self, pieces, piece_bytes, tree_leaves, hashes, release: bool = True) -> tuple:
+        """tv_hybrid_verify_list: (ok, v1, v2), one byte (0/1) per listed entry each: GLOBAL piece pieces[k] of a layout
+        over the v1 space (set_digests holds the v1 `pieces` string) with piece_bytes[k] file bytes, a merkle tree of
+        tree_leaves[k] leaves and the expected root hashes[32 k : 32 k + 32].  The pad range of every listed row or slot
+        is zeroed first; v1 = SHA-1 of the padded piece matches, v2 = the merkle root matches, ok = v1 AND v2.
+        release=False keeps the listed pieces' slots."""
+        pc, pb, tl = _v2_arrays("hybrid_verify_list", piece_bytes, tree_leaves, pieces)
+        n = len(pc)
+        a, keep = _v2_hashes("hybrid_verify_list", hashes, memoryview(hashes).nbytes, n, "entry")
+        rel = int(bool(release))
+        if n == 0:
+            self._check(self._L.tv_hybrid_verify_list(self._h, 0, None, None, None, None, None, None, None, rel))
+            return b"", b"", b""
+        v1, v2, ok = (ctypes.create_string_buffer(n) for _ in range(3))
+        self._check(self._L.tv_hybrid_verify_list(self._h, n, pc.ctypes.data, pb.ctypes.data, tl.ctypes.data, a, v1, v2,
+                                                  ok, rel))
+        del keep
+        return ok.raw[:n], v1.raw[:n], v2.raw[:n]
 
     def last_timing(self) -> tuple:
         k, t = ctypes.c_double(0), ctypes.c_double(0)

@@ -3,7 +3,7 @@
 // staging rings, windows, slot pool, kernel choice, the host -> HBM copy path; tv_stage.hip: staging from memory;
 // tv_files.hip: staging from files; tv_stream.hip: the streamed engine; tv_verify.hip: verify / list / hash;
 // tv_v2.hip: the BitTorrent v2 piece table, verify, hash and list verify (the streamed v2 verify: tv_stream.hip);
-// tv_hybrid.hip: hybrid torrents (the pad kernel, then the SHA-1 and the v2 launches over one staging).
+// tv_hybrid.hip: hybrid torrents (the pad kernel, then the SHA-1 and the v2 launches over one staging; the list call).
 // The device memory a call allocates is a DevBuf each (grow_buf / free_buf, tv_core.hip): the context lists them, so
 // free_device and TV_COUNTER_DEVICE_BYTES cover every one.  The steps the list calls share (list_*) are in tv_core.hip,
 // their pure parts (the digest-word codec, the v1 list's launch order) in tv_plan.h.
@@ -368,6 +368,7 @@ struct tv_ctx {
     uint64_t hy_probe_ns = 0;          // TV_COUNTER_HYBRID_PAD_NS
     DevBuf d_hy_tails{call_bufs, sizeof(tvi::HybridTail)};   // tail entries
     DevBuf d_hy_bits{call_bufs, 2 * 8};   // [2][cap] 64-bit words: the v2 bitfield of a hybrid verify (or stream), then its v2 availability
+    DevBuf d_hy_list{call_bufs, 8};       // tv_hybrid_verify_list: the GLOBAL piece of every launched entry (the pad launch's)
 
     bool open_rw = true;               // TV_OPT_OPEN_RW: files opened read + write (fsStorage.get) or read-only
     bool stream_rows = false;          // TV_OPT_STREAM_ROWS: stream requests carry whole pieces (windows of pieces)
@@ -600,6 +601,42 @@ inline uint32_t list_row(const tv_ctx* c, uint64_t j) { return c->slots ? c->slo
 void list_release(tv_ctx* c, uint64_t n, const uint64_t* pieces);   // a slot pool: the listed pieces' slots are free again
 void list_zero_unread(const tv_ctx* c, uint64_t n, const uint64_t* pieces, uint8_t* ok_out);  // file staging's bad pieces: 0
 int list_finish(tv_ctx* c, int kernel, uint64_t m);      // the call's record and timing (m = 0: nothing was launched)
+
+// The launch parts of tv_verify_list (tv_verify.hip) and tv_v2_verify_list (tv_v2.hip), which tv_hybrid_verify_list
+// (tv_hybrid.hip) runs one after the other on the compute stream.  A call plans on the host (*_plan: the entries
+// launched, `m` of them, and where their answers go; ok_out of an entry that holds no slot is set to 0), makes room
+// (*_reserve: nothing queued may still use the buffers), then queues upload, launch and download on the compute stream;
+// it records the events and waits itself, and *_scatter hands the answers out.  The host vectors of the plan outlive
+// the copies (a DrainGuard declared after it).
+struct V1List {
+    std::vector<uint32_t> launch;   // shard-relative pieces in tv_plan.h list_plan's order, then (slot pool) their rows
+    std::vector<int64_t> origin;    // launch position -> index in the caller's arrays (-1: padding)
+    std::vector<uint8_t> ok;        // the launch's out bytes
+    uint64_t m = 0;
+};
+int v1_list_plan(tv_ctx* c, uint64_t n, const uint64_t* pieces, uint8_t* ok_out, V1List* l);   // TV_ERR_ARG: outside the shard
+int v1_list_reserve(tv_ctx* c, const V1List& l);
+int v1_list_upload(tv_ctx* c, const V1List& l);
+int v1_list_launch(tv_ctx* c, const V1List& l, int* kernel);   // tv_verify_list's kernel choice and companion rule
+int v1_list_download(tv_ctx* c, V1List& l);
+void v1_list_scatter(const V1List& l, uint8_t* ok_out);
+struct V2List {
+    std::vector<uint64_t> origin;   // entry -> index in the caller's arrays
+    std::vector<uint32_t> tab;      // rows, bytes, widths, expected root words [8][m] (big-endian values)
+    std::vector<uint8_t> ok;
+    uint64_t m = 0;
+};
+// The argument checks of a v2 list (after the NULL checks): the list's and the piece length's limits, every entry in
+// the shard and inside tv_v2_set_pieces' ranges (its texts).
+int v2_list_check(tv_ctx* c, const char* what, uint64_t n, const uint64_t* pieces, const uint32_t* piece_bytes,
+                  const uint32_t* tree_leaves);
+void v2_list_plan(tv_ctx* c, uint64_t n, const uint64_t* pieces, const uint32_t* piece_bytes,
+                  const uint32_t* tree_leaves, const uint8_t* hashes, uint8_t* ok_out, V2List* l);
+int v2_list_reserve(tv_ctx* c, const V2List& l);
+int v2_list_upload(tv_ctx* c, const V2List& l);
+int v2_list_launch(tv_ctx* c, const V2List& l);
+int v2_list_download(tv_ctx* c, V2List& l);
+void v2_list_scatter(const V2List& l, uint8_t* ok_out);
 
 // ---- the streamed engine (tv_stream.hip) -----------------------------------------------------------------------------
 

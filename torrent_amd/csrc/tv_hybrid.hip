@@ -4,7 +4,9 @@
 // followed by the pad file's zeros out to v1_len(i).  tv_hybrid_pad_kernel writes those zeros into the resident rows
 // (one launch over the shard's tail table, tv_plan.h hybrid_tails); then the SHA-1 launch of tv_verify / tv_hash and
 // the launch set of tv_v2_verify / tv_v2_hash run over the same rows.  A hybrid STREAM (tv_stream.hip) zeroes the pad
-// ranges of each unit's chunk buffer with tv_hybrid_col_pad_kernel instead.
+// ranges of each unit's chunk buffer with tv_hybrid_col_pad_kernel instead.  tv_hybrid_verify_list checks completed
+// pieces on a slot pool (or a resident shard): tv_hybrid_list_pad_kernel over the listed rows, then the launch parts of
+// tv_verify_list and tv_v2_verify_list (tv_ctx.h V1List / V2List), one wait.
 #include <cstring>
 
 #include "tv_ctx.h"
@@ -88,6 +90,51 @@ __global__ __launch_bounds__(256) void tv_hybrid_col_pad_kernel(TvHybridColPad p
     if (ve + tid < pe) *reinterpret_cast<uint8_t*>(ve + tid) = 0;   // (at most 15 bytes)
 }
 
+// ------------------------------------------------------------------------------------------
+// list pad kernel (tv_hybrid_verify_list: m launched entries, each a whole piece in a payload row or a slot).  Workgroup
+// (x = entry, y = chunk) derives the entry's range itself -- its row and piece bytes from the v2 list table the call
+// uploads anyway, its v1 length from its GLOBAL piece and the layout (tv_plan.h hybrid_list_chunk: the column rule with
+// offset 0 and C = L) -- so the call builds and copies no tail table.  An entry with an empty range, and a chunk outside
+// it, return at once.  The stores are the pad kernel's: bytes, uint4 from the first 16-byte aligned address, bytes;
+// nothing below piece_bytes, nothing at or past v1_len (<= L <= the stride), nothing in a row outside the payload.  A
+// piece listed twice is stored twice, with the same zeros.
+// ------------------------------------------------------------------------------------------
+struct TvHybridListPad {
+    uint8_t* data;
+    uint64_t stride;
+    const uint32_t* rows;          // [m] payload row (or slot) of entry e
+    const uint32_t* piece_bytes;   // [m]
+    const uint64_t* pieces;        // [m] GLOBAL piece
+    uint64_t total, L;             // the layout: v1_len(i) = min(L, total - i * L)
+    uint32_t m;
+    uint32_t nrows;                // rows of the payload (an entry outside them is skipped: never a store out of bounds)
+};
+
+__global__ __launch_bounds__(256) void tv_hybrid_list_pad_kernel(TvHybridListPad p) {
+    const uint32_t en = blockIdx.x;
+    if (en >= p.m) return;
+    const uint32_t r = p.rows[en];
+    uint64_t b, e;
+    if (r >= p.nrows || !hybrid_list_chunk(p.piece_bytes[en], p.total, p.L, p.pieces[en], blockIdx.y, &b, &e)) return;
+    const uint64_t row = reinterpret_cast<uint64_t>(p.data) + (uint64_t)r * p.stride;
+    const uint64_t pb = row + b, pe = row + e;
+    uint64_t va, ve;
+    hybrid_split(pb, pe, &va, &ve);
+    const uint32_t tid = threadIdx.x;
+    if (pb + tid < va) *reinterpret_cast<uint8_t*>(pb + tid) = 0;   // (at most 15 bytes)
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    for (uint64_t q = va + 16ull * tid; q < ve; q += 16ull * 256) *reinterpret_cast<uint4*>(q) = z;
+    if (ve + tid < pe) *reinterpret_cast<uint8_t*>(ve + tid) = 0;   // (at most 15 bytes)
+}
+
+// `chunks` = the most chunks an entry's range has (0 = no entry has one: nothing is launched).
+hipError_t launch_list_pad(const TvHybridListPad& p, uint64_t chunks, hipStream_t s) {
+    if (p.m == 0 || chunks == 0) return hipSuccess;
+    if (p.m > 0x7FFFFFFFu || chunks > 65535 || p.L > p.stride) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(tv_hybrid_list_pad_kernel, dim3(p.m, (uint32_t)chunks), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 namespace tvi {
@@ -137,6 +184,7 @@ void hybrid_on_layout(tv_ctx* c) {
     // (the rules of the list buffers and of the bit words: kept while not far larger than the new shard needs)
     if (c->d_hy_tails.cap > std::max<uint64_t>(1024, 2 * c->count)) free_buf(c->d_hy_tails);
     if (!reuse_fits(c->bit_words, c->d_hy_bits.cap)) free_buf(c->d_hy_bits);
+    if (c->d_hy_list.cap > std::max<uint64_t>(1024, 2 * c->count)) free_buf(c->d_hy_list);
 }
 
 }  // namespace tvi
@@ -297,6 +345,102 @@ int tv_hybrid_hash(tv_ctx* c, uint8_t* digests_out, uint8_t* roots_out) {
         digest_unpack(soa2.data(), c->count, j, 8, roots_out + 32 * j);
     }
     return finish_timing(c);
+}
+
+// The check of completed pieces of a hybrid torrent: tv_verify_list's and tv_v2_verify_list's launch
+// parts (tv_ctx.h V1List / V2List) over the same rows or slots, after the list pad launch; one wait.
+int tv_hybrid_verify_list(tv_ctx* c, uint64_t n, const uint64_t* pieces, const uint32_t* piece_bytes,
+                          const uint32_t* tree_leaves, const uint8_t* hashes, uint8_t* v1_ok_out, uint8_t* v2_ok_out,
+                          uint8_t* ok_out, int release) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    // the state, in the order the header lists it
+    if (!c->has_layout) return fail(c, TV_ERR_STATE, "tv_set_layout has not been called");
+    if (!c->digests_set) return fail(c, TV_ERR_STATE, "tv_set_digests has not been called");
+    if (c->win)
+        return fail(c, TV_ERR_STATE, "tv_hybrid_verify_list needs the shard resident or a slot pool (TV_OPT_LIST_SLOTS); "
+                                     "this layout is windowed (the shard exceeds the device budget)");
+    if (c->count && !c->d_payload)
+        return fail(c, TV_ERR_STATE, "no resident payload (the layout was set with TV_OPT_RESIDENT = 0): use tv_stream_*");
+    if (c->st.active) return fail(c, TV_ERR_STATE, "a stream is active (finish it with tv_stream_end or tv_stream_abort)");
+    if (n == 0) return TV_OK;
+    if (!pieces || !piece_bytes || !tree_leaves || !hashes || !ok_out) return fail(c, TV_ERR_ARG, "NULL argument");
+    // every entry is checked before anything is stored, launched or freed: a refused call changes nothing
+    int rc = v2_list_check(c, "tv_hybrid_verify_list", n, pieces, piece_bytes, tree_leaves);
+    if (rc) return rc;
+    for (uint64_t k = 0; k < n; k++) {
+        const uint64_t v1 = hybrid_v1_len(c->total, c->L, pieces[k]);
+        if (piece_bytes[k] > v1)
+            return fail(c, TV_ERR_ARG, "tv_hybrid_verify_list: piece_bytes[%llu] = %llu exceeds the piece's v1 length "
+                                       "%llu (total_length %llu): the layout is not the v1 space of these pieces",
+                        (unsigned long long)k, (unsigned long long)piece_bytes[k], (unsigned long long)v1,
+                        (unsigned long long)c->total);
+    }
+    std::vector<uint8_t> ok1(n, 0), ok2(n, 0);
+    V1List l1;
+    V2List l2;
+    rc = v1_list_plan(c, n, pieces, ok1.data(), &l1);
+    if (rc) return rc;
+    v2_list_plan(c, n, pieces, piece_bytes, tree_leaves, hashes, ok2.data(), &l2);
+    // the pad launch reads the v2 table's rows and bytes; it needs each launched entry's GLOBAL piece beside them
+    const uint64_t m = l2.m;
+    std::vector<uint64_t> global(m);
+    uint64_t chunks = 0;
+    for (uint64_t e = 0; e < m; e++) {
+        const uint64_t k = l2.origin[e];
+        global[e] = pieces[k];
+        chunks = std::max(chunks, hybrid_list_chunks(piece_bytes[k], c->total, c->L, pieces[k]));
+    }
+    TV_HIP(c, hipSetDevice(c->device));
+    if (m) {
+        DrainGuard drain(c);  // after the host vectors: their H2D / D2H copies end before they go
+        rc = v1_list_reserve(c, l1);
+        if (!rc) rc = v2_list_reserve(c, l2);
+        if (!rc) rc = grow_buf(c, c->d_hy_list, m, false, std::max<uint64_t>(m, 1024));
+        if (rc) return rc;
+        TV_HIP(c, hipEventRecord(c->ev_call0, c->stream));
+        rc = v1_list_upload(c, l1);
+        if (!rc) rc = v2_list_upload(c, l2);
+        if (rc) return rc;
+        TV_HIP(c, hipMemcpyAsync(c->d_hy_list.ptr, global.data(), m * 8, hipMemcpyHostToDevice, c->stream));
+        TvHybridListPad pad{};
+        pad.data = c->d_payload;
+        pad.stride = c->stride;
+        pad.rows = c->d_v2_list.get<uint32_t>();
+        pad.piece_bytes = pad.rows + m;
+        pad.pieces = c->d_hy_list.get<uint64_t>();
+        pad.total = c->total;
+        pad.L = c->L;
+        pad.m = (uint32_t)m;
+        pad.nrows = (uint32_t)(c->slots ? c->slots : c->count);
+        int kernel = 0;
+        TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
+        TV_HIP(c, launch_list_pad(pad, chunks, c->stream));   // (a list with no pad range launches nothing)
+        rc = v1_list_launch(c, l1, &kernel);
+        if (!rc) rc = v2_list_launch(c, l2);   // (last: TV_COUNTER_LAST_WORKGROUPS is its grid)
+        if (rc) return rc;
+        TV_HIP(c, hipEventRecord(c->ev_k1, c->stream));
+        rc = v1_list_download(c, l1);
+        if (!rc) rc = v2_list_download(c, l2);
+        if (rc) return rc;
+        TV_HIP(c, hipEventRecord(c->ev_call1, c->stream));
+        TV_HIP(c, hipEventSynchronize(c->ev_call1));
+    } else {
+        c->last_workgroups = 0;
+    }
+    v1_list_scatter(l1, ok1.data());
+    v2_list_scatter(l2, ok2.data());
+    list_zero_unread(c, n, pieces, ok1.data());
+    list_zero_unread(c, n, pieces, ok2.data());
+    for (uint64_t k = 0; k < n; k++) {
+        if (v1_ok_out) v1_ok_out[k] = ok1[k];
+        if (v2_ok_out) v2_ok_out[k] = ok2[k];
+        ok_out[k] = ok1[k] & ok2[k];
+    }
+    if (release) list_release(c, n, pieces);
+    rc = list_finish(c, TV_KERNEL_HYBRID_LIST, m);
+    c->last_launches = m ? 2 + (chunks ? 1 : 0) : 0;
+    return rc;
 }
 
 }  // extern "C"

@@ -154,6 +154,7 @@ hipError_t tv_v2_launch_blocks(const TvV2Blocks& p, bool check, hipStream_t s, u
 // ---- hybrid torrents (tv_hybrid.hip): the pad kernel, then the SHA-1 launch and the v2 launch set over the same rows --
 #define TV_KERNEL_HYBRID 128      // tv_last_kernel id of tv_hybrid_verify / tv_hybrid_hash
 #define TV_KERNEL_HYBRID_STREAM 256   // ... of a hybrid stream (per unit: column pad, SHA-1 column, v2 column launches)
+#define TV_KERNEL_HYBRID_LIST 512     // ... of tv_hybrid_verify_list (list pad, SHA-1 list, v2 list launches)
 
 // workgroups (optional): set to the launch's grid size, companions included.
 hipError_t tv_launch_verify(const TvPieces& p, int kernel, bool hash, hipStream_t s, int split_pairs = 0,

@@ -3,8 +3,9 @@
 // v2 torrent's aligned file offsets (v2_file_starts) and the item list of a v2 block launch (v2_block_items,
 // v2_block_scatter), the digest-word codec (digest_pack, digest_unpack), the launch order of a v1 list (list_plan)
 // and the tail table of a hybrid call (hybrid_tails) and a hybrid stream's geometry and column pad ranges
-// (hybrid_stream_geometry, hybrid_col_range) and the stream engine's copy plan and row walk (for_row_copies,
-// walk_row_files), as plain host code with no HIP in it, so they are unit-tested
+// (hybrid_stream_geometry, hybrid_col_range), the pad chunks of a hybrid list entry (hybrid_list_chunk;
+// tests/c/plan_hybrid_list_main.cpp, tests/test_plan_hybrid_list.py) and the stream engine's copy plan and row walk
+// (for_row_copies, walk_row_files), as plain host code with no HIP in it, so they are unit-tested
 // on the CPU (tests/c/plan_test.cpp, tests/c/walk_main.cpp, tests/c/plan_v2_main.cpp, tests/c/plan_v2_blocks_main.cpp,
 // tests/c/plan_codec_main.cpp, tests/c/plan_list_main.cpp, tests/c/plan_hybrid_main.cpp,
 // tests/c/plan_hybrid_stream_main.cpp, tests/c/plan_stream_rows_main.cpp; tests/test_plan.py, test_plan_v2.py,
@@ -517,6 +518,23 @@ TV_PLAN_HD inline bool hybrid_col_chunk(uint64_t piece_bytes, uint64_t total, ui
     if (b >= e) return false;
     const HybridTail t{0, (uint32_t)b, (uint32_t)e, 0};
     return hybrid_chunk_range(t, k, cb, ce);
+}
+
+// ---- the pad launch of a hybrid list (tv_hybrid.hip: tv_hybrid_verify_list) -------------------------------------------
+//
+// A listed entry is a whole piece in a payload row or a slot: the column [0, L) of its piece.  The list pad launch
+// (tv_hybrid_list_pad_kernel) is entries x chunks workgroups: workgroup (e, k) stores chunk k of the entry's pad range
+// [piece_bytes, v1_len), cut by the column rule above with offset = 0 and C = L.  hybrid_list_chunks: the chunks of
+// an entry (0: no pad range; the host takes the largest as the grid's y).  Shared by the kernel and the CPU test that
+// replays it (tests/c/plan_hybrid_list_main.cpp).
+TV_PLAN_HD inline uint64_t hybrid_list_chunks(uint64_t piece_bytes, uint64_t total, uint64_t L, uint64_t piece) {
+    uint64_t b, e;
+    hybrid_col_range(piece_bytes, hybrid_v1_len(total, L, piece), 0, L, &b, &e);
+    return hybrid_col_chunks(b, e);
+}
+TV_PLAN_HD inline bool hybrid_list_chunk(uint64_t piece_bytes, uint64_t total, uint64_t L, uint64_t piece, uint32_t k,
+                                         uint64_t* b, uint64_t* e) {
+    return hybrid_col_chunk(piece_bytes, total, L, piece, 0, L, k, b, e);
 }
 
 }  // namespace tvi

@@ -233,6 +233,88 @@ int v2_blocks_call(tv_ctx* c, const char* what, bool check, uint64_t n, const ui
 
 }  // namespace
 
+namespace tvi {
+
+// ---- the launch parts of tv_v2_verify_list (tv_ctx.h: V2List), shared with tv_hybrid_verify_list ------------------------
+
+int v2_list_check(tv_ctx* c, const char* what, uint64_t n, const uint64_t* pieces, const uint32_t* piece_bytes,
+                  const uint32_t* tree_leaves) {
+    if (n >= 0xFFFFFF00ull) return fail(c, TV_ERR_ARG, "list too long");
+    if (!v2_piece_length_ok(c->L))
+        return fail(c, TV_ERR_ARG, "a v2 piece length is a power of two >= %d (the layout has %llu)", TV_V2_LEAF_BYTES,
+                    (unsigned long long)c->L);
+    if (c->L / TV_V2_LEAF_BYTES > (1ull << TV_V2_LIST_MAX_LOGW))
+        return fail(c, TV_ERR_ARG, "%s takes pieces of up to %llu bytes (the layout has %llu)", what,
+                    (unsigned long long)TV_V2_LEAF_BYTES << TV_V2_LIST_MAX_LOGW, (unsigned long long)c->L);
+    return v2_check_entries(c, n, pieces, piece_bytes, tree_leaves);
+}
+
+// The entries launched: every listed piece, or, in a slot pool, the listed pieces that hold a slot (the others were
+// never staged: 0).  origin[e] = the entry's index in the caller's arrays.
+void v2_list_plan(tv_ctx* c, uint64_t n, const uint64_t* pieces, const uint32_t* piece_bytes,
+                  const uint32_t* tree_leaves, const uint8_t* hashes, uint8_t* ok_out, V2List* l) {
+    l->origin.clear();
+    l->origin.reserve(n);
+    for (uint64_t k = 0; k < n; k++) {
+        if (list_held(c, pieces[k] - c->first)) l->origin.push_back(k);
+        else ok_out[k] = 0;
+    }
+    const uint64_t m = l->m = l->origin.size();
+    l->tab.assign(11 * m, 0);
+    for (uint64_t e = 0; e < m; e++) {
+        const uint64_t k = l->origin[e], j = pieces[k] - c->first;
+        l->tab[e] = list_row(c, j);
+        l->tab[m + e] = piece_bytes[k];
+        l->tab[2 * m + e] = tree_leaves[k];
+        digest_pack(hashes + 32 * k, 8, l->tab.data() + 3 * m, m, e);
+    }
+    l->ok.assign(m, 0);
+}
+
+// (11 table words and 4 out bytes per entry)
+int v2_list_reserve(tv_ctx* c, const V2List& l) {
+    return grow_buf(c, c->d_v2_list, l.m, false, std::max<uint64_t>(l.m, 1024));
+}
+
+static uint8_t* v2_list_out(const tv_ctx* c) {
+    return reinterpret_cast<uint8_t*>(c->d_v2_list.get<uint32_t>() + 11 * c->d_v2_list.cap);
+}
+
+int v2_list_upload(tv_ctx* c, const V2List& l) {
+    TV_HIP(c, hipMemcpyAsync(c->d_v2_list.ptr, l.tab.data(), l.tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    // fail closed: an entry the launch does not write reads as 0
+    TV_HIP(c, hipMemsetAsync(v2_list_out(c), 0, l.m, c->stream));
+    return TV_OK;
+}
+
+int v2_list_launch(tv_ctx* c, const V2List& l) {
+    const uint64_t m = l.m, W = c->L / TV_V2_LEAF_BYTES;
+    uint32_t* d = c->d_v2_list.get<uint32_t>();
+    TvV2List p{};
+    p.data = c->d_payload;
+    p.stride = c->stride;
+    p.m = (uint32_t)m;
+    while ((1ull << p.logW) < W) p.logW++;
+    p.rows = d;
+    p.bytes = d + m;
+    p.widths = d + 2 * m;
+    p.expect = d + 3 * m;
+    p.out_bytes = v2_list_out(c);
+    TV_HIP(c, tv_v2_launch_list(p, c->stream, &c->last_workgroups));
+    return TV_OK;
+}
+
+int v2_list_download(tv_ctx* c, V2List& l) {
+    TV_HIP(c, hipMemcpyAsync(l.ok.data(), v2_list_out(c), l.m, hipMemcpyDeviceToHost, c->stream));
+    return TV_OK;
+}
+
+void v2_list_scatter(const V2List& l, uint8_t* ok_out) {
+    for (uint64_t e = 0; e < l.m; e++) ok_out[l.origin[e]] = l.ok[e];
+}
+
+}  // namespace tvi
+
 extern "C" {
 
 int tv_v2_set_pieces(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const uint32_t* tree_leaves,
@@ -335,70 +417,34 @@ int tv_v2_verify_list(tv_ctx* c, uint64_t n, const uint64_t* pieces, const uint3
                                      "this layout is windowed (the shard exceeds the device budget)");
     if (n == 0) return TV_OK;
     if (!pieces || !piece_bytes || !tree_leaves || !hashes || !ok_out) return fail(c, TV_ERR_ARG, "NULL argument");
-    if (n >= 0xFFFFFF00ull) return fail(c, TV_ERR_ARG, "list too long");
-    if (!v2_piece_length_ok(c->L))
-        return fail(c, TV_ERR_ARG, "a v2 piece length is a power of two >= %d (the layout has %llu)", TV_V2_LEAF_BYTES,
-                    (unsigned long long)c->L);
-    const uint64_t W = c->L / TV_V2_LEAF_BYTES;
-    if (W > (1ull << TV_V2_LIST_MAX_LOGW))
-        return fail(c, TV_ERR_ARG, "tv_v2_verify_list takes pieces of up to %llu bytes (the layout has %llu)",
-                    (unsigned long long)TV_V2_LEAF_BYTES << TV_V2_LIST_MAX_LOGW, (unsigned long long)c->L);
     // every entry is checked before anything is launched or freed: a refused call changes nothing
-    rc = v2_check_entries(c, n, pieces, piece_bytes, tree_leaves);
+    rc = v2_list_check(c, "tv_v2_verify_list", n, pieces, piece_bytes, tree_leaves);
     if (rc) return rc;
-    // The entries launched: every listed piece, or, in a slot pool, the listed pieces that hold a slot (the others
-    // were never staged: 0).  origin[e] = the entry's index in the caller's arrays.
-    std::vector<uint64_t> origin;
-    origin.reserve(n);
-    for (uint64_t k = 0; k < n; k++) {
-        if (list_held(c, pieces[k] - c->first)) origin.push_back(k);
-        else ok_out[k] = 0;
-    }
-    const uint64_t m = origin.size();
-    std::vector<uint32_t> tab(11 * m);   // rows, bytes, widths, expected root words [8][m] (big-endian values)
-    for (uint64_t e = 0; e < m; e++) {
-        const uint64_t k = origin[e], j = pieces[k] - c->first;
-        tab[e] = list_row(c, j);
-        tab[m + e] = piece_bytes[k];
-        tab[2 * m + e] = tree_leaves[k];
-        digest_pack(hashes + 32 * k, 8, tab.data() + 3 * m, m, e);
-    }
-    std::vector<uint8_t> ok_launch(m);
+    V2List l;
+    v2_list_plan(c, n, pieces, piece_bytes, tree_leaves, hashes, ok_out, &l);
     TV_HIP(c, hipSetDevice(c->device));
-    if (m) {
+    if (l.m) {
         DrainGuard drain(c);  // after the host vectors: their H2D / D2H copies end before they go
-        // (11 table words and 4 out bytes per entry)
-        rc = grow_buf(c, c->d_v2_list, m, false, std::max<uint64_t>(m, 1024));
+        rc = v2_list_reserve(c, l);
         if (rc) return rc;
-        uint32_t* d = c->d_v2_list.get<uint32_t>();
-        uint8_t* d_ok = reinterpret_cast<uint8_t*>(d + 11 * c->d_v2_list.cap);
         TV_HIP(c, hipEventRecord(c->ev_call0, c->stream));
-        TV_HIP(c, hipMemcpyAsync(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
-        // fail closed: an entry the launch does not write reads as 0
-        TV_HIP(c, hipMemsetAsync(d_ok, 0, m, c->stream));
-        TvV2List p{};
-        p.data = c->d_payload;
-        p.stride = c->stride;
-        p.m = (uint32_t)m;
-        while ((1ull << p.logW) < W) p.logW++;
-        p.rows = d;
-        p.bytes = d + m;
-        p.widths = d + 2 * m;
-        p.expect = d + 3 * m;
-        p.out_bytes = d_ok;
+        rc = v2_list_upload(c, l);
+        if (rc) return rc;
         TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
-        TV_HIP(c, tv_v2_launch_list(p, c->stream, &c->last_workgroups));
+        rc = v2_list_launch(c, l);
+        if (rc) return rc;
         TV_HIP(c, hipEventRecord(c->ev_k1, c->stream));
-        TV_HIP(c, hipMemcpyAsync(ok_launch.data(), d_ok, m, hipMemcpyDeviceToHost, c->stream));
+        rc = v2_list_download(c, l);
+        if (rc) return rc;
         TV_HIP(c, hipEventRecord(c->ev_call1, c->stream));
         TV_HIP(c, hipEventSynchronize(c->ev_call1));
     } else {
         c->last_workgroups = 0;
     }
-    for (uint64_t e = 0; e < m; e++) ok_out[origin[e]] = ok_launch[e];
+    v2_list_scatter(l, ok_out);
     list_zero_unread(c, n, pieces, ok_out);
     list_release(c, n, pieces);
-    return list_finish(c, TV_KERNEL_V2_LIST, m);
+    return list_finish(c, TV_KERNEL_V2_LIST, l.m);
 }
 
 int tv_v2_leaf_hashes(tv_ctx* c, uint64_t n, const uint64_t* pieces, const uint32_t* piece_bytes,

@@ -6,6 +6,88 @@
 
 using namespace tvi;
 
+namespace tvi {
+
+// ---- the launch parts of tv_verify_list (tv_ctx.h: V1List), shared with tv_hybrid_verify_list ---------------------------
+
+// The entries launched: every listed piece, or, in a slot pool, the listed pieces that hold a slot (the others were
+// never staged: 0), in tv_plan.h list_plan's order (a short last piece in waves of its own).
+int v1_list_plan(tv_ctx* c, uint64_t n, const uint64_t* pieces, uint8_t* ok_out, V1List* l) {
+    std::vector<uint32_t> local(n);
+    for (uint64_t k = 0; k < n; k++) {
+        const int rc = list_in_shard(c, pieces[k]);
+        if (rc) return rc;
+        local[k] = (uint32_t)(pieces[k] - c->first);
+    }
+    std::vector<uint8_t> held(c->slots ? n : 0);
+    for (uint64_t k = 0; k < held.size(); k++) {
+        held[k] = list_held(c, local[k]);
+        if (!held[k]) ok_out[k] = 0;
+    }
+    const bool short_last = c->first + c->count == c->P && piece_len(c, c->P - 1) != c->L;
+    list_plan(n, local.data(), c->slots ? held.data() : nullptr, short_last ? c->count - 1 : UINT64_MAX, &l->launch,
+              &l->origin);
+    l->m = l->launch.size();
+    if (c->slots)  // the rows: each entry's slot (the kernels read piece launch[j]'s bytes from slot rows[j])
+        for (uint64_t j = 0; j < l->m; j++) l->launch.push_back(list_row(c, l->launch[j]));
+    l->ok.assign(l->m, 0);
+    return TV_OK;
+}
+
+int v1_list_reserve(tv_ctx* c, const V1List& l) {
+    int rc = grow_buf(c, c->d_list, l.m, false, std::max<uint64_t>(l.m, 1024));
+    if (!rc) rc = grow_buf(c, c->d_list_out, l.m, false, std::max<uint64_t>(l.m, 1024));
+    return rc;
+}
+
+int v1_list_upload(tv_ctx* c, const V1List& l) {
+    TV_HIP(c, hipMemcpyAsync(c->d_list.ptr, l.launch.data(), l.launch.size() * 4, hipMemcpyHostToDevice, c->stream));
+    return TV_OK;
+}
+
+int v1_list_launch(tv_ctx* c, const V1List& l, int* kernel_out) {
+    const uint64_t m = l.m;
+    uint32_t* d_list = c->d_list.get<uint32_t>();
+    TvPieces p = resident_launch(c);
+    p.n = (uint32_t)m;
+    p.n_main = (uint32_t)m;
+    p.idx = d_list;
+    p.rows = c->slots ? d_list + m : nullptr;
+    p.clock = nullptr;
+    p.out_bytes = c->d_list_out.get<uint8_t>();
+    // twin (two lanes per piece) while its 2-wave workgroups fit two per CU, then split (rounds + helper pair,
+    // ~30 % shorter serial stream per block than lane) while one pair per CU suffices, like choose_kernel;
+    // the lane list kernel for longer lists
+    const int kernel = (c->kernel_opt == TV_KERNEL_LANE || c->kernel_opt == TV_KERNEL_SPLIT ||
+                        c->kernel_opt == TV_KERNEL_TWIN)
+                           ? c->kernel_opt
+                           : (m <= 64 * (uint64_t)c->cus ? TV_KERNEL_TWIN : (m <= 256 * 64 ? TV_KERNEL_SPLIT : TV_KERNEL_LANE));
+    // Companions (as resident launches) only for a list that gives every CU a workgroup: a shorter one would
+    // fill 2 x CUs workgroups with copies re-hashing the same few pieces (a 1-piece flush: 512 copies) for a
+    // ~4 % shorter flush (r03 latency: tools/latency_probe.py)
+    const uint64_t list_wgs = (m + 31) / 32;
+    if (kernel == TV_KERNEL_TWIN && (c->twin_fill == 2 || ((c->twin_fill == 1 || c->twin_fill == 3) &&
+                                                            list_wgs >= (uint64_t)c->cus && companions_on(c)))) {
+        p.fill_to = 2u * (uint32_t)c->cus;
+        p.fill_all = c->fill_all ? 1u : 0u;
+    }
+    TV_HIP(c, tv_launch_verify_list(p, kernel, c->stream, &c->last_workgroups));
+    *kernel_out = kernel;
+    return TV_OK;
+}
+
+int v1_list_download(tv_ctx* c, V1List& l) {
+    TV_HIP(c, hipMemcpyAsync(l.ok.data(), c->d_list_out.ptr, l.m, hipMemcpyDeviceToHost, c->stream));
+    return TV_OK;
+}
+
+void v1_list_scatter(const V1List& l, uint8_t* ok_out) {
+    for (uint64_t i = 0; i < l.m; i++)
+        if (l.origin[i] >= 0) ok_out[l.origin[i]] = l.ok[i];
+}
+
+}  // namespace tvi
+
 extern "C" {
 
 int tv_verify(tv_ctx* c, const uint8_t* avail_bits, uint8_t* bitfield_out) {
@@ -60,74 +142,31 @@ int tv_verify_list(tv_ctx* c, const uint64_t* pieces, uint64_t n, uint8_t* ok_ou
     if (c->win)
         return fail(c, TV_ERR_STATE, "tv_verify_list needs the shard resident or a slot pool (TV_OPT_LIST_SLOTS); "
                                      "this layout is windowed (the shard exceeds the device budget)");
-    std::vector<uint32_t> local(n);
-    for (uint64_t k = 0; k < n; k++) {
-        rc = list_in_shard(c, pieces[k]);
-        if (rc) return rc;
-        local[k] = (uint32_t)(pieces[k] - c->first);
-    }
-    // The entries launched: every listed piece, or, in a slot pool, the listed pieces that hold a slot (the others
-    // were never staged: 0), in tv_plan.h list_plan's order (a short last piece in waves of its own).
-    std::vector<uint8_t> held(c->slots ? n : 0);
-    for (uint64_t k = 0; k < held.size(); k++) {
-        held[k] = list_held(c, local[k]);
-        if (!held[k]) ok_out[k] = 0;
-    }
-    const bool short_last = c->first + c->count == c->P && piece_len(c, c->P - 1) != c->L;
-    std::vector<uint32_t> launch;  // shard-relative pieces in launch order (then, for a slot pool, their slots)
-    std::vector<int64_t> origin;   // launch position -> index in `pieces` (-1 = padding)
-    list_plan(n, local.data(), c->slots ? held.data() : nullptr, short_last ? c->count - 1 : UINT64_MAX, &launch,
-              &origin);
-    const uint64_t m = launch.size();
-    if (c->slots)  // the rows: each entry's slot (the kernels read piece launch[j]'s bytes from slot rows[j])
-        for (uint64_t j = 0; j < m; j++) launch.push_back(list_row(c, launch[j]));
-    std::vector<uint8_t> ok_launch(m);
+    V1List l;
+    rc = v1_list_plan(c, n, pieces, ok_out, &l);
+    if (rc) return rc;
     TV_HIP(c, hipSetDevice(c->device));
     int kernel = 0;
-    if (m) {
+    if (l.m) {
         DrainGuard drain(c);  // after the host vectors: their H2D / D2H copies end before they go
-        rc = grow_buf(c, c->d_list, m, false, std::max<uint64_t>(m, 1024));
-        if (!rc) rc = grow_buf(c, c->d_list_out, m, false, std::max<uint64_t>(m, 1024));
+        rc = v1_list_reserve(c, l);
         if (rc) return rc;
-        uint32_t* d_list = c->d_list.get<uint32_t>();
-        uint8_t* d_ok = c->d_list_out.get<uint8_t>();
         TV_HIP(c, hipEventRecord(c->ev_call0, c->stream));
-        TV_HIP(c, hipMemcpyAsync(d_list, launch.data(), launch.size() * 4, hipMemcpyHostToDevice, c->stream));
-        TvPieces p = resident_launch(c);
-        p.n = (uint32_t)m;
-        p.n_main = (uint32_t)m;
-        p.idx = d_list;
-        p.rows = c->slots ? d_list + m : nullptr;
-        p.clock = nullptr;
-        p.out_bytes = d_ok;
+        rc = v1_list_upload(c, l);
+        if (rc) return rc;
         TV_HIP(c, hipEventRecord(c->ev_k0, c->stream));
-        // twin (two lanes per piece) while its 2-wave workgroups fit two per CU, then split (rounds + helper pair,
-        // ~30 % shorter serial stream per block than lane) while one pair per CU suffices, like choose_kernel;
-        // the lane list kernel for longer lists
-        kernel = (c->kernel_opt == TV_KERNEL_LANE || c->kernel_opt == TV_KERNEL_SPLIT ||
-                  c->kernel_opt == TV_KERNEL_TWIN)
-                     ? c->kernel_opt
-                     : (m <= 64 * (uint64_t)c->cus ? TV_KERNEL_TWIN : (m <= 256 * 64 ? TV_KERNEL_SPLIT : TV_KERNEL_LANE));
-        // Companions (as resident launches) only for a list that gives every CU a workgroup: a shorter one would
-        // fill 2 x CUs workgroups with copies re-hashing the same few pieces (a 1-piece flush: 512 copies) for a
-        // ~4 % shorter flush (r03 latency: tools/latency_probe.py)
-        const uint64_t list_wgs = (m + 31) / 32;
-        if (kernel == TV_KERNEL_TWIN && (c->twin_fill == 2 || ((c->twin_fill == 1 || c->twin_fill == 3) &&
-                                                                list_wgs >= (uint64_t)c->cus && companions_on(c)))) {
-            p.fill_to = 2u * (uint32_t)c->cus;
-            p.fill_all = c->fill_all ? 1u : 0u;
-        }
-        TV_HIP(c, tv_launch_verify_list(p, kernel, c->stream, &c->last_workgroups));
+        rc = v1_list_launch(c, l, &kernel);
+        if (rc) return rc;
         TV_HIP(c, hipEventRecord(c->ev_k1, c->stream));
-        TV_HIP(c, hipMemcpyAsync(ok_launch.data(), d_ok, m, hipMemcpyDeviceToHost, c->stream));
+        rc = v1_list_download(c, l);
+        if (rc) return rc;
         TV_HIP(c, hipEventRecord(c->ev_call1, c->stream));
         TV_HIP(c, hipEventSynchronize(c->ev_call1));
     }
-    for (uint64_t i = 0; i < m; i++)
-        if (origin[i] >= 0) ok_out[origin[i]] = ok_launch[i];
+    v1_list_scatter(l, ok_out);
     list_zero_unread(c, n, pieces, ok_out);   // (recover_segment's marks)
     list_release(c, n, pieces);
-    return list_finish(c, kernel, m);
+    return list_finish(c, kernel, l.m);
 }
 
 int tv_hash(tv_ctx* c, uint8_t* digests_out) {

@@ -16,8 +16,12 @@ files are never looked for on disk, staged or read) and runs the SHA-1 kernel an
 
 They shard over `devices` as the v2 calls do.  The resident forms need every shard within the device budget;
 verify_stream_hybrid and stream=True run both hash sets over the chunk buffers of one stream instead
-(tv_hybrid_stream_begin / tv_hybrid_stream_file_table) and verify any size.  Not built: a hybrid list call for
-incremental verify on a slot pool.
+(tv_hybrid_stream_begin / tv_hybrid_stream_file_table) and verify any size.
+
+Pieces as they complete: verify_piece_hybrid(meta, index, data) -> (ok, v1_ok, v2_ok) checks one piece against both
+descriptions, and incremental.IncrementalVerifierHybrid batches completed pieces on a slot pool; both are one
+tv_hybrid_verify_list call (the pad range of each listed row zeroed on the device, then the SHA-1 list launch and the v2
+list launch over the same bytes).
 """
 from __future__ import annotations
 
@@ -31,7 +35,8 @@ from .metainfo_v2 import FileV2, MetainfoV2, V2Layout, parse_metainfo_v2
 from . import _native
 from .v2 import (_creation_layout, _file_hashes, _file_paths, _file_tree, _resident_layout, _source_files,
                  _stage_file_buffers, _stage_files_v2, _torrent, piece_length_for_v2)
-from .verify import _bits_shards, _file_options, _hash_shards, _layout, _safe_paths, _shard_avail, _stream_rows
+from .verify import (_PIECE_SLOT, _bits_shards, _context, _file_options, _hash_shards, _layout, _safe_paths,
+                     _shard_avail, _stream_rows)
 
 CREATED_BY = "torrent_amd make_torrent_hybrid"
 
@@ -226,6 +231,27 @@ def verify_files_hybrid(meta: MetainfoHybrid, dir_path: str, devices=None, threa
         return ctx.hybrid_verify()
 
     return HybridResult(*_bits_shards(devices, lay.n_pieces, shard, fields=3))
+
+
+def verify_piece_hybrid(meta: MetainfoHybrid, index: int, data) -> tuple:
+    """One piece of a hybrid torrent against both descriptions: (ok, v1_ok, v2_ok), ok = v1 AND v2.  `data` is the
+    piece's file bytes (layout.piece_bytes[index] of them; the pad's zeros are written on the device, never passed);
+    v1_ok: SHA-1 of the bytes and the pad zeros out to the piece's v1 length equals its `pieces` slice; v2_ok: the
+    merkle root equals the piece's expected hash.  Raises ValueError for an index out of range; a piece of the wrong
+    length is (False, False, False)."""
+    lay = meta.layout
+    if index < 0 or index >= lay.n_pieces:
+        raise ValueError(f"verify_piece_hybrid: invalid piece index {index}")
+    n = memoryview(data).nbytes
+    if n != lay.piece_bytes[index]:
+        return False, False, False
+    L = lay.piece_length
+    v1_len = min(L, meta.total_length - index * L)
+    with _context(0, _PIECE_SLOT) as ctx:      # its own context: never evicts a bulk call's payload
+        _layout(ctx, v1_len, L, 1, 0, 1, None, digests=meta.pieces[20 * index:20 * index + 20])
+        ctx.stage(0, data)
+        ok, v1, v2 = ctx.hybrid_verify_list([0], [n], [lay.tree_leaves[index]], lay.hashes[32 * index:32 * index + 32])
+        return bool(ok[0]), bool(v1[0]), bool(v2[0])
 
 
 def hash_files_hybrid(dir_path: str, piece_length: int, files: Optional[Sequence[tuple]] = None, devices=None,

@@ -36,6 +36,10 @@ merkle roots, each piece's tree inside one workgroup), whose serial unit is one 
 whatever the piece length (flush_cost_ms_v2), so its age bound does not grow with the piece length.
 merkle_v2.BlockRepairVerifierV2 extends it: a failed piece whose leaf layer is known keeps its good blocks and only
 the bad ones are named for re-download.
+
+IncrementalVerifierHybrid is the same for a hybrid torrent (hybrid.MetainfoHybrid): a flush is one
+tv_hybrid_verify_list call, both hashes of every pending piece from its one staging; a piece's have-bit is v1 AND v2,
+and `disagree` names the pieces exactly one description accepted.
 """
 from __future__ import annotations
 
@@ -265,21 +269,24 @@ class IncrementalVerifierV2(_Incremental):
                  on_verified: Optional[Callable[[int, bool], None]] = None, slots: Optional[int] = None):
         if len(layout.hashes) != 32 * layout.n_pieces:
             raise ValueError("the layout has no expected hashes (a creation-mode table)")
-        self.layout = layout
-        self.storage = storage
+        self._init_v2(layout, storage)
         P = layout.n_pieces
-        # start of each file in the unaligned concatenation: a file's length is where its last piece ends
-        ends = list(layout.file_first_piece[1:]) + [P]
-        self._file_start, pos = [], 0
-        for a, b in zip(layout.file_first_piece, ends):
-            self._file_start.append(pos)
-            if b > a:
-                pos += layout.piece_offset[b - 1] + layout.piece_bytes[b - 1]
         self._init_policy(P, shard, flush_pieces, flush_age_ms, flush_cost_ms_v2(layout.piece_length), on_verified,
                           slots)
         self.ctx = _native.Context(device)
         self.ctx.set_option(_native.TV_OPT_LIST_SLOTS, self.slots)
         self.ctx.set_layout(layout.total_length, layout.piece_length, P, self.first, self.count)
+
+    def _init_v2(self, layout: V2Layout, storage) -> None:
+        self.layout = layout
+        self.storage = storage
+        # start of each file in the unaligned concatenation: a file's length is where its last piece ends
+        ends = list(layout.file_first_piece[1:]) + [layout.n_pieces]
+        self._file_start, pos = [], 0
+        for a, b in zip(layout.file_first_piece, ends):
+            self._file_start.append(pos)
+            if b > a:
+                pos += layout.piece_offset[b - 1] + layout.piece_bytes[b - 1]
 
     def _validate(self, msg: PieceMsg) -> None:
         validate_received_block_v2(self.layout, msg)
@@ -298,3 +305,46 @@ class IncrementalVerifierV2(_Incremental):
         return self.ctx.v2_verify_list(pending, [lay.piece_bytes[i] for i in pending],
                                        [lay.tree_leaves[i] for i in pending],
                                        b"".join(lay.hashes[32 * i:32 * i + 32] for i in pending))
+
+
+# ---- hybrid torrents (v1 + v2 descriptions of one payload) -----------------------------------------------------------
+
+def flush_cost_ms_hybrid(piece_len: int) -> float:
+    """Estimated GPU time of one hybrid list flush: the SHA-1 list launch and the v2 list launch run one after the
+    other on one stream, so the two models' sum (the pad launch is not modelled: its cost depends on the tails)."""
+    return flush_cost_ms(piece_len) + flush_cost_ms_v2(piece_len)
+
+
+class IncrementalVerifierHybrid(IncrementalVerifierV2):
+    """IncrementalVerifier for a hybrid torrent (hybrid.MetainfoHybrid): the same methods and flush policy; a flush is
+    one tv_hybrid_verify_list call, which zeroes the pad range of every pending piece's slot and runs the SHA-1 list
+    launch and the v2 list launch over the same bytes.  Blocks are the v2 side's (validate_received_block_v2 against
+    meta.layout: a block lies inside the file bytes of its piece; pads are never received) and `storage` is addressed
+    as IncrementalVerifierV2 addresses it.  The slot pool is laid over the v1 space (meta.total_length, pads
+    included) with the v1 `pieces` string as its digests.  A piece's have-bit is v1 AND v2; `disagree` lists the pieces
+    exactly one description accepted, in the order they were found: the host should refuse the torrent for these."""
+
+    def __init__(self, meta, storage=None, device: int = 0,
+                 shard: Optional[Tuple[int, int]] = None, flush_pieces=_AUTO, flush_age_ms=_AUTO,
+                 on_verified: Optional[Callable[[int, bool], None]] = None, slots: Optional[int] = None):
+        layout = meta.layout
+        if len(layout.hashes) != 32 * layout.n_pieces:
+            raise ValueError("the layout has no expected hashes (a creation-mode table)")
+        self.meta = meta
+        self.disagree: List[int] = []
+        self._init_v2(layout, storage)
+        L = layout.piece_length
+        self._init_policy(layout.n_pieces, shard, flush_pieces, flush_age_ms, flush_cost_ms_hybrid(L), on_verified,
+                          slots)
+        self.ctx = _native.Context(device)
+        self.ctx.set_option(_native.TV_OPT_LIST_SLOTS, self.slots)
+        self.ctx.set_layout(meta.total_length, L, layout.n_pieces, self.first, self.count)
+        self.ctx.set_digests(meta.pieces)
+
+    def _verify_list(self, pending: List[int]) -> bytes:
+        lay = self.layout
+        ok, v1, v2 = self.ctx.hybrid_verify_list(pending, [lay.piece_bytes[i] for i in pending],
+                                                 [lay.tree_leaves[i] for i in pending],
+                                                 b"".join(lay.hashes[32 * i:32 * i + 32] for i in pending))
+        self.disagree += [i for i, a, b in zip(pending, v1, v2) if a != b and i not in self.disagree]
+        return ok

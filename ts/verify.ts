@@ -82,6 +82,11 @@ const SYMBOLS = {
     nonblocking: true,
   },
   tv_hybrid_hash: { parameters: ["pointer", "pointer", "pointer"], result: "i32", nonblocking: true },
+  tv_hybrid_verify_list: {
+    parameters: ["pointer", "u64", "pointer", "pointer", "pointer", "pointer", "pointer", "pointer", "pointer", "i32"],
+    result: "i32",
+    nonblocking: true,
+  },
   tv_hybrid_stream_begin: {
     parameters: ["pointer", "u64", "pointer", "pointer", "pointer", "pointer"],
     result: "i32",
