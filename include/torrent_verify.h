@@ -571,6 +571,54 @@ int tv_hybrid_stream_file_table(tv_ctx *ctx, uint64_t n_pieces, const uint32_t *
                                 uint64_t paths_bytes, const uint8_t *avail_bits, uint8_t *v1_bits_out,
                                 uint8_t *v2_bits_out, uint8_t *bitfield_out, int32_t *status_out);
 
+/*
+ * Streamed CREATION through the same bounded ring: the hashes of a new torrent without a resident shard.  The
+ * reference's only SHA-1 loop is its creator, and that creator streams: makeTorrent reads each file in pieceLength
+ * parts and hashes every part as it arrives (tools/make_torrent.ts:18-113 for a directory, :147-173 for one file;
+ * hashAndStore :28-31).  tv_hash / tv_v2_hash / tv_hybrid_hash need the whole shard in device memory first; these
+ * calls hash it while it arrives, within the device memory of the verify stream of the same kind.
+ *
+ * tv_stream_hash_begin (v1 pieces, piece.ts:16-19), tv_v2_stream_hash_begin (BEP 52 merkle pieces; the GLOBAL piece
+ * table as tv_v2_stream_begin takes it) and tv_hybrid_stream_hash_begin (both; the layout is the v1 space of the table,
+ * as for tv_hybrid_stream_begin) start a stream that is the verify stream of its kind in every respect but its end:
+ * the same geometry (TV_OPT_STREAM_CHUNK, TV_OPT_STREAM_ROWS, TV_OPT_RESIDENT_BUDGET), ring, chunk buffers, row rule
+ * and launches (the hybrid column pad launch included); tv_stream_next / _commit / _commit_from / _fill_synthetic /
+ * _abort serve it unchanged.  It needs no tv_set_digests, no expected roots and no availability: every piece is
+ * hashed (make_torrent.ts never skips one), and tv_stream_unreadable on it is TV_ERR_STATE (the stream stays active).
+ * The layout is set with TV_OPT_RESIDENT = 0 (a windowed layout is TV_ERR_STATE).  The last launch of each window
+ * stores where a verify stream's compares: the SHA-1 digests, and the merkle roots in place of the expected ones, so a
+ * creation stream holds no device memory beyond the verify stream's.
+ *
+ * tv_stream_hash_end writes what the resident calls write, in piece order: tv_hash's 20-byte digests
+ * (crypto.subtle.digest("SHA-1", ...), make_torrent.ts:28-31) into digests_out and tv_v2_hash's 32-byte roots into
+ * roots_out.  A v1 stream takes roots_out == NULL, a v2 stream digests_out == NULL, a hybrid stream both pointers; a
+ * required pointer that is NULL is TV_ERR_ARG and the stream is aborted.  Ending before the last column aborts
+ * (TV_ERR_STATE), as for tv_stream_end.  tv_stream_end or tv_hybrid_stream_end on a creation stream, and
+ * tv_stream_hash_end on a verify stream, are TV_ERR_STATE and abort the stream.  A refused call writes nothing to its
+ * outputs.  tv_last_timing, tv_last_kernel (the ids and launch counts of the verify streams),
+ * TV_COUNTER_LAST_WORKGROUPS and TV_COUNTER_LAST_STREAM_REQUESTS report as for the verify streams.
+ *
+ * The *_hash_file_table calls are those streams with the library's own readers as the producer, the file table as
+ * tv_stream_file_table / tv_v2_stream_file_table take it (the v2 and hybrid forms: the REAL files, each at its aligned
+ * offset).  Files are opened read-only, as the creator opens its sources (Deno.open(path), make_torrent.ts:78),
+ * whatever TV_OPT_OPEN_RW says, and the cold-file options apply as they do to verify.  Creation cannot skip a piece:
+ * if any byte of the shard cannot be read (a missing, unopenable or short file) the call returns TV_ERR_IO with
+ * status_out[k] = TV_ERR_IO for the file, the outputs untouched and the stream aborted; the ctx stays usable.
+ */
+int tv_stream_hash_begin(tv_ctx *ctx);
+int tv_v2_stream_hash_begin(tv_ctx *ctx, uint64_t n, const uint32_t *piece_bytes, const uint32_t *tree_leaves);
+int tv_hybrid_stream_hash_begin(tv_ctx *ctx, uint64_t n, const uint32_t *piece_bytes, const uint32_t *tree_leaves);
+int tv_stream_hash_end(tv_ctx *ctx, uint8_t *digests_out /* 20*shard_count */, uint8_t *roots_out /* 32*shard_count */);
+int tv_stream_hash_file_table(tv_ctx *ctx, uint64_t n, const uint64_t *lengths, const char *paths, uint64_t paths_bytes,
+                              uint8_t *digests_out, int32_t *status_out);
+int tv_v2_stream_hash_file_table(tv_ctx *ctx, uint64_t n_pieces, const uint32_t *piece_bytes, const uint32_t *tree_leaves,
+                                 uint64_t n_files, const uint64_t *lengths, const char *paths, uint64_t paths_bytes,
+                                 uint8_t *roots_out, int32_t *status_out);
+int tv_hybrid_stream_hash_file_table(tv_ctx *ctx, uint64_t n_pieces, const uint32_t *piece_bytes,
+                                     const uint32_t *tree_leaves, uint64_t n_files, const uint64_t *lengths,
+                                     const char *paths, uint64_t paths_bytes, uint8_t *digests_out, uint8_t *roots_out,
+                                     int32_t *status_out);
+
 /* Page-locked host memory for tv_verify_host / tv_stage sources.  A pinned source is read by
  * DMA directly (no staging memcpy); pageable memory goes through the library's pinned ring.
  * tv_host_register pins an existing range (e.g. a caller's buffer), tv_host_unregister undoes it. */

@@ -154,6 +154,13 @@ SYMBOLS = [
     ("tv_hybrid_stream_begin", _int, [_p, _u64, _p, _p, _p, _p]),
     ("tv_hybrid_stream_end", _int, [_p, _p, _p, _p]),
     ("tv_hybrid_stream_file_table", _int, [_p, _u64, _p, _p, _p, _u64, _p, _p, _u64, _p, _p, _p, _p, _p]),
+    ("tv_stream_hash_begin", _int, [_p]),
+    ("tv_v2_stream_hash_begin", _int, [_p, _u64, _p, _p]),
+    ("tv_hybrid_stream_hash_begin", _int, [_p, _u64, _p, _p]),
+    ("tv_stream_hash_end", _int, [_p, _p, _p]),
+    ("tv_stream_hash_file_table", _int, [_p, _u64, _p, _p, _u64, _p, _p]),
+    ("tv_v2_stream_hash_file_table", _int, [_p, _u64, _p, _p, _u64, _p, _p, _u64, _p, _p]),
+    ("tv_hybrid_stream_hash_file_table", _int, [_p, _u64, _p, _p, _u64, _p, _p, _u64, _p, _p, _p]),
     ("tv_stream_begin", _int, [_p, _p]),
     ("tv_stream_next", _int, [_p, _REQ]),
     ("tv_stream_commit", _int, [_p, _REQ]),
@@ -605,6 +612,76 @@ class Context:
                                       n, ln.ctypes.data, blob, len(blob), avail=avail, outs=3, tail=(st.ctypes.data,))
         del keep
         return (out, v1, v2), st[:n].tolist()
+
+    # -- streamed creation (tv_stream_hash_*): the verify streams' ring, the hashes out instead of a bitfield ----
+    def stream_hash_begin(self) -> None:
+        """tv_stream_hash_begin: a v1 stream that hashes instead of verifying (no set_digests, no availability); then
+        stream_next / stream_commit as after stream_begin, and stream_hash_end."""
+        self._v2_stream_bytes = None
+        self._check(self._L.tv_stream_hash_begin(self._h))
+        self._hash_stream = "v1"
+
+    def v2_stream_hash_begin(self, piece_bytes, tree_leaves) -> None:
+        """tv_v2_stream_hash_begin: v2_stream_begin's stream in creation mode (the GLOBAL piece table, no hashes)."""
+        pb, tl = _v2_arrays("v2_stream_hash_begin", piece_bytes, tree_leaves)
+        self._check(self._L.tv_v2_stream_hash_begin(self._h, len(pb), pb.ctypes.data, tl.ctypes.data))
+        self._v2_stream_bytes = pb
+        self._hash_stream = "v2"
+
+    def hybrid_stream_hash_begin(self, piece_bytes, tree_leaves) -> None:
+        """tv_hybrid_stream_hash_begin: hybrid_stream_begin's stream in creation mode (no set_digests, no hashes)."""
+        pb, tl = _v2_arrays("hybrid_stream_hash_begin", piece_bytes, tree_leaves)
+        self._check(self._L.tv_hybrid_stream_hash_begin(self._h, len(pb), pb.ctypes.data, tl.ctypes.data))
+        self._v2_stream_bytes = pb
+        self._hash_stream = "hybrid"
+
+    def _hash_outs(self, kind: str) -> tuple:
+        """(digests buffer or None, roots buffer or None) a creation stream of this kind writes, never empty."""
+        d = ctypes.create_string_buffer(max(1, 20 * self.shard_count)) if kind in ("v1", "hybrid") else None
+        r = ctypes.create_string_buffer(max(1, 32 * self.shard_count)) if kind in ("v2", "hybrid") else None
+        return d, r
+
+    def _hash_result(self, kind: str, d, r):
+        dg = d.raw[:20 * self.shard_count] if d is not None else None
+        rt = r.raw[:32 * self.shard_count] if r is not None else None
+        return (dg, rt) if kind == "hybrid" else (dg if kind == "v1" else rt)
+
+    def stream_hash_end(self):
+        """tv_stream_hash_end: what the resident creation calls return -- a v1 stream's 20-byte digests (as hash), a v2
+        stream's 32-byte roots (as v2_hash), a hybrid stream's (digests, roots) (as hybrid_hash)."""
+        kind = getattr(self, "_hash_stream", None) or "v1"
+        d, r = self._hash_outs(kind)
+        self._hash_stream = None
+        self._check(self._L.tv_stream_hash_end(self._h, d, r))
+        return self._hash_result(kind, d, r)
+
+    def _hash_table_call(self, kind: str, fn, head: tuple, what: str, lengths, paths) -> tuple:
+        n, ln, blob, st = _file_table(what, lengths, paths)
+        d, r = self._hash_outs(kind)
+        outs = tuple(b for b in (d, r) if b is not None)
+        rc = fn(self._h, *head, n, ln.ctypes.data, blob, len(blob), *outs, st.ctypes.data)
+        if rc == TV_ERR_IO:
+            return None, st[:n].tolist()
+        self._check(rc)
+        return self._hash_result(kind, d, r), st[:n].tolist()
+
+    def stream_hash_file_table(self, lengths, paths) -> tuple:
+        """tv_stream_hash_file_table: the shard's v1 digests from the files through the bounded ring (files opened
+        read-only).  -> (digests, per-file statuses); digests is None when a file is missing or short (TV_ERR_IO)."""
+        return self._hash_table_call("v1", self._L.tv_stream_hash_file_table, (), "stream_hash_file_table", lengths, paths)
+
+    def v2_stream_hash_file_table(self, piece_bytes, tree_leaves, lengths, paths) -> tuple:
+        """tv_v2_stream_hash_file_table: -> (piece roots or None, per-file statuses), as stream_hash_file_table."""
+        pb, tl = _v2_arrays("v2_stream_hash_file_table", piece_bytes, tree_leaves)
+        return self._hash_table_call("v2", self._L.tv_v2_stream_hash_file_table, (len(pb), pb.ctypes.data, tl.ctypes.data),
+                                     "v2_stream_hash_file_table", lengths, paths)
+
+    def hybrid_stream_hash_file_table(self, piece_bytes, tree_leaves, lengths, paths) -> tuple:
+        """tv_hybrid_stream_hash_file_table: -> ((digests, roots) or None, per-file statuses)."""
+        pb, tl = _v2_arrays("hybrid_stream_hash_file_table", piece_bytes, tree_leaves)
+        return self._hash_table_call("hybrid", self._L.tv_hybrid_stream_hash_file_table,
+                                     (len(pb), pb.ctypes.data, tl.ctypes.data), "hybrid_stream_hash_file_table", lengths,
+                                     paths)
 
     def stream_next(self) -> StreamReq:
         """The next request (req.rows == 0: every byte has been requested)."""

@@ -147,6 +147,10 @@ struct StreamState {
     // a hybrid stream (tv_hybrid_stream_begin): a v2 stream (v2 is set too) whose units are also hashed as v1 pieces,
     // after the column pad kernel; the v2 bits go to d_hy_bits, the v1 bits to d_out
     bool hybrid = false;
+    // a creation stream (tv_stream_hash_begin and its v2 and hybrid forms): the same units and launches, the last ones
+    // store instead of compare -- SHA-1 digests into d_hash, v2 roots into the hash rows of d_v2s_tab; it needs no
+    // digests, no expected roots and no availability, and ends with tv_stream_hash_end
+    bool hash = false;
     uint32_t v2_logc = 0, v2_logn = 0;   // log2 of the leaves per column (C / 16 KiB) and of the columns per piece (L / C)
     int launches = 0;                    // kernel launches so far, every kind of stream (tv_stream.hip unit_launch)
     std::vector<uint32_t> v2_bytes;      // shard-relative valid bytes of every piece: the requests' row lengths
@@ -354,7 +358,7 @@ struct tv_ctx {
     // rows, leaves, lens, hash words [8] (expected or out)
     DevBuf d_v2_blk{call_bufs, 48};
     // a v2 stream's device memory beyond the chunk buffers (tv_v2_stream_begin; kept for a later stream that fits)
-    DevBuf d_v2s_tab{call_bufs, 4};    // words, [11][count]: piece bytes, tree leaves, top-tree widths, expected [8] per window
+    DevBuf d_v2s_tab{call_bufs, 4};    // words, [11][count]: piece bytes, tree leaves, top-tree widths, expected (creation: computed) roots [8] per window
     DevBuf d_v2s_nodes{call_bufs, 4};  // words, a window's partial nodes: level buffers A [8][wn x ncol], B [8][wn x max(ncol/2, 1)]
     int v2_map_opt = 0;                // TV_OPT_V2_MAP: 0 auto, else TV_V2_MAP_*
     int v2_last_map = 0;               // the mapping the last v2 call's leaf kernel ran with

@@ -286,6 +286,27 @@ inline bool v2_file_starts(uint64_t n, const uint64_t* lengths, uint64_t L, std:
     return true;
 }
 
+// ---- a v2 stream's device table (tv_stream.hip: v2_stream_begin_locked, v2_top_launch, stream_hash_end_locked) --------
+//
+// One table of 11 words per shard piece: three rows of `count` words (piece bytes, tree leaves, top-tree widths), then
+// eight hash words per piece, SoA [8][wcount] window after window, so a window's finish launch sees a table of its own
+// (pitch wcount) at the window's base.  A verify stream holds the expected roots there (the host packs them), a
+// creation stream the roots its finish launches write (tv_stream_hash_end reads them back): the same words, so a
+// creation stream needs no further buffer.  Windows are wn pieces, the last one the rest.
+inline uint64_t v2s_tab_words(uint64_t count) { return 11 * count; }
+// the words of the hash region: eight per shard piece
+inline uint64_t v2s_hash_words(uint64_t count) { return 8 * count; }
+// the word of the table at which the hash rows of the window starting at shard piece j0 begin (j0 a multiple of wn)
+inline uint64_t v2s_hash_base(uint64_t count, uint64_t j0) { return 3 * count + 8 * j0; }
+// hash word q (0 .. 7) of shard piece j in the hash region (index from v2s_hash_base(count, 0))
+inline uint64_t v2s_hash_word(uint64_t count, uint64_t wn, uint64_t j, uint32_t q) {
+    const uint64_t j0 = j / wn * wn, wcount = std::min(wn, count - j0);
+    return 8 * j0 + (uint64_t)q * wcount + (j - j0);
+}
+// A window's top tree over the column nodes: level buffer A is [8][wcount x ncol] words, B follows it at this word
+// ([8][wcount x max(ncol / 2, 1)]); both fit v2_node_words(wn, ncol) of any window of the stream.
+inline uint64_t v2s_nodes_b_base(uint64_t wcount, uint64_t ncol) { return 8 * wcount * ncol; }
+
 // ---- the item list of a v2 block launch (tv_v2.hip: tv_v2_leaf_hashes, tv_v2_check_blocks) --------------------------
 //
 // Entry k is a piece of piece_bytes[k] valid bytes in a torrent whose full piece holds W blocks of 16 KiB.  Its block

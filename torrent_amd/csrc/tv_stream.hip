@@ -3,7 +3,9 @@
 // tv_v2_stream_begin / tv_v2_stream_file_table run BitTorrent v2 pieces through the same engine: one column-kernel
 // launch per unit and the window's top tree after its last column.  tv_hybrid_stream_begin /
 // tv_hybrid_stream_file_table run both hash sets of a hybrid torrent over each unit's chunk buffer: the column pad
-// kernel, the SHA-1 column launch, the v2 column launch.
+// kernel, the SHA-1 column launch, the v2 column launch.  tv_stream_hash_begin and its v2 and hybrid forms run each kind
+// in creation mode (StreamState::hash): the same units and launches, the last ones storing the hashes, which
+// tv_stream_hash_end hands out.
 //
 // The kinds share one row rule (stream_row_bytes), one geometry setter (set_geometry), one commit path
 // (stream_commit_locked over tv_plan.h for_row_copies) and one unit dispatch (unit_launch); the library's own reader
@@ -88,13 +90,15 @@ void budget_geometry(const tv_ctx* c, uint64_t budget, uint64_t min_win, uint64_
     stream_geometry(c->L, c->count, budget, min_win, kRingSlotBytes, kSlack, col, win);
 }
 
-// What both begin calls start with: a fresh state holding the availability bits.  false = the shard is empty and the
-// stream is active already: there is nothing to hash, the first tv_stream_next reports completion.
-static bool begin_state(tv_ctx* c, const uint8_t* avail_bits) {
+// What both begin calls start with: a fresh state holding the availability bits (a creation stream, `hash`, has none:
+// every piece is hashed).  false = the shard is empty and the stream is active already: there is nothing to hash, the
+// first tv_stream_next reports completion.
+static bool begin_state(tv_ctx* c, const uint8_t* avail_bits, bool hash = false) {
     StreamState& st = c->st;
     st = StreamState{};
+    st.hash = hash;
     st.av.assign((c->count + 7) / 8, 0xFF);
-    if (avail_bits) memcpy(st.av.data(), avail_bits, st.av.size());
+    if (avail_bits && !hash) memcpy(st.av.data(), avail_bits, st.av.size());
     st.active = c->count == 0;
     return !st.active;
 }
@@ -136,8 +140,8 @@ static void set_geometry(tv_ctx* c, uint64_t C, uint64_t wn, uint64_t req_bytes)
 // (The begin functions share begin_state, set_geometry, grow_chunks and begin_done; the HIP calls between them stay per
 // kind: a v2 begin synchronises the compute stream before it replaces buffers and after its table copy, v1 never.)
 int stream_begin_locked(tv_ctx* c, const uint8_t* avail_bits, uint64_t col_override = 0, uint64_t win_override = 0,
-                        uint64_t req_bytes = 0) {
-    if (!begin_state(c, avail_bits)) return TV_OK;
+                        uint64_t req_bytes = 0, bool hash = false) {
+    if (!begin_state(c, avail_bits, hash)) return TV_OK;
     if (stream_rows(c))  // whole pieces per row, windows of stream_row_window pieces
         set_geometry(c, (c->L + 63) / 64 * 64, stream_row_window(c), req_bytes);
     else                 // columns across the whole shard (or across windows of win_override pieces)
@@ -158,10 +162,13 @@ int stream_begin_locked(tv_ctx* c, const uint8_t* avail_bits, uint64_t col_overr
 // as v1 pieces (unit_launch): the SHA-1 column launches use the state of a v1 stream (the digests, d_state,
 // d_base_avail; bits into d_out), the v2 launches write a second bitfield, the first half of d_hy_bits (its sizing
 // rule: bit_words), cleared here so it fails closed.  The caller has also checked the digests and piece_bytes <= v1_len.
+//
+// hash (tv_v2_stream_hash_begin, tv_hybrid_stream_hash_begin): the same stream without expected roots (`hashes` is not
+// read): the hash rows of the table stay zero until the windows' finish launches write the roots there.
 int v2_stream_begin_locked(tv_ctx* c, const uint32_t* piece_bytes, const uint32_t* tree_leaves, const uint8_t* hashes,
-                           const uint8_t* avail_bits, uint64_t req_bytes = 0, bool hybrid = false) {
+                           const uint8_t* avail_bits, uint64_t req_bytes = 0, bool hybrid = false, bool hash = false) {
     StreamState& st = c->st;
-    const bool hashes_any = begin_state(c, avail_bits);
+    const bool hashes_any = begin_state(c, avail_bits, hash);
     st.v2 = true;
     st.hybrid = hybrid;
     st.kernel = hybrid ? TV_KERNEL_HYBRID_STREAM : TV_KERNEL_V2_STREAM;
@@ -175,7 +182,7 @@ int v2_stream_begin_locked(tv_ctx* c, const uint32_t* piece_bytes, const uint32_
     while ((1ull << st.v2_logn) < st.ncol) st.v2_logn++;
     TV_HIP(c, hipStreamSynchronize(c->stream));   // (nothing queued still reads the buffers replaced below)
     // (whole-piece columns run no level: the finish launch reads the column nodes themselves, level buffer A alone)
-    const uint64_t need_tab = 11 * c->count, need_nodes = st.ncol > 1 ? v2_node_words(wn, st.ncol) : 8 * wn;
+    const uint64_t need_tab = v2s_tab_words(c->count), need_nodes = st.ncol > 1 ? v2_node_words(wn, st.ncol) : 8 * wn;
     int rc = grow_chunks(c, st.row_pitch * wn + kSlack);
     if (!rc) rc = grow_buf(c, c->d_v2s_tab, need_tab, true, need_tab);
     if (!rc) rc = grow_buf(c, c->d_v2s_nodes, need_nodes, true, need_nodes);
@@ -191,7 +198,7 @@ int v2_stream_begin_locked(tv_ctx* c, const uint32_t* piece_bytes, const uint32_
         st.v2_bytes[j] = tab[j] = piece_bytes[i];
         tab[c->count + j] = tree_leaves[i];
         tab[2 * c->count + j] = std::max<uint32_t>(1, tree_leaves[i] >> st.v2_logc);
-        digest_pack(hashes + 32 * i, 8, tab.data() + 3 * c->count + 8 * j0, wcount, j - j0);
+        if (!hash) digest_pack(hashes + 32 * i, 8, tab.data() + v2s_hash_base(c->count, j0), wcount, j - j0);
     }
     TV_HIP(c, hipMemcpyAsync(c->d_v2s_tab.ptr, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
     TV_HIP(c, hipStreamSynchronize(c->stream));   // (tab is the call's own)
@@ -221,7 +228,8 @@ static int v2_column_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount) {
 }
 
 // After a v2 window's last column, its top tree over the column nodes (one level launch per doubling of the columns,
-// none when a column is a whole piece) and the finish launch into the window's bitfield words.
+// none when a column is a whole piece) and the finish launch into the window's bitfield words (a creation stream: the
+// roots into the window's hash rows of the table, [8][wcount] at its base).
 static int v2_top_launch(tv_ctx* c, uint64_t j0, uint64_t wcount) {
     StreamState& st = c->st;
     uint32_t* tab = c->d_v2s_tab.get<uint32_t>();
@@ -231,8 +239,9 @@ static int v2_top_launch(tv_ctx* c, uint64_t j0, uint64_t wcount) {
     p.piece_bytes = tab + j0;
     p.tree_leaves = tab + 2 * c->count + j0;
     p.nodes_a = c->d_v2s_nodes.get<uint32_t>();
-    p.nodes_b = p.nodes_a + 8 * wcount * st.ncol;
-    p.expect = tab + 3 * c->count + 8 * j0;
+    p.nodes_b = p.nodes_a + v2s_nodes_b_base(wcount, st.ncol);
+    if (st.hash) p.roots = tab + v2s_hash_base(c->count, j0);
+    else p.expect = tab + v2s_hash_base(c->count, j0);
     // (availability: st.av, applied at the end with the unreadable pieces; a hybrid stream's v2 bits: d_hy_bits)
     p.out64 = (st.hybrid ? c->d_hy_bits.get<uint64_t>() : c->d_out) + j0 / 64;
     p.out_words = (uint32_t)((wcount + 63) / 64);
@@ -240,14 +249,16 @@ static int v2_top_launch(tv_ctx* c, uint64_t j0, uint64_t wcount) {
         TV_HIP(c, tv_v2_launch_level(p, l, st.v2_logn, c->stream));
         st.launches++;
     }
-    TV_HIP(c, tv_v2_launch_finish(p, false, c->stream));
+    TV_HIP(c, tv_v2_launch_finish(p, st.hash, c->stream));
     st.launches++;
     return TV_OK;
 }
 
 // A completed unit's SHA-1 column launch: the window's pieces (the shard's digest / state rows from j0; bitfield words
 // from j0 / 64: a window of a multi-window stream is a multiple of 64 pieces) over bytes [offset, offset + C) of each,
-// the chaining values carried in d_state; the window's last column pads, compares and writes the bits.
+// the chaining values carried in d_state; the window's last column pads, compares and writes the bits (a creation
+// stream: stores the digests in the shard's d_hash rows from j0, window_launch's out_digests [5][count], and is given
+// neither digests nor availability).
 static int v1_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount, uint64_t offset) {
     StreamState& st = c->st;
     const bool last = st.unit % st.ncol + 1 == st.ncol;
@@ -259,10 +270,15 @@ static int v1_unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount, uint
     p.blk_begin = offset / 64;
     p.blk_end = last ? UINT64_MAX : (offset + st.C) / 64;
     p.finalize = last ? 1 : 0;
+    if (st.hash) {
+        p.digests = nullptr;
+        p.avail64 = nullptr;
+        p.out64 = nullptr;
+    }
     const int kernel = choose_kernel_n(c, wcount, p.n_main < p.n);
     if (!st.v2) st.kernel = kernel;   // (tv_last_kernel: a hybrid stream reports its own id)
     p.lane_pairs = lane_pairs_for(c, p.n);
-    TV_HIP(c, tv_launch_verify(p, kernel, false, c->stream, c->split_pairs, &c->last_workgroups));
+    TV_HIP(c, tv_launch_verify(p, kernel, st.hash, c->stream, c->split_pairs, &c->last_workgroups));
     st.launches++;
     return TV_OK;
 }
@@ -386,6 +402,10 @@ int stream_commit_locked(tv_ctx* c, const tv_stream_req* req, const uint8_t* src
 int stream_end_locked(tv_ctx* c, uint8_t* bitfield_out, uint8_t* v1_out = nullptr, uint8_t* v2_out = nullptr) {
     StreamState& st = c->st;
     if (!st.active) return fail(c, TV_ERR_STATE, "tv_stream_begin has not been called");
+    if (st.hash) {
+        stream_abort_locked(c);
+        return fail(c, TV_ERR_STATE, "the active stream is a creation stream (it ends with tv_stream_hash_end); aborted");
+    }
     if (st.outstanding || st.unit < st.nunits) {
         const unsigned long long done = st.unit, all = st.nunits;
         stream_abort_locked(c);
@@ -427,6 +447,66 @@ int stream_end_locked(tv_ctx* c, uint8_t* bitfield_out, uint8_t* v1_out = nullpt
     c->last_stream_requests = st.seq;   // (an empty shard: 0)
     st = StreamState{};
     return TV_OK;
+}
+
+// The end of a creation stream (tv_stream_hash_end): what the resident calls hand back -- tv_hash's digests out of
+// d_hash (a v1 or hybrid stream), tv_v2_hash's roots out of the table's hash rows (a v2 or hybrid stream), through the
+// digest codec, in piece order.  Every refusal comes before the first byte is written.
+int stream_hash_end_locked(tv_ctx* c, uint8_t* digests_out, uint8_t* roots_out) {
+    StreamState& st = c->st;
+    if (!st.active) return fail(c, TV_ERR_STATE, "tv_stream_hash_begin has not been called");
+    if (!st.hash) {
+        stream_abort_locked(c);
+        return fail(c, TV_ERR_STATE, "the active stream is a verify stream (it ends with tv_stream_end); aborted");
+    }
+    if (st.outstanding || st.unit < st.nunits) {
+        const unsigned long long done = st.unit, all = st.nunits;
+        stream_abort_locked(c);
+        return fail(c, TV_ERR_STATE, "stream ended before its last column (%llu of %llu hashed); aborted", done, all);
+    }
+    const bool v1 = !st.v2 || st.hybrid, v2 = st.v2;
+    if (c->count && ((v1 && !digests_out) || (v2 && !roots_out))) {
+        stream_abort_locked(c);
+        return fail(c, TV_ERR_ARG, "%s is NULL", v1 && !digests_out ? "digests_out" : "roots_out");
+    }
+    if (!c->count) {
+        c->last_stream_requests = st.seq;   // (an empty shard: 0)
+        st = StreamState{};
+        return TV_OK;
+    }
+    std::vector<uint32_t> soa1(v1 ? 5 * c->count : 0), soa2(v2 ? v2s_hash_words(c->count) : 0);
+    int rc;
+    {
+        DrainGuard drain(c);  // declared after the vectors: their copies end before they go, also on error paths
+        rc = [&]() -> int {
+            TV_HIP(c, hipEventRecord(c->ev_k1, c->stream));
+            if (v1)
+                TV_HIP(c, hipMemcpyAsync(soa1.data(), c->d_hash, soa1.size() * 4, hipMemcpyDeviceToHost, c->stream));
+            if (v2)
+                TV_HIP(c, hipMemcpyAsync(soa2.data(), c->d_v2s_tab.get<uint32_t>() + v2s_hash_base(c->count, 0),
+                                         soa2.size() * 4, hipMemcpyDeviceToHost, c->stream));
+            TV_HIP(c, hipEventRecord(c->ev_call1, c->stream));
+            TV_HIP(c, hipEventSynchronize(c->ev_call1));
+            return TV_OK;
+        }();
+    }
+    if (rc) {
+        stream_abort_locked(c);
+        return rc;
+    }
+    for (uint64_t j = 0; j < c->count; j++) {
+        if (v1) digest_unpack(soa1.data(), c->count, j, 5, digests_out + 20 * j);
+        if (v2) {   // the window's own [8][wcount] rows
+            const uint64_t j0 = j / st.wn * st.wn, wcount = std::min(st.wn, c->count - j0);
+            digest_unpack(soa2.data() + v2s_hash_word(c->count, st.wn, j0, 0), wcount, j - j0, 8, roots_out + 32 * j);
+        }
+    }
+    c->last_kernel = st.kernel;
+    c->last_launches = st.launches;
+    rc = finish_timing(c);
+    c->last_stream_requests = st.seq;
+    st = StreamState{};
+    return rc;
 }
 
 // Public stream calls: a HIP failure leaves the stream unusable, so it is aborted (the ctx stays usable).
@@ -486,8 +566,10 @@ struct FdCache {
     std::unique_ptr<std::atomic<bool>[]> no_direct;
     int cached = 0;
     std::mutex mu;
-    FdCache(const tv_ctx* c, uint64_t n, const uint64_t* lengths, const std::vector<const char*>& path)
-        : c(c), lengths(lengths), path(path), fds(n, -1), dfds(n, -1), no_direct(new std::atomic<bool>[n ? n : 1]()) {}
+    const bool rw;   // TV_OPT_OPEN_RW; a creation call's readers always open read-only (make_torrent.ts:78)
+    FdCache(const tv_ctx* c, uint64_t n, const uint64_t* lengths, const std::vector<const char*>& path, bool read_only)
+        : c(c), lengths(lengths), path(path), fds(n, -1), dfds(n, -1), no_direct(new std::atomic<bool>[n ? n : 1]()),
+          rw(c->open_rw && !read_only) {}
     ~FdCache() {
         for (int x : fds)
             if (x >= 0) close(x);
@@ -508,7 +590,7 @@ struct FdCache {
             if (fds[k] != -1) return cached_fd(k, dfd);
         }
         int e = 0;
-        const int d = path[k][0] ? open_file(path[k], c->open_rw, &e) : -1;
+        const int d = path[k][0] ? open_file(path[k], rw, &e) : -1;
         std::lock_guard<std::mutex> fg(mu);
         if (fds[k] != -1) {   // another reader opened it meanwhile
             if (d >= 0) close(d);
@@ -522,7 +604,7 @@ struct FdCache {
             cached++;
             fds[k] = d;
             if (c->file_odirect && lengths[k] >= (1u << 20)) {
-                if (is_cold(cached_fraction(d, 0, lengths[k]))) dfds[k] = open_direct(path[k], c->open_rw);
+                if (is_cold(cached_fraction(d, 0, lengths[k]))) dfds[k] = open_direct(path[k], rw);
                 if (dfds[k] >= 0) *dfd = dfds[k];
             }
             return d;
@@ -565,13 +647,15 @@ static uint64_t read_segment(tv_ctx* c, FdCache& files, uint64_t k, uint64_t fo,
 // The reader loop: begin(cold) starts the stream (its geometry and availability are the caller's) once the shard's files
 // are known to be mostly in the page cache or not.  The lane-0 pool fills each request's ring slot: a row's bytes
 // (stream_row_bytes) are walked over the file table (tv_plan.h walk_row_files) and read segment by segment; a row that
-// a missing, unopenable or short file cannot fill makes its piece unreadable and the file's status TV_ERR_IO.
+// a missing, unopenable or short file cannot fill makes its piece unreadable and the file's status TV_ERR_IO.  end():
+// the stream's end call, which hands the results out.  hash: a creation call -- the files are opened read-only, and a
+// row that cannot be filled ends the call (creation cannot skip a piece): TV_ERR_IO after the statuses are set, the
+// stream aborted, end() never called.
 int stream_files_locked(tv_ctx* c, uint64_t n, const uint64_t* lengths, const std::vector<const char*>& path,
                         const std::vector<uint64_t>& start, const std::function<int(bool)>& begin,
-                        uint8_t* bitfield_out, int32_t* status_out, uint8_t* v1_out = nullptr,
-                        uint8_t* v2_out = nullptr) {
+                        int32_t* status_out, const std::function<int()>& end, bool hash = false) {
     const bool cold = shard_is_cold(c, n, lengths, path, start);
-    FdCache files(c, n, lengths, path);
+    FdCache files(c, n, lengths, path, hash);
     const int readers = cold ? (c->stream_cold_readers ? c->stream_cold_readers : 2 * c->file_threads) : c->file_threads;
     DrainGuard drain(c);  // (the ring's copies and the column kernels are done when the call returns)
     int rc = begin(cold);
@@ -581,6 +665,7 @@ int stream_files_locked(tv_ctx* c, uint64_t n, const uint64_t* lengths, const st
     }
     std::vector<std::atomic<int32_t>> file_err(n);
     for (auto& e : file_err) e.store(TV_OK);
+    bool unread = false;   // a row could not be filled
     for (;;) {
         tv_stream_req req;
         rc = stream_next_locked(c, &req);
@@ -603,7 +688,11 @@ int stream_files_locked(tv_ctx* c, uint64_t n, const uint64_t* lengths, const st
             if (w != kRowWalked) row_bad[q] = 1;
         });
         for (uint64_t q = 0; q < req.rows; q++)
-            if (row_bad[q]) clear_bit(c->st.av.data(), req.piece + q - c->first);
+            if (row_bad[q]) {
+                clear_bit(c->st.av.data(), req.piece + q - c->first);
+                unread = true;
+            }
+        if (hash && unread) break;   // (the lent slot goes back with the abort)
         rc = stream_commit_locked(c, &req, nullptr, 0, true, req.rows);
         if (rc) break;
     }
@@ -613,20 +702,28 @@ int stream_files_locked(tv_ctx* c, uint64_t n, const uint64_t* lengths, const st
         stream_abort_locked(c);
         return rc;
     }
-    return stream_end_locked(c, bitfield_out, v1_out, v2_out);
+    if (hash && unread) {
+        stream_abort_locked(c);
+        return fail(c, TV_ERR_IO, "a file is missing, unopenable or shorter than its declared length (status_out); "
+                                  "nothing was hashed out");
+    }
+    return end();
 }
 
 // What tv_v2_stream_begin and tv_hybrid_stream_begin (and their file-table forms) check before anything changes: the
 // layout, the GLOBAL piece table and its hashes; a hybrid stream also needs the digests (TV_ERR_STATE) and a layout that
 // is the v1 space of the table: piece_bytes <= v1_len for every shard piece (tv_hybrid_verify's rule and text).
+// hash: the creation forms (tv_v2_stream_hash_begin, tv_hybrid_stream_hash_begin) need neither digests nor hashes.
 int v2_stream_check(tv_ctx* c, bool hybrid, uint64_t n, const uint32_t* piece_bytes, const uint32_t* tree_leaves,
-                    const uint8_t* hashes) {
-    const char* what = hybrid ? "tv_hybrid_stream_begin" : "tv_v2_stream_begin";
-    int rc = require_layout(c, hybrid);
+                    const uint8_t* hashes, bool hash = false) {
+    const char* what = hybrid ? (hash ? "tv_hybrid_stream_hash_begin" : "tv_hybrid_stream_begin") : "tv_v2_stream_begin";
+    int rc = require_layout(c, hybrid && !hash);
     if (rc) return rc;
     rc = v2_check_table(c, n, piece_bytes, tree_leaves);
     if (rc) return rc;
-    if (n && !hashes) return fail(c, TV_ERR_ARG, "NULL argument");
+    if (n && !hashes && !hash) return fail(c, TV_ERR_ARG, "NULL argument");
+    if (hash && c->win)
+        return fail(c, TV_ERR_STATE, "a creation stream needs a layout without windows (TV_OPT_RESIDENT = 0)");
     if (!hybrid) return TV_OK;
     if (c->L > kHybridMaxL)
         return fail(c, TV_ERR_ARG, "%s takes piece lengths up to %llu bytes (the layout has %llu)", what,
@@ -641,13 +738,13 @@ int v2_stream_check(tv_ctx* c, bool hybrid, uint64_t n, const uint32_t* piece_by
 }
 
 int v2_stream_begin_call(tv_ctx* c, bool hybrid, uint64_t n, const uint32_t* piece_bytes, const uint32_t* tree_leaves,
-                         const uint8_t* hashes, const uint8_t* avail_bits) {
+                         const uint8_t* hashes, const uint8_t* avail_bits, bool hash = false) {
     if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
     std::lock_guard<std::mutex> g(c->mu);
-    int rc = v2_stream_check(c, hybrid, n, piece_bytes, tree_leaves, hashes);
+    int rc = v2_stream_check(c, hybrid, n, piece_bytes, tree_leaves, hashes, hash);
     if (rc) return rc;
     TV_HIP(c, hipSetDevice(c->device));
-    rc = v2_stream_begin_locked(c, piece_bytes, tree_leaves, hashes, avail_bits, 0, hybrid);
+    rc = v2_stream_begin_locked(c, piece_bytes, tree_leaves, hashes, avail_bits, 0, hybrid, hash);
     if (rc) c->st = StreamState{};   // (a failed begin leaves no stream, v2 or other)
     return rc;
 }
@@ -655,16 +752,21 @@ int v2_stream_begin_call(tv_ctx* c, bool hybrid, uint64_t n, const uint32_t* pie
 // tv_v2_stream_file_table / tv_hybrid_stream_file_table: tv_stream_file_table's reader loop over the ALIGNED file table
 // (every file starts a piece), the rows ending with their piece's bytes.  A v2 piece lies in one file, so it is
 // unreadable exactly when that file cannot supply its bytes; there are no zero-length segments to open, and a hybrid
-// torrent's pad files are not in the table: they are never opened or looked for.
+// torrent's pad files are not in the table: they are never opened or looked for.  hash: the creation forms
+// (tv_v2_stream_hash_file_table, tv_hybrid_stream_hash_file_table): the same table checks, no hashes and no
+// availability, the outputs tv_stream_hash_end's.
 int v2_stream_files_call(tv_ctx* c, bool hybrid, uint64_t n_pieces, const uint32_t* piece_bytes,
                          const uint32_t* tree_leaves, const uint8_t* hashes, uint64_t n, const uint64_t* lengths,
                          const char* paths, uint64_t paths_bytes, const uint8_t* avail_bits, uint8_t* v1_out,
-                         uint8_t* v2_out, uint8_t* bitfield_out, int32_t* status_out) {
+                         uint8_t* v2_out, uint8_t* bitfield_out, int32_t* status_out, bool hash = false,
+                         uint8_t* digests_out = nullptr, uint8_t* roots_out = nullptr) {
     if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
     std::lock_guard<std::mutex> g(c->mu);
-    int rc = v2_stream_check(c, hybrid, n_pieces, piece_bytes, tree_leaves, hashes);
+    int rc = v2_stream_check(c, hybrid, n_pieces, piece_bytes, tree_leaves, hashes, hash);
     if (rc) return rc;
-    if (!bitfield_out && c->count) return fail(c, TV_ERR_ARG, "bitfield_out is NULL");
+    if (!hash && !bitfield_out && c->count) return fail(c, TV_ERR_ARG, "bitfield_out is NULL");
+    if (hash && c->count && (!roots_out || (hybrid && !digests_out)))
+        return fail(c, TV_ERR_ARG, "%s is NULL", !roots_out ? "roots_out" : "digests_out");
     if (n && (!lengths || !paths || !status_out)) return fail(c, TV_ERR_ARG, "NULL argument");
     std::vector<const char*> path(n);
     const uint64_t np = parse_path_table(n, paths, paths_bytes, path.data());
@@ -687,8 +789,11 @@ int v2_stream_files_call(tv_ctx* c, bool hybrid, uint64_t n_pieces, const uint32
     if (!c->count) return TV_OK;
     TV_HIP(c, hipSetDevice(c->device));
     rc = stream_files_locked(c, n, lengths, path, start, [&](bool cold) {
-        return v2_stream_begin_locked(c, piece_bytes, tree_leaves, hashes, avail_bits, cold ? c->stream_cold_req : 0, hybrid);
-    }, bitfield_out, status_out, v1_out, v2_out);
+        return v2_stream_begin_locked(c, piece_bytes, tree_leaves, hashes, avail_bits, cold ? c->stream_cold_req : 0, hybrid,
+                                      hash);
+    }, status_out, [&] {
+        return hash ? stream_hash_end_locked(c, digests_out, roots_out) : stream_end_locked(c, bitfield_out, v1_out, v2_out);
+    }, hash);
     if (rc && !c->st.active) c->st = StreamState{};
     return rc;
 }
@@ -757,13 +862,20 @@ int tv_verify_host(tv_ctx* c, const uint8_t* src, uint64_t src_len, const uint8_
 // for it: a byte of it in a missing, unopenable or too-short file, a zero-length segment of its walk whose open
 // fails (storage.ts:109-110,158), or bytes past the files' end.  Files are opened as fsStorage.get opens them
 // (TV_OPT_OPEN_RW), kept open for the call, never created.
-int tv_stream_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const char* paths, uint64_t paths_bytes,
-                         const uint8_t* avail_bits, uint8_t* bitfield_out, int32_t* status_out) {
+//
+// hash (tv_stream_hash_file_table): the creation stream over the same readers.  No digests, no availability; the files
+// are opened read-only (make_torrent.ts:78), and a byte of the shard that cannot be read ends the call with TV_ERR_IO.
+static int v1_stream_files_call(tv_ctx* c, uint64_t n, const uint64_t* lengths, const char* paths, uint64_t paths_bytes,
+                                const uint8_t* avail_bits, uint8_t* bitfield_out, int32_t* status_out, bool hash,
+                                uint8_t* digests_out) {
     if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
     std::lock_guard<std::mutex> g(c->mu);
-    int rc = require_layout(c, true);
+    int rc = require_layout(c, !hash);
     if (rc) return rc;
-    if (!bitfield_out && c->count) return fail(c, TV_ERR_ARG, "bitfield_out is NULL");
+    if (!hash && !bitfield_out && c->count) return fail(c, TV_ERR_ARG, "bitfield_out is NULL");
+    if (hash && !digests_out && c->count) return fail(c, TV_ERR_ARG, "digests_out is NULL");
+    if (hash && c->win)
+        return fail(c, TV_ERR_STATE, "a creation stream needs a layout without windows (TV_OPT_RESIDENT = 0)");
     if (n && (!lengths || !paths || !status_out)) return fail(c, TV_ERR_ARG, "NULL argument");
     std::vector<const char*> path(n);
     std::vector<uint64_t> start(n + 1, 0);   // file k's linear bytes: [start[k], start[k + 1])
@@ -793,12 +905,17 @@ int tv_stream_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const c
             return fail(c, TV_ERR_ARG, "file %llu: the lengths overflow 64-bit offsets", (unsigned long long)bad);
         for (const TableSeg& sg : segs) {
             if (sg.len || sg.linear < lo || sg.linear >= hi) continue;
-            if (fs_openable(path[sg.file], c->open_rw)) {
+            if (fs_openable(path[sg.file], c->open_rw && !hash)) {
                 status_out[sg.file] = TV_ERR_IO;
                 clear_bit(av.data(), sg.linear / c->L - c->first);
             }
         }
     }
+    if (hash)   // creation cannot skip a piece: the files end before the shard does, or a zero-length file does not open
+        for (uint64_t j = 0; j < c->count; j++)
+            if (!get_bit(av.data(), j))
+                return fail(c, TV_ERR_IO, "piece %llu cannot be read: the files end before it does, or a zero-length "
+                                          "file of its range cannot be opened", (unsigned long long)(c->first + j));
     // Geometry: windows x columns within the budget (TV_OPT_RESIDENT_BUDGET, or 1 GiB); a cold shard's windows are
     // 512 pieces (rows 4 x longer; ~44 GB/s of hashing, above what the disk gives).  An explicit TV_OPT_STREAM_CHUNK
     // keeps the engine's columns across the whole shard.
@@ -808,8 +925,63 @@ int tv_stream_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const c
             const uint64_t min_win = cold ? (c->stream_cold_window ? c->stream_cold_window : 512) : 2048;
             budget_geometry(c, c->budget_opt ? c->budget_opt : (1ull << 30), min_win, &col, &win);
         }
-        return stream_begin_locked(c, av.data(), col, win, cold ? c->stream_cold_req : 0);
-    }, bitfield_out, status_out);
+        return stream_begin_locked(c, av.data(), col, win, cold ? c->stream_cold_req : 0, hash);
+    }, status_out, [&] {
+        return hash ? stream_hash_end_locked(c, digests_out, nullptr) : stream_end_locked(c, bitfield_out);
+    }, hash);
+}
+
+int tv_stream_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const char* paths, uint64_t paths_bytes,
+                         const uint8_t* avail_bits, uint8_t* bitfield_out, int32_t* status_out) {
+    return v1_stream_files_call(c, n, lengths, paths, paths_bytes, avail_bits, bitfield_out, status_out, false, nullptr);
+}
+
+int tv_stream_hash_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const char* paths, uint64_t paths_bytes,
+                              uint8_t* digests_out, int32_t* status_out) {
+    return v1_stream_files_call(c, n, lengths, paths, paths_bytes, nullptr, nullptr, status_out, true, digests_out);
+}
+
+// Creation streams (tv_stream_hash_begin and its v2 and hybrid forms): the verify stream of the same kind -- its
+// geometry, ring, requests and launches -- whose last launches store what the resident creation calls compute
+// (make_torrent.ts:18-113,147-173 is the reference's streaming creator).  They need no digests, no expected roots and
+// no availability; tv_stream_hash_end hands the hashes out.
+int tv_stream_hash_begin(tv_ctx* c) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    int rc = require_layout(c, false);
+    if (rc) return rc;
+    if (c->win) return fail(c, TV_ERR_STATE, "a creation stream needs a layout without windows (TV_OPT_RESIDENT = 0)");
+    TV_HIP(c, hipSetDevice(c->device));
+    return stream_result(c, stream_begin_locked(c, nullptr, 0, 0, 0, true));
+}
+
+int tv_v2_stream_hash_begin(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const uint32_t* tree_leaves) {
+    return v2_stream_begin_call(c, false, n, piece_bytes, tree_leaves, nullptr, nullptr, true);
+}
+
+int tv_hybrid_stream_hash_begin(tv_ctx* c, uint64_t n, const uint32_t* piece_bytes, const uint32_t* tree_leaves) {
+    return v2_stream_begin_call(c, true, n, piece_bytes, tree_leaves, nullptr, nullptr, true);
+}
+
+int tv_stream_hash_end(tv_ctx* c, uint8_t* digests_out, uint8_t* roots_out) {
+    if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
+    std::lock_guard<std::mutex> g(c->mu);
+    TV_HIP(c, hipSetDevice(c->device));
+    return stream_hash_end_locked(c, digests_out, roots_out);
+}
+
+int tv_v2_stream_hash_file_table(tv_ctx* c, uint64_t n_pieces, const uint32_t* piece_bytes, const uint32_t* tree_leaves,
+                                 uint64_t n, const uint64_t* lengths, const char* paths, uint64_t paths_bytes,
+                                 uint8_t* roots_out, int32_t* status_out) {
+    return v2_stream_files_call(c, false, n_pieces, piece_bytes, tree_leaves, nullptr, n, lengths, paths, paths_bytes,
+                                nullptr, nullptr, nullptr, nullptr, status_out, true, nullptr, roots_out);
+}
+
+int tv_hybrid_stream_hash_file_table(tv_ctx* c, uint64_t n_pieces, const uint32_t* piece_bytes,
+                                     const uint32_t* tree_leaves, uint64_t n, const uint64_t* lengths, const char* paths,
+                                     uint64_t paths_bytes, uint8_t* digests_out, uint8_t* roots_out, int32_t* status_out) {
+    return v2_stream_files_call(c, true, n_pieces, piece_bytes, tree_leaves, nullptr, n, lengths, paths, paths_bytes,
+                                nullptr, nullptr, nullptr, nullptr, status_out, true, digests_out, roots_out);
 }
 
 int tv_stream_begin(tv_ctx* c, const uint8_t* avail_bits) {
@@ -877,6 +1049,8 @@ int tv_stream_unreadable(tv_ctx* c, uint64_t piece) {
     if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
     std::lock_guard<std::mutex> g(c->mu);
     if (!c->st.active) return fail(c, TV_ERR_STATE, "tv_stream_begin has not been called");
+    if (c->st.hash)   // (the stream stays active: tv_stream_abort gives it up)
+        return fail(c, TV_ERR_STATE, "tv_stream_unreadable: a creation stream cannot skip a piece");
     if (piece < c->first || piece >= c->first + c->count)
         return fail(c, TV_ERR_ARG, "piece %llu is not in this context's shard", (unsigned long long)piece);
     clear_bit(c->st.av.data(), piece - c->first);
@@ -893,7 +1067,8 @@ int tv_stream_end(tv_ctx* c, uint8_t* bitfield_out) {
 int tv_hybrid_stream_end(tv_ctx* c, uint8_t* v1_bits_out, uint8_t* v2_bits_out, uint8_t* bitfield_out) {
     if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
     std::lock_guard<std::mutex> g(c->mu);
-    if (c->st.active && !c->st.hybrid)   // (the stream stays active: tv_stream_end ends it)
+    if (c->st.active && !c->st.hybrid && !c->st.hash)   // (the stream stays active: tv_stream_end ends it; a creation
+                                                         // stream is refused and aborted by stream_end_locked)
         return fail(c, TV_ERR_STATE, "tv_hybrid_stream_end: the active stream is not a hybrid stream");
     TV_HIP(c, hipSetDevice(c->device));
     return stream_end_locked(c, bitfield_out, v1_bits_out, v2_bits_out);

@@ -12,6 +12,7 @@ files are never looked for on disk, staged or read) and runs the SHA-1 kernel an
     verify_files_hybrid(meta, dir_path, devices=None, threads=None, stream=False) -> HybridResult
     verify_stream_hybrid(meta, read, devices=None, ...) -> HybridResult      through the bounded ring, any size
     hash_files_hybrid(dir_path, piece_length, ...) -> (v1 `pieces`, per-file v2 hashes)      creation mode
+    hash_stream_hybrid(lengths, piece_length, read, ...) -> (v1 `pieces`, piece roots)       through the bounded ring
     make_torrent_hybrid(path, tracker, ...) -> bytes of a hybrid .torrent
 
 They shard over `devices` as the v2 calls do.  The resident forms need every shard within the device budget;
@@ -31,10 +32,10 @@ from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
 from .bencode import bdecode_raw
-from .metainfo_v2 import FileV2, MetainfoV2, V2Layout, parse_metainfo_v2
+from .metainfo_v2 import FileV2, MetainfoV2, V2Layout, make_layout, parse_metainfo_v2, valid_piece_length
 from . import _native
 from .v2 import (_creation_layout, _file_hashes, _file_paths, _file_tree, _resident_layout, _source_files,
-                 _stage_file_buffers, _stage_files_v2, _torrent, piece_length_for_v2)
+                 _stage_file_buffers, _stage_files_v2, _stream_hash_table, _torrent, piece_length_for_v2)
 from .verify import (_PIECE_SLOT, _bits_shards, _context, _file_options, _hash_shards, _layout, _safe_paths,
                      _shard_avail, _stream_rows)
 
@@ -254,14 +255,41 @@ def verify_piece_hybrid(meta: MetainfoHybrid, index: int, data) -> tuple:
         return bool(ok[0]), bool(v1[0]), bool(v2[0])
 
 
+def hash_stream_hybrid(lengths: Sequence[int], piece_length: int, read, devices=None, chunk: int = 0,
+                       threads: Optional[int] = None, budget: Optional[int] = None) -> tuple:
+    """Creation mode through the library's BOUNDED pinned ring (tv_hybrid_stream_hash_begin, tv_stream_*), both hash sets
+    from one pass: (the v1 `pieces` string over the padded linear space -- no pad after the last file --, the 32-byte
+    merkle root of every piece, in piece order) of the files of these lengths (file-tree order).  read(file_index,
+    offset, length) -> bytes is verify_stream_hybrid's: pad ranges are never asked for.  A read that returns None or a
+    short result raises FileNotFoundError."""
+    if not valid_piece_length(piece_length):
+        raise ValueError("a v2 piece length is a power of two >= 16 KiB")
+    lay = make_layout(list(lengths), piece_length)
+
+    def shard(ctx, first: int, count: int) -> tuple:
+        _layout(ctx, lay.total_length, lay.piece_length, lay.n_pieces, first, count, budget, resident=False, chunk=chunk)
+        return _stream_rows(
+            ctx, threads, lambda i, offset, n: read(lay.piece_file[i], lay.piece_offset[i] + offset, n),
+            lambda: ctx.hybrid_stream_hash_begin(lay.piece_bytes, lay.tree_leaves), end=ctx.stream_hash_end,
+            must="hash_stream_hybrid")
+
+    return _hash_shards(devices, lay.n_pieces, shard, fields=2)
+
+
 def hash_files_hybrid(dir_path: str, piece_length: int, files: Optional[Sequence[tuple]] = None, devices=None,
-                      threads: Optional[int] = None, budget: Optional[int] = None) -> tuple:
+                      threads: Optional[int] = None, budget: Optional[int] = None, stream: bool = False) -> tuple:
     """Creation mode from disk, both hash sets from one staging (tv_hybrid_hash): (the v1 `pieces` string over the
     padded linear space -- no pad after the last file --, [FileHashV2] as hash_files_v2 returns them).  files:
-    [(path components, length)] in file-tree order (default: collect_files_v2).  Raises if a file is missing or short."""
+    [(path components, length)] in file-tree order (default: collect_files_v2).  Raises if a file is missing or short.
+    stream=True hashes through the bounded ring in the library's own threads (tv_hybrid_stream_hash_file_table) and never
+    raises for size; the default needs every shard resident within the budget."""
     files, lengths, lay, paths = _creation_layout(dir_path, piece_length, files)
 
     def shard(ctx, first: int, count: int) -> tuple:
+        if stream:
+            _layout(ctx, lay.total_length, lay.piece_length, lay.n_pieces, first, count, budget, resident=False)
+            return _stream_hash_table(ctx, ctx.hybrid_stream_hash_file_table, lay, lengths, paths,
+                                      threads or ctx.thread_budget, "hash_files_hybrid")
         _hybrid_layout(ctx, lay, lay.total_length, first, count, None, None, budget)
         _stage_files_v2(ctx, lay, lengths, paths, first, count, threads or ctx.thread_budget, must="hash_files_hybrid")
         return ctx.hybrid_hash()
@@ -271,15 +299,18 @@ def hash_files_hybrid(dir_path: str, piece_length: int, files: Optional[Sequence
 
 
 def make_torrent_hybrid(path: str, tracker: str, comment: Optional[str] = None, creation_date: Optional[int] = None,
-                        piece_length: Optional[int] = None, devices=None) -> bytes:
+                        piece_length: Optional[int] = None, devices=None, budget: Optional[int] = None,
+                        stream: bool = False) -> bytes:
     """A hybrid .torrent for a file or a directory: one info dict with the v1 keys (`files` with a pad entry --
     `attr` "p", path [".pad", "<length>"] -- after every file that does not end a piece, none after the last file that
     holds bytes; `length`
     for a single file; `pieces`) and the v2 keys (`meta version` 2, `file tree`), and the top-level `piece layers`.
-    Both hash sets come from one staging on the GPU.  Dictionary keys are written sorted (canonical bencoding)."""
+    Both hash sets come from one staging on the GPU.  Dictionary keys are written sorted (canonical bencoding).
+    stream=True hashes through the bounded ring (hash_files_hybrid), so a payload larger than `budget` bytes of device
+    memory still makes its torrent."""
     name, base, files, single = _source_files(path)
     L = piece_length or piece_length_for_v2(sum(n for _, n in files))
-    pieces, hashed = hash_files_hybrid(base, L, files=files, devices=devices)
+    pieces, hashed = hash_files_hybrid(base, L, files=files, devices=devices, budget=budget, stream=stream)
     info: dict = {"file tree": _file_tree(hashed)}          # (bencode writes keys in insertion order: keep them sorted)
     if single:
         info["length"] = hashed[0].length

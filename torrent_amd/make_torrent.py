@@ -52,8 +52,10 @@ def collect_files(initial_dir: str) -> List[FileInfo]:
 
 def make_torrent(path: str, tracker: str, comment: Optional[str] = None,
                  creation_date: Optional[int] = None, piece_length: Optional[int] = None,
-                 files: Optional[List[FileInfo]] = None, devices=None) -> bytes:
-    """makeTorrent(path, tracker, comment) (make_torrent.ts:115-188), digests on the GPU."""
+                 files: Optional[List[FileInfo]] = None, devices=None, budget: Optional[int] = None,
+                 stream: bool = False) -> bytes:
+    """makeTorrent(path, tracker, comment) (make_torrent.ts:115-188), digests on the GPU.  stream=True hashes the files
+    through the bounded ring while they are read (hash_files), as the reference's creator hashes each part it reads."""
     path = os.path.abspath(path)
     name = os.path.basename(path)
     common = {
@@ -72,7 +74,7 @@ def make_torrent(path: str, tracker: str, comment: Optional[str] = None,
         if n_pieces == 1 and size < L:
             pieces = bytes(20)                    # never hashed by the reference (quirk)
         else:
-            pieces = hash_files(geom, path, devices=devices)
+            pieces = hash_files(geom, path, devices=devices, budget=budget, stream=stream)
         info = {"files": [{"length": f.length, "path": list(f.path)} for f in files], "name": name,
                 "piece length": L, "pieces": pieces, "private": 0}
     else:
@@ -80,7 +82,7 @@ def make_torrent(path: str, tracker: str, comment: Optional[str] = None,
         L = piece_length or piece_length_for(size)
         n_pieces = -(-size // L)
         geom = make_info(L, bytes(20 * n_pieces), name, length=size)
-        pieces = hash_files(geom, os.path.dirname(path), devices=devices)
+        pieces = hash_files(geom, os.path.dirname(path), devices=devices, budget=budget, stream=stream)
         info = {"length": size, "name": name, "piece length": L, "pieces": pieces, "private": 0}
     return bencode({**common, "info": info})
 

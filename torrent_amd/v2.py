@@ -10,13 +10,15 @@ staging: every file starts a new piece, so file k is staged at its ALIGNED linea
     verify_stream_v2(meta, read, devices=None, avail=None, chunk=0, ...) -> bytearray    read(file, offset, length)
     verify_piece_v2(meta, index, data) -> bool
     hash_files_v2(dir_path, piece_length, files=None, ...) -> per-file pieces roots and layers (creation mode)
+    hash_stream_v2(lengths, piece_length, read, ...) -> bytes      piece roots through the bounded ring
     make_torrent_v2(path, tracker, ...) -> bytes of a v2-only .torrent
 
 All of them shard over `devices` with shard_ranges, as the v1 calls do.  There is no CPU fallback for piece hashing
 (only a file's P - 1 layer hashes and the info-hash are host work).  By default a shard must fit the device's resident
 budget and a larger one raises; stream=True (and verify_stream_v2) verify through the library's bounded pinned ring
 instead (tv_v2_stream_begin / tv_v2_stream_file_table): two chunk buffers within the budget, whatever the shard's
-size.  Creation (hash_files_v2) is resident only; windowed resident v2 layouts are not built.
+size.  Creation is resident by default too; hash_stream_v2 and stream=True (hash_files_v2, make_torrent_v2) hash through
+the same ring (tv_v2_stream_hash_begin / tv_v2_stream_hash_file_table).  Windowed resident v2 layouts are not built.
 """
 from __future__ import annotations
 
@@ -235,15 +237,56 @@ def _file_hashes(files: Sequence[tuple], lay: V2Layout, roots: bytes) -> List[Fi
     return out
 
 
+def hash_stream_v2(lengths: Sequence[int], piece_length: int, read, devices=None, chunk: int = 0,
+                   threads: Optional[int] = None, budget: Optional[int] = None) -> bytes:
+    """Creation mode through the library's BOUNDED pinned ring (tv_v2_stream_hash_begin, tv_stream_*): the 32-byte merkle
+    root of every piece of the files of these lengths (file-tree order; the aligned layout of make_layout), in piece
+    order, within `budget` bytes of device memory (default 1 GiB) whatever the size.  read(file_index, offset, length)
+    -> bytes is verify_stream_v2's, and so are the geometry and `chunk`.  Creation cannot skip a piece: a read that
+    returns None or a short result raises FileNotFoundError."""
+    if not valid_piece_length(piece_length):
+        raise ValueError("a v2 piece length is a power of two >= 16 KiB")
+    lay = make_layout(list(lengths), piece_length)
+
+    def shard(ctx, first: int, count: int) -> bytes:
+        _layout(ctx, lay.total_length, lay.piece_length, lay.n_pieces, first, count, budget, resident=False, chunk=chunk)
+        return _stream_rows(
+            ctx, threads, lambda i, offset, n: read(lay.piece_file[i], lay.piece_offset[i] + offset, n),
+            lambda: ctx.v2_stream_hash_begin(lay.piece_bytes, lay.tree_leaves), end=ctx.stream_hash_end,
+            must="hash_stream_v2")
+
+    return _hash_shards(devices, lay.n_pieces, shard)
+
+
+def _stream_hash_table(ctx, call, lay: V2Layout, lengths: Sequence[int], paths: Sequence[str], threads: int, what: str):
+    """A creation stream's file-table call (ctx.v2_stream_hash_file_table or its hybrid form) after its layout: files
+    opened read-only; a missing or short file raises, as the resident creation calls do."""
+    _file_options(ctx, threads, False)
+    try:
+        out, _ = call(lay.piece_bytes, lay.tree_leaves, lengths, _safe_paths(paths))
+    finally:
+        ctx.set_option(_native.TV_OPT_OPEN_RW, 1)
+    if out is None:
+        raise FileNotFoundError(f"{what}: a file is missing or shorter than its declared length")
+    return out
+
+
 def hash_files_v2(dir_path: str, piece_length: int, files: Optional[Sequence[tuple]] = None, devices=None,
-                  threads: Optional[int] = None, budget: Optional[int] = None) -> List[FileHashV2]:
+                  threads: Optional[int] = None, budget: Optional[int] = None,
+                  stream: bool = False) -> List[FileHashV2]:
     """Creation mode from disk: the pieces root and piece layer of every file (files: [(path components, length)] in
     file-tree order; default: collect_files_v2(dir_path)).  The GPU emits the piece roots (tv_v2_hash); the host
     reduces each longer file's layer to its pieces root (_file_hashes).  Raises if a file is missing or short.  Files
-    are opened read-only."""
+    are opened read-only.  stream=True hashes through the bounded ring in the library's own threads
+    (tv_v2_stream_hash_file_table) and never raises for size; the default needs every shard resident within the
+    budget."""
     files, lengths, lay, paths = _creation_layout(dir_path, piece_length, files)
 
     def shard(ctx, first: int, count: int) -> bytes:
+        if stream:
+            _layout(ctx, lay.total_length, lay.piece_length, lay.n_pieces, first, count, budget, resident=False)
+            return _stream_hash_table(ctx, ctx.v2_stream_hash_file_table, lay, lengths, paths,
+                                      threads or ctx.thread_budget, "hash_files_v2")
         _resident_layout(ctx, lay, first, count, None, budget)
         _stage_files_v2(ctx, lay, lengths, paths, first, count, threads or ctx.thread_budget, must="hash_files_v2")
         return ctx.v2_hash()
@@ -293,12 +336,14 @@ def _torrent(tracker: str, comment: Optional[str], creation_date: Optional[int],
 
 
 def make_torrent_v2(path: str, tracker: str, comment: Optional[str] = None, creation_date: Optional[int] = None,
-                    piece_length: Optional[int] = None, devices=None) -> bytes:
+                    piece_length: Optional[int] = None, devices=None, budget: Optional[int] = None,
+                    stream: bool = False) -> bytes:
     """A v2-only .torrent (meta version 2: `file tree` + `piece layers`) for a file or a directory, piece roots hashed
-    on the GPU.  Dictionary keys are written sorted, so the file is canonical bencoding."""
+    on the GPU.  Dictionary keys are written sorted, so the file is canonical bencoding.  stream=True hashes through the
+    bounded ring (hash_files_v2), so a payload larger than `budget` bytes of device memory still makes its torrent."""
     name, base, files, _ = _source_files(path)
     L = piece_length or piece_length_for_v2(sum(n for _, n in files))
-    hashed = hash_files_v2(base, L, files=files, devices=devices)
+    hashed = hash_files_v2(base, L, files=files, devices=devices, budget=budget, stream=stream)
     info = {"file tree": _file_tree(hashed), "meta version": 2, "name": name, "piece length": L}
     return _torrent(tracker, comment, creation_date, CREATED_BY, info, hashed)
 

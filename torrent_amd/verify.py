@@ -26,6 +26,7 @@ Public API (names follow the reference's camelCase surface, snake_cased):
     verify_payload(info, payload, devices=None, resident=None) -> bytearray
     verify_stream(info, read, devices=None) -> bytearray             (bounded-ring resume check)
     hash_pieces(payload, piece_length, devices=None) -> bytes       (creation mode, make_torrent.ts)
+    hash_stream(total, piece_length, read, devices=None) -> bytes   (creation through the bounded ring)
 and asyncio wrappers verify_pieces_async / verify_piece_async (the reference API is Promise-based).
 """
 from __future__ import annotations
@@ -412,13 +413,14 @@ def verify_stream(info: InfoDict, read, devices=None, avail: Optional[bytes] = N
     return _bits_shards(devices, P, shard)
 
 
-def _stream_rows(ctx, threads: Optional[int], read_row, begin, end=None):
+def _stream_rows(ctx, threads: Optional[int], read_row, begin, end=None, must: Optional[str] = None):
     """The ring loop of a streamed check, after its layout: begin() opens the stream, then every request's rows are
     read -- read_row(i, offset, n) -> the n bytes of piece i from `offset`, or None -- on `threads` threads
     (_storage_threads), each copying its row into the slot itself, without the GIL.  A row that is None or short makes
-    its piece unreadable.  -> the shard's bits: end() (default ctx.stream_end; a hybrid stream's three bitfields come
-    from ctx.hybrid_stream_end).  Any exception ends the stream (stream_abort); either way the stream
-    options are back at their defaults afterwards."""
+    its piece unreadable (must="<the caller>": a creation stream, which cannot skip a piece -- FileNotFoundError).
+    -> the shard's bits: end() (default ctx.stream_end; a hybrid stream's three bitfields come
+    from ctx.hybrid_stream_end; a creation stream's hashes from ctx.stream_hash_end).  Any exception ends the stream
+    (stream_abort); either way the stream options are back at their defaults afterwards."""
     nthr = _storage_threads(ctx, threads)
     pool = ThreadPoolExecutor(nthr) if nthr > 1 else None
     try:
@@ -441,6 +443,8 @@ def _stream_rows(ctx, threads: Optional[int], read_row, begin, end=None):
                 return None
 
             for i in _chunked_map(pool, fill, req.rows, nthr):
+                if i is not None and must:
+                    raise FileNotFoundError(f"{must}: a file is missing or shorter than its declared length")
                 if i is not None:
                     ctx.stream_unreadable(i)
             ctx.stream_commit(req)
@@ -571,18 +575,61 @@ def verify_files(info: InfoDict, dir_path: str, devices=None, threads: Optional[
     return _bits_shards(devices, P, shard)
 
 
+def hash_stream(total: int, piece_length_: int, read, devices=None, chunk: int = 0,
+                threads: Optional[int] = None) -> bytes:
+    """Creation mode through the library's BOUNDED pinned ring (tv_stream_hash_begin, tv_stream_*): the `pieces` string
+    of `total` linear bytes without a resident payload or a whole-shard host buffer, as make_torrent.ts hashes each
+    part while it reads the next (:62-113, :147-173).  read(linear_offset, length) -> bytes is verify_stream's; the
+    geometry too (chunk=0: each request row is a whole piece; chunk=C: columns of C bytes across the shard).  Creation
+    cannot skip a piece: a read that returns None or a short result raises FileNotFoundError."""
+    L = piece_length_
+    P = -(-total // L) if total else 0
+
+    def shard(ctx, first: int, count: int) -> bytes:
+        _layout(ctx, total, L, P, first, count, 0, resident=False, chunk=chunk, rows=0 if chunk else 1)
+        return _stream_rows(ctx, threads, lambda i, offset, n: read(i * L + offset, n), ctx.stream_hash_begin,
+                            end=ctx.stream_hash_end, must="hash_stream")
+
+    return _hash_shards(devices, P, shard)
+
+
+def _budget_chunk(L: int, count: int, budget: Optional[int]) -> int:
+    """The widest column (TV_OPT_STREAM_CHUNK; a multiple of 64 bytes, at most a piece) whose two chunk buffers -- rows
+    of chunk + 256 bytes for every shard piece, 256 after the last -- fit the budget; 0 (the library's own) without one."""
+    if not budget:
+        return 0
+    per = (budget // 2 - 256) // max(1, count) - 256
+    return max(64, min(-(-L // 64) * 64, per // 64 * 64))
+
+
 def hash_files(info: InfoDict, dir_path: str, devices=None, threads: Optional[int] = None,
-               direct_min: Optional[int] = None, budget: Optional[int] = None) -> bytes:
+               direct_min: Optional[int] = None, budget: Optional[int] = None, stream: bool = False) -> bytes:
     """Creation mode from disk: the `pieces` string of the files info describes under dir_path
     (info.pieces is ignored; only the geometry is used).  Raises if a file is missing or short.  Files are
-    opened read-only, as make_torrent.ts:78 opens its sources: the process need not be able to write them."""
+    opened read-only, as make_torrent.ts:78 opens its sources: the process need not be able to write them.
+    stream=True reads the files through the bounded ring in the library's own threads (tv_stream_hash_file_table):
+    columns within `budget` (default 1 GiB), hashed while the next ones are read, no resident payload."""
     from .storage import Storage, fs_storage
 
     L = info.piece_length
     P = -(-info.length // L) if info.length else 0
     storage = Storage(fs_storage, info, dir_path)
 
+    def stream_shard(ctx, first: int, count: int) -> bytes:
+        _layout(ctx, info.length, L, P, first, count, budget, resident=False)
+        _file_options(ctx, threads or ctx.thread_budget, False)
+        lengths = [info.length] if info.files is None else [f.length for f in info.files]
+        try:
+            digests, _ = ctx.stream_hash_file_table(lengths, _safe_paths(storage.file_paths()))
+        finally:
+            ctx.set_option(_native.TV_OPT_OPEN_RW, 1)
+        if digests is None:
+            raise FileNotFoundError("hash_files: a file is missing or shorter than its declared length")
+        return digests
+
     def shard(ctx, first: int, count: int) -> bytes:
+        if stream:
+            return stream_shard(ctx, first, count)
         _layout(ctx, info.length, L, P, first, count, budget)
         status: list = []
         avail = _files_shard(ctx, info, storage, first, count, threads or ctx.thread_budget, direct_min, status,
@@ -609,14 +656,36 @@ def verify_piece(info: InfoDict, index: int, data) -> bool:
         return bool(ctx.verify()[0] & 0x80)
 
 
-def hash_pieces(payload, piece_length_: int, devices=None, budget: Optional[int] = None) -> bytes:
+def hash_pieces(payload, piece_length_: int, devices=None, budget: Optional[int] = None,
+                stream: bool = False) -> bytes:
     """Creation mode: the `pieces` byte string for a linear payload (make_torrent.ts:147-173;
-    multi-file payloads are the files concatenated in order, make_torrent.ts:62-113)."""
+    multi-file payloads are the files concatenated in order, make_torrent.ts:62-113).  stream=True hashes it through
+    the bounded ring (tv_stream_hash_begin) instead of staging it: columns across the shard whose two chunk buffers fit
+    `budget`, each request's rows copied straight from the payload (tv_stream_commit_from)."""
     mv = memoryview(payload).cast("B")
     total = len(mv)
     P = -(-total // piece_length_) if total else 0
 
+    def stream_shard(ctx, first: int, count: int) -> bytes:
+        L = piece_length_
+        _layout(ctx, total, L, P, first, count, 0, resident=False, chunk=_budget_chunk(L, count, budget))
+        try:
+            ctx.stream_hash_begin()
+            while True:
+                req = ctx.stream_next()
+                if not req.rows:
+                    break
+                ctx.stream_commit_from(req, mv, L, req.piece * L + req.offset)
+            return ctx.stream_hash_end()
+        except BaseException:
+            ctx.stream_abort()
+            raise
+        finally:
+            ctx.set_option(_native.TV_OPT_STREAM_CHUNK, 0)
+
     def shard(ctx, first: int, count: int) -> bytes:
+        if stream:
+            return stream_shard(ctx, first, count)
         _layout(ctx, total, piece_length_, P, first, count, budget)
         lo, hi = first * piece_length_, min(total, (first + count) * piece_length_)
         if hi > lo:

@@ -110,6 +110,28 @@ const SYMBOLS = {
     result: "i32",
     nonblocking: true,
   },
+  // Streamed creation (the verify streams' ring, the hashes out): bound so that the table covers the header; the host
+  // functions are torrent_amd's hash_stream* and the stream=True creation calls.
+  tv_stream_hash_begin: { parameters: ["pointer"], result: "i32" },
+  tv_v2_stream_hash_begin: { parameters: ["pointer", "u64", "pointer", "pointer"], result: "i32", nonblocking: true },
+  tv_hybrid_stream_hash_begin: { parameters: ["pointer", "u64", "pointer", "pointer"], result: "i32", nonblocking: true },
+  tv_stream_hash_end: { parameters: ["pointer", "pointer", "pointer"], result: "i32", nonblocking: true },
+  tv_stream_hash_file_table: {
+    parameters: ["pointer", "u64", "pointer", "pointer", "u64", "pointer", "pointer"],
+    result: "i32",
+    nonblocking: true,
+  },
+  tv_v2_stream_hash_file_table: {
+    parameters: ["pointer", "u64", "pointer", "pointer", "u64", "pointer", "pointer", "u64", "pointer", "pointer"],
+    result: "i32",
+    nonblocking: true,
+  },
+  tv_hybrid_stream_hash_file_table: {
+    parameters: ["pointer", "u64", "pointer", "pointer", "u64", "pointer", "pointer", "u64", "pointer", "pointer",
+                 "pointer"],
+    result: "i32",
+    nonblocking: true,
+  },
   tv_stream_begin: { parameters: ["pointer", "pointer"], result: "i32" },
   tv_stream_next: { parameters: ["pointer", "pointer"], result: "i32", nonblocking: true },
   tv_stream_commit: { parameters: ["pointer", "pointer"], result: "i32", nonblocking: true },
