@@ -256,6 +256,46 @@ int tv_stream_file_table(tv_ctx *ctx, uint64_t n, const uint64_t *lengths, const
 int tv_hash(tv_ctx *ctx, uint8_t *digests_out);
 
 /*
+ * A BATCH LAYOUT: many v1 torrents of any piece lengths resident at once, verified by ONE kernel launch.  The
+ * interface it serves is the client's torrent map (client.ts: `torrents: Map<string, Torrent>`): when a client
+ * starts, every torrent it holds is re-checked, and SHA-1 is serial inside a piece, so a launch per torrent costs at
+ * least one piece's serial hash each while filling a sliver of the GPU.
+ *
+ * Torrent t has the geometry tv_set_layout(total_length[t], piece_length[t], n_pieces[t], 0, n_pieces[t]) would give
+ * it (n_pieces[t] digests, which may differ from ceil(total / L); piece lengths per piece.ts:16-19; 0 pieces allowed).
+ * The payload is one device allocation, a region per torrent laid out as a resident layout's rows (stride =
+ * round_up(L, 64) + TV_OPT_STRIDE_PAD), every region 256-byte aligned, the usual slack after the last.  There are no
+ * windows and no slot pool: a batch beyond TV_OPT_RESIDENT_BUDGET (or the automatic budget) is TV_ERR_NOMEM (the
+ * message names the bytes and the budget; the context stays usable), TV_OPT_LIST_SLOTS set or TV_OPT_RESIDENT = 0 is
+ * TV_ERR_STATE.  TV_ERR_ARG (naming the torrent): a geometry tv_set_layout would refuse, 2^32 - 1 pieces or more in
+ * all.  Allocations are reused as tv_set_layout reuses them.  Torrent 0 is selected on return; tv_set_layout ends
+ * the batch.
+ */
+int tv_set_batch_layout(tv_ctx *ctx, uint64_t n_torrents, const uint64_t *total_length,
+                        const uint64_t *piece_length, const uint64_t *n_pieces);
+
+/*
+ * Select torrent t of the batch (one entry of client.ts's torrent map): tv_set_digests, tv_stage, tv_stage_many,
+ * tv_stage_file, tv_stage_files, tv_stage_file_table, tv_read and tv_fill_synthetic then work on it unchanged,
+ * linear_offset meaning ITS linear space.  A torrent's ragged-digest bits, the unreadable marks file staging left
+ * and whether its digests were set survive selecting another torrent and coming back.  TV_ERR_ARG: t >= n_torrents;
+ * TV_ERR_STATE: no batch layout.
+ */
+int tv_batch_select(tv_ctx *ctx, uint64_t torrent);
+
+/*
+ * Verify every piece of every torrent of the batch (the start-up re-check of client.ts's torrent map) in ONE
+ * launch.  bitfield_out: the per-torrent MSB-first bitfields back to back, torrent t's starting at byte
+ * sum over u < t of ceil(n_pieces[u] / 8); avail_bits (optional, NULL = all readable): the same shape.  A piece's bit
+ * is 1 iff it is available, not marked unreadable by file staging, its digest slice is 20 bytes long and SHA-1 of its
+ * resident bytes equals the slice.  TV_ERR_STATE (naming the torrent) when a torrent's digests were never set.
+ * tv_last_timing, tv_last_kernel (the form that ran, 1 launch) and TV_COUNTER_LAST_WORKGROUPS report it.
+ * While a batch layout is set, every other verifying or hashing call (tv_verify, tv_hash, tv_verify_list,
+ * tv_verify_host, tv_stream_*, tv_v2_*, tv_hybrid_*) is TV_ERR_STATE.
+ */
+int tv_batch_verify(tv_ctx *ctx, const uint8_t *avail_bits, uint8_t *bitfield_out);
+
+/*
  * BitTorrent v2 (BEP 52) pieces: SHA-256 merkle roots over 16 KiB blocks.  The reference knows v1 torrents only
  * (metainfo.ts:12-44 has no `file tree`); these calls verify and create the format current clients write by default.
  *

@@ -12,6 +12,7 @@ from .storage import FsStorage, MemoryStorage, Storage, fs_storage  # noqa: F401
 from .verify import (context_counters, hash_files, hash_pieces, hash_stream, release_contexts, shard_ranges,  # noqa: F401
                      verify_files, verify_payload, verify_piece, verify_piece_async, verify_pieces,
                      verify_pieces_async, verify_stream)
+from .batch import plan_batches, verify_files_batch, verify_payload_batch  # noqa: F401
 from .incremental import (IncrementalVerifier, IncrementalVerifierHybrid, IncrementalVerifierV2,  # noqa: F401
                           flush_cost_ms_v2, validate_received_block_v2)
 from .make_torrent import make_torrent  # noqa: F401
@@ -38,4 +39,5 @@ __all__ = [
     "HybridResult", "MetainfoHybrid", "parse_metainfo_hybrid", "verify_payload_hybrid", "verify_files_hybrid",
     "verify_stream_hybrid", "verify_piece_hybrid", "IncrementalVerifierHybrid",
     "hash_files_hybrid", "make_torrent_hybrid", "hash_stream", "hash_stream_v2", "hash_stream_hybrid",
+    "plan_batches", "verify_files_batch", "verify_payload_batch",
 ]

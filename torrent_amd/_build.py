@@ -16,7 +16,8 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libtorrent_verify.so")
 SOURCES = ["tv_kernels.hip", "tv_core.hip", "tv_context.hip", "tv_stage.hip", "tv_files.hip",
-           "tv_stream.hip", "tv_verify.hip", "tv_v2_kernels.hip", "tv_v2.hip", "tv_hybrid.hip"]
+           "tv_stream.hip", "tv_verify.hip", "tv_v2_kernels.hip", "tv_v2.hip", "tv_hybrid.hip",
+           "tv_batch.hip"]
 HOST_SOURCES = ["tv_host.cpp"]          # host-only C++ (no device code): the host compiler
 EXPORTS = os.path.join(CSRC, "exports.map")   # the link exports tv_* only
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -140,6 +140,9 @@ SYMBOLS = [
     ("tv_verify_host", _int, [_p, _p, _u64, _p, _p]),
     ("tv_verify_list", _int, [_p, _p, _u64, _p]),
     ("tv_hash", _int, [_p, _p]),
+    ("tv_set_batch_layout", _int, [_p, _u64, _p, _p, _p]),
+    ("tv_batch_select", _int, [_p, _u64]),
+    ("tv_batch_verify", _int, [_p, _p, _p]),
     ("tv_v2_set_pieces", _int, [_p, _u64, _p, _p, _p]),
     ("tv_v2_verify", _int, [_p, _p, _p]),
     ("tv_v2_hash", _int, [_p, _p]),
@@ -181,6 +184,8 @@ SYMBOLS = [
     ("tv_host_unregister", _int, [_p]),
 ]
 
+BATCH_SYMBOLS = ("tv_set_batch_layout", "tv_batch_select", "tv_batch_verify")   # the batch layout's calls
+
 _lib = None
 
 
@@ -199,13 +204,28 @@ def lib() -> ctypes.CDLL:
                               "(there is no CPU fallback)")
         L = ctypes.CDLL(LIB_PATH)
         for name, res, args in SYMBOLS:
-            fn = getattr(L, name)
+            try:
+                fn = getattr(L, name)
+            except AttributeError:
+                if name in BATCH_SYMBOLS:
+                    raise ImportError(f"{LIB_PATH}: library too old for batch verify (it has no {name}): rebuild it "
+                                      "with `python -m torrent_amd._build`") from None
+                raise
             fn.restype = res
             fn.argtypes = args
         if L.tv_abi_version() != 1:
             raise ImportError("libtorrent_verify ABI version mismatch")
         _lib = L
     return _lib
+
+
+def batch_offsets(n_pieces) -> list:
+    """Where each torrent's bitfield starts in tv_batch_verify's concatenated bitfields: torrent t's ceil(n_pieces[t]
+    / 8) bytes start at offsets[t]; offsets[-1] is the total."""
+    offs = [0]
+    for n in n_pieces:
+        offs.append(offs[-1] + (int(n) + 7) // 8)
+    return offs
 
 
 def _addr(buf, writable: bool = False) -> tuple:
@@ -541,6 +561,38 @@ class Context:
         bits = self._bits_call(self._L.tv_verify_host, a, n, avail=avail_bits)
         del keep
         return bits
+
+    # -- the batch layout: many v1 torrents resident at once, one launch (tv_batch.hip) ----
+    def set_batch_layout(self, totals, piece_lengths, n_pieces) -> None:
+        """tv_set_batch_layout: torrent t has total length totals[t], piece length piece_lengths[t] and n_pieces[t]
+        digests; torrent 0 is selected.  set_layout ends the batch."""
+        n = len(totals)
+        if len(piece_lengths) != n or len(n_pieces) != n:
+            raise ValueError("set_batch_layout: totals, piece_lengths and n_pieces differ in length")
+        arr = lambda v: (ctypes.c_uint64 * n)(*v)  # noqa: E731
+        self._check(self._L.tv_set_batch_layout(self._h, n, arr(totals), arr(piece_lengths), arr(n_pieces)))
+        self._batch_pieces = [int(v) for v in n_pieces]
+        self._batch_select(0)
+
+    def _batch_select(self, t: int) -> None:
+        self.shard_first, self.shard_count = 0, self._batch_pieces[t]
+
+    def batch_select(self, t: int) -> None:
+        """tv_batch_select: set_digests, the stage calls, read and fill_synthetic then work on torrent t."""
+        self._check(self._L.tv_batch_select(self._h, t))
+        self._batch_select(t)
+
+    def batch_verify(self, avail=None) -> list:
+        """tv_batch_verify: every piece of every torrent in one launch -> one bitfield (bytearray) per torrent.
+        avail: None, or the per-torrent availability bitfields back to back (batch_offsets' layout)."""
+        offs = batch_offsets(self._batch_pieces)
+        out = ctypes.create_string_buffer(max(1, offs[-1]))
+        if avail is not None and memoryview(avail).nbytes != offs[-1]:
+            raise ValueError(f"batch_verify: avail holds {memoryview(avail).nbytes} bytes, the batch's bitfields {offs[-1]}")
+        a, keep = _addr(avail)
+        self._check(self._L.tv_batch_verify(self._h, a, out))
+        del keep
+        return [bytearray(out.raw[offs[t]:offs[t + 1]]) for t in range(len(self._batch_pieces))]
 
     def verify_list(self, pieces) -> bytes:
         """tv_verify_list: one byte (0/1) per listed global piece index."""

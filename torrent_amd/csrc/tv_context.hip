@@ -375,6 +375,7 @@ int tv_set_layout(tv_ctx* c, uint64_t total_length, uint64_t piece_length, uint6
         if (rc) return rc;
     }
     c->has_layout = false;
+    batch_end(c);
     c->digests_set = false;
     c->v2_set = c->v2_hashes = false;
     c->total = total_length;
@@ -523,7 +524,7 @@ int tv_set_digests(tv_ctx* c, const uint8_t* pieces, uint64_t pieces_len) {
         TV_HIP(c, hipSetDevice(c->device));
         stream_abort_locked(c);
     }
-    int rc = require_layout(c, false);
+    int rc = require_layout(c, false, false, /*batch_ok=*/true);
     if (rc) return rc;
     if (!pieces && pieces_len) return fail(c, TV_ERR_ARG, "pieces is NULL");
     c->digests_set = false;  // until the digests AND their base availability are both on the device
@@ -536,12 +537,13 @@ int tv_set_digests(tv_ctx* c, const uint8_t* pieces, uint64_t pieces_len) {
         digest_pack(pieces + 20 * i, 5, soa.data(), c->count, j);
         set_bit(c->digest_ok.data(), j);
     }
-    if (c->count) {
+    if (c->batch_on) {   // the selected torrent's columns of the batch's table; tv_batch_verify applies the base bits
+        rc = batch_put_digests(c, soa.data());
+        if (rc) return rc;
+    } else if (c->count) {
         TV_HIP(c, hipSetDevice(c->device));
         TV_HIP(c, hipMemcpyAsync(c->d_digests, soa.data(), soa.size() * 4, hipMemcpyHostToDevice, c->stream));
         TV_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    if (c->count) {
         rc = upload_base_avail(c);
         if (rc) return rc;
     }

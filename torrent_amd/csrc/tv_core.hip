@@ -641,7 +641,7 @@ int piece_dst(tv_ctx* c, uint64_t i, uint8_t** out) {
     } else if (c->win) {
         *out = win_base(c, c->win_buf) + (j - c->win_cur * c->win_n) * c->stride;
     } else {
-        *out = c->d_payload + j * c->stride;
+        *out = c->d_payload + c->region + j * c->stride;
     }
     return TV_OK;
 }
@@ -810,8 +810,9 @@ uint64_t win_end_linear(const tv_ctx* c, uint64_t w) {
 
 // The state every non-stream call needs.  need_resident: the call reads or writes the resident payload
 // (absent with TV_OPT_RESIDENT = 0).  Calls sharing the output / chunk buffers wait for a stream to end.
-int require_layout(tv_ctx* c, bool need_digests, bool need_resident) {
+int require_layout(tv_ctx* c, bool need_digests, bool need_resident, bool batch_ok) {
     if (!c->has_layout) return fail(c, TV_ERR_STATE, "tv_set_layout has not been called");
+    if (c->batch_on && !batch_ok) return batch_refused(c);
     if (need_digests && !c->digests_set) return fail(c, TV_ERR_STATE, "tv_set_digests has not been called");
     if (c->st.active) return fail(c, TV_ERR_STATE, "a stream is active (finish it with tv_stream_end or tv_stream_abort)");
     if (need_resident && c->count && !c->d_payload)

@@ -3,7 +3,8 @@
 // staging rings, windows, slot pool, kernel choice, the host -> HBM copy path; tv_stage.hip: staging from memory;
 // tv_files.hip: staging from files; tv_stream.hip: the streamed engine; tv_verify.hip: verify / list / hash;
 // tv_v2.hip: the BitTorrent v2 piece table, verify, hash and list verify (the streamed v2 verify: tv_stream.hip);
-// tv_hybrid.hip: hybrid torrents (the pad kernel, then the SHA-1 and the v2 launches over one staging; the list call).
+// tv_hybrid.hip: hybrid torrents (the pad kernel, then the SHA-1 and the v2 launches over one staging; the list call);
+// tv_batch.hip: the batch layout (many v1 torrents resident at once, verified by one launch).
 // The device memory a call allocates is a DevBuf each (grow_buf / free_buf, tv_core.hip): the context lists them, so
 // free_device and TV_COUNTER_DEVICE_BYTES cover every one.  The steps the list calls share (list_*) are in tv_core.hip,
 // their pure parts (the digest-word codec, the v1 list's launch order) in tv_plan.h.
@@ -179,6 +180,17 @@ struct DevBuf {
     uint64_t bytes() const { return cap * unit; }
 };
 
+// One torrent of a batch layout (tv_set_batch_layout): its geometry, where its region and its digest columns start, and
+// the per-torrent state that outlives tv_batch_select (the context's own fields hold the SELECTED torrent's).
+struct BatchTorrent {
+    uint64_t total = 0, L = 0, count = 0, stride = 0;
+    uint64_t region = 0;   // byte offset of its rows in d_payload (256-byte aligned)
+    uint64_t col0 = 0;     // its first column in the [5][N] digest table; its bitfield starts at byte bit0
+    uint64_t bit0 = 0;
+    bool digests_set = false, any_file_bad = false;
+    std::vector<uint8_t> digest_ok, file_bad;
+};
+
 }  // namespace tvi
 
 using tvi::DevBuf;
@@ -240,6 +252,7 @@ struct tv_ctx {
 
     // device memory
     uint8_t* d_payload = nullptr;
+    uint64_t region = 0;              // a batch layout: the selected torrent's rows start at d_payload + region (else 0)
     uint32_t* d_digests = nullptr;    // [5][count]
     uint64_t* d_avail = nullptr;      // bit words, sized to whole 256-piece groups (caller-masked)
     uint64_t* d_base_avail = nullptr; // same shape: digest slice complete & piece inside the torrent
@@ -374,6 +387,16 @@ struct tv_ctx {
     DevBuf d_hy_bits{call_bufs, 2 * 8};   // [2][cap] 64-bit words: the v2 bitfield of a hybrid verify (or stream), then its v2 availability
     DevBuf d_hy_list{call_bufs, 8};       // tv_hybrid_verify_list: the GLOBAL piece of every launched entry (the pad launch's)
 
+    // A batch layout (tv_batch.hip): many v1 torrents resident in d_payload, one region each, verified by ONE launch
+    // (tv_batch_verify).  total / L / P / count / stride / region / digest_ok / file_bad / digests_set above are the
+    // SELECTED torrent's (first = 0), so the staging calls work on it unchanged; `batch` keeps the others'.
+    bool batch_on = false;
+    uint64_t batch_cur = 0;            // the selected torrent
+    uint64_t batch_pieces = 0;         // N: the pieces of every torrent (the digest table is [5][N])
+    std::vector<tvi::BatchTorrent> batch;
+    DevBuf d_batch{call_bufs, 24};     // per launch position: cap offsets (64-bit), cap lengths (64-bit), cap digest columns (32-bit)
+    DevBuf d_batch_geom{call_bufs, sizeof(TvBatchGeom)};   // per group
+
     bool open_rw = true;               // TV_OPT_OPEN_RW: files opened read + write (fsStorage.get) or read-only
     bool stream_rows = false;          // TV_OPT_STREAM_ROWS: stream requests carry whole pieces (windows of pieces)
     int lane_pairs = 0;                // TV_OPT_LANE_PAIRS: 0 auto (>= 256 x CUs pieces in the launch), 1 on, 2 off
@@ -416,7 +439,13 @@ inline void shard_bytes(const tv_ctx* c, bool clamp_total, uint64_t* lo, uint64_
 // Clip the LINEAR range [off, off + len) to this ctx's shard / to the pieces the payload can take now.
 void clip_to_whole_shard(const tv_ctx* c, uint64_t off, uint64_t len, uint64_t* a, uint64_t* b);
 void clip_to_shard(const tv_ctx* c, uint64_t off, uint64_t len, uint64_t* a, uint64_t* b);
-int require_layout(tv_ctx* c, bool need_digests, bool need_resident = false);
+// batch_ok: the call also works on the selected torrent of a batch layout (staging, tv_read, tv_set_digests); every
+// other call is TV_ERR_STATE there
+int require_layout(tv_ctx* c, bool need_digests, bool need_resident = false, bool batch_ok = false);
+int batch_refused(tv_ctx* c);        // TV_ERR_STATE and its text: a batch layout is set
+void batch_end(tv_ctx* c);           // tv_set_layout: the context holds one torrent again
+// tv_set_digests on a batch layout: the selected torrent's [5][count] words into its columns of the [5][N] table
+int batch_put_digests(tv_ctx* c, const uint32_t* soa);
 
 // ---- files (fsStorage.get's open rules) -------------------------------------------------------------------------
 

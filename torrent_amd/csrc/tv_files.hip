@@ -725,7 +725,7 @@ int tv_stage_file(tv_ctx* c, const char* path, uint64_t file_offset, uint64_t li
     if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
     std::lock_guard<std::mutex> g(c->mu);
     FileClock call_clock(c, TV_FILE_PHASE_CALL);
-    int rc = require_layout(c, false, true);
+    int rc = require_layout(c, false, true, /*batch_ok=*/true);
     if (rc) return rc;
     if (!path) return fail(c, TV_ERR_ARG, "path is NULL");
     if (linear_offset + len < linear_offset || file_offset + len < file_offset)
@@ -774,7 +774,7 @@ int tv_stage_files(tv_ctx* c, uint64_t n, const char* const* paths, const uint64
     if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
     std::lock_guard<std::mutex> g(c->mu);
     FileClock call_clock(c, TV_FILE_PHASE_CALL);
-    int rc = require_layout(c, false, true);
+    int rc = require_layout(c, false, true, /*batch_ok=*/true);
     if (rc) return rc;
     if (n == 0) return TV_OK;
     if (!paths || !file_offsets || !linear_offsets || !lens || !status_out)
@@ -793,7 +793,7 @@ int tv_stage_file_table(tv_ctx* c, uint64_t n, const uint64_t* lengths, const ch
     if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
     std::lock_guard<std::mutex> g(c->mu);
     FileClock call_clock(c, TV_FILE_PHASE_CALL);
-    int rc = require_layout(c, false, true);
+    int rc = require_layout(c, false, true, /*batch_ok=*/true);
     if (rc) return rc;
     if (n == 0) return TV_OK;
     if (!lengths || !paths || !status_out) return fail(c, TV_ERR_ARG, "NULL argument");

@@ -356,6 +356,7 @@ int tv_hybrid_verify_list(tv_ctx* c, uint64_t n, const uint64_t* pieces, const u
     std::lock_guard<std::mutex> g(c->mu);
     // the state, in the order the header lists it
     if (!c->has_layout) return fail(c, TV_ERR_STATE, "tv_set_layout has not been called");
+    if (c->batch_on) return batch_refused(c);
     if (!c->digests_set) return fail(c, TV_ERR_STATE, "tv_set_digests has not been called");
     if (c->win)
         return fail(c, TV_ERR_STATE, "tv_hybrid_verify_list needs the shard resident or a slot pool (TV_OPT_LIST_SLOTS); "

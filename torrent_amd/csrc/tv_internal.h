@@ -17,6 +17,13 @@
 // to 4 waves in each of 65,536 workgroups
 constexpr size_t kClockWords = 4 + (TV_STAMPS ? 8 * 4 * 65536 : 0);
 
+// The block ranges of one group of a batch launch (tv_plan.h batch_plan computes them; WaveGeom of tv_kernels.hip with
+// fast_begin = 0): blocks [0, fast_end) are raw data for EVERY entry of the group (fast_end * 64 <= every length),
+// blocks [.., end) are processed (the longest entry's count), every entry has at least nb_min blocks.
+struct TvBatchGeom {
+    uint32_t fast_end, end, nb_min, reserved;
+};
+
 // One launch over a contiguous run of n pieces.  Piece j's byte k (piece-relative) is at
 // data + j*stride + k - data_off.  Blocks [blk_begin, min(blk_end, nb_j)) are processed.
 struct TvPieces {
@@ -52,6 +59,12 @@ struct TvPieces {
                              // 100 MHz real-time counter} at its start and end here (4 words); null = off
     uint32_t lane_pairs;     // host-side choice for the lane kernel: 1 = the pair-load instantiation (a lane's two
                              // 64-B blocks of a 128-B line loaded back to back; >= 1 wave per SIMD), 0 = 3-deep ring
+    // batch mode (tv_batch_verify: tv_launch_verify_batch): launch position j is a whole piece of ANY length, anywhere
+    // in the payload; the positions are cut into groups of the kernel form's span by tv_plan.h batch_plan
+    const uint64_t* b_off;   // [n] byte offset of position j's piece (its byte 0) from `data`
+    const uint64_t* b_len;   // [n] its length
+    const uint32_t* b_col;   // [n] its column in digests ([5][dcount])
+    const TvBatchGeom* b_geom;   // [groups] the block ranges every wave of group g runs (uniform: loop bounds come from here only)
 };
 
 // ---- BitTorrent v2 (BEP 52): SHA-256 merkle piece roots over 16 KiB leaves (tv_v2_kernels.hip, tv_v2.hip) ----------
@@ -160,6 +173,10 @@ hipError_t tv_v2_launch_blocks(const TvV2Blocks& p, bool check, hipStream_t s, u
 hipError_t tv_launch_verify(const TvPieces& p, int kernel, bool hash, hipStream_t s, int split_pairs = 0,
                             uint32_t* workgroups = nullptr);
 hipError_t tv_launch_verify_list(const TvPieces& p, int kernel, hipStream_t s, uint32_t* workgroups = nullptr);
+// The batch launch: p.n positions described by b_off / b_len / b_col, groups of tv_batch_span(kernel) by b_geom;
+// results through out_bytes as in list mode.
+inline uint32_t tv_batch_span(int kernel) { return kernel == TV_KERNEL_TWIN ? 32u : 64u; }
+hipError_t tv_launch_verify_batch(const TvPieces& p, int kernel, hipStream_t s, uint32_t* workgroups = nullptr);
 hipError_t tv_launch_fill(uint8_t* payload, uint64_t stride, uint64_t first, uint32_t n, uint64_t L,
                           uint64_t seed, hipStream_t s);
 // Windowed layouts: bit j of out64 (MSB-first bytes in 64-bit words, as the verify kernels write it) = the

@@ -6,7 +6,7 @@
 // the digest equals info.pieces[i] (metainfo.ts:111) and the bytes were readable
 // (Storage.get non-null, storage.ts:50-65), MSB-first (torrent.ts:147-149).
 //
-// SHA-1 is serial inside a piece, so parallelism comes from pieces only.  Three kernels (plus list modes):
+// SHA-1 is serial inside a piece, so parallelism comes from pieces only.  Three kernels (plus list and batch modes):
 //   lane  : one lane per piece; each lane loads its own 64-byte blocks (register prefetch, TV_LANE_DEPTH = 3
 //           blocks ahead) and runs the full compression (schedule + rounds) as one generated asm block
 //           (613 VALU per block).  For > 32,768 pieces per GPU, where every SIMD has a wave.
@@ -22,7 +22,7 @@
 //           partner by DPP; a two-lane helper expands the schedule by parity.  For <= 16,384 pieces per GPU
 //           (every wave still has a SIMD to itself).
 // What the kernels share is written once: resolve_group() turns a group of a launch into each lane's piece, block
-// range and bytes (resident and list mode); helper_wave() / rounds_wave() are the two wave bodies of split and twin,
+// range and bytes (resident, list and batch mode); helper_wave() / rounds_wave() are the two wave bodies of split and twin,
 // with the barrier protocol stated above them; finish() / finish_list() write the results.  The generated blocks
 // and loops are in sha1_asm.h (tools/gen_sha1_asm.py).
 //
@@ -106,24 +106,47 @@ struct Group {
 // when the payload is a slot pool (TV_OPT_LIST_SLOTS).  There is no last group: the last piece may sit in any
 // lane, so the geometry comes from the wave's ballots (the host puts the last piece's entries in groups of their
 // own; waves that must agree, a helper and its rounds wave, see the same entries, so their ballots agree).
-template <bool LIST>
+// BATCH = many torrents in one launch (tv_batch_verify): entry j is a whole piece of its own length b_len[j] at
+// data + b_off[j], its digest in column b_col[j].  The group's block ranges are the host's (b_geom[gi], tv_plan.h
+// batch_plan: fast_end * 64 <= every member's length), indexed by the group alone and kept scalar, so every wave of a
+// workgroup runs the same loop bounds; lengths, padding and the digest-update mask stay per lane.
+enum GroupMode : int { RESIDENT = 0, LIST = 1, BATCH = 2 };
+
+template <int MODE>
 __device__ __forceinline__ Group resolve_group(const TvPieces& p, uint32_t gi, uint32_t span, uint32_t off) {
     Group q;
-    const uint32_t nlim = LIST ? p.n : p.n_main;
-    q.last_grp = !LIST && gi >= (nlim + span - 1) / span;
+    if constexpr (MODE == BATCH) {
+        q.last_grp = false;
+        q.g0 = gi * span;
+        q.j = q.g0 + off;
+        const uint32_t jl = q.j < p.n ? q.j : p.n - 1;   // (the last group's spare lanes: its last entry, a member)
+        q.jj = p.b_col[jl];
+        const TvBatchGeom r = p.b_geom[gi];
+        q.g.fast_begin = 0;
+        q.g.fast_end = uni(r.fast_end);
+        q.g.end = uni(r.end);
+        q.g.nb_min = uni(r.nb_min);
+        q.len = p.b_len[jl];
+        q.nb = (uint32_t)nblocks(q.len);
+        q.piece = p.data + p.b_off[jl];
+        return q;
+    }
+    constexpr bool listed = MODE == LIST;
+    const uint32_t nlim = listed ? p.n : p.n_main;
+    q.last_grp = !listed && gi >= (nlim + span - 1) / span;
     q.g0 = gi * span;
     q.j = q.last_grp ? p.last_idx : q.g0 + off;
     const uint32_t jl = q.last_grp ? p.last_idx : (q.j < nlim ? q.j : nlim - 1);
-    q.jj = LIST ? p.idx[jl] : jl;
+    q.jj = listed ? p.idx[jl] : jl;
     const bool is_last = q.jj == p.last_idx;
-    q.g = LIST ? wave_geom(p, __ballot(is_last) != 0, __ballot(!is_last) == 0)
-               : q.last_grp ? wave_geom(p, true, true) : main_geom(p, q.g0, span);
+    q.g = listed ? wave_geom(p, __ballot(is_last) != 0, __ballot(!is_last) == 0)
+                 : q.last_grp ? wave_geom(p, true, true) : main_geom(p, q.g0, span);
     q.len = is_last ? p.last_len : p.L;
     q.nb = (uint32_t)nblocks(q.len);
-    const uint32_t row = (LIST && p.rows) ? p.rows[jl] : q.jj;
+    const uint32_t row = (listed && p.rows) ? p.rows[jl] : q.jj;
     // a list launch always covers whole resident pieces (tv_core.hip resident_launch: data_off = 0, every block),
     // so list mode reads neither data_off nor, in start_state(), a chaining state
-    q.piece = p.data + (uint64_t)row * p.stride - (LIST ? 0 : p.data_off);
+    q.piece = p.data + (uint64_t)row * p.stride - (listed ? 0 : p.data_off);
     return q;
 }
 
@@ -506,10 +529,11 @@ __device__ __forceinline__ void rounds_wave(const TvPieces& p, const Ops& ops, c
 
 // A workgroup is PAIRS x {rounds, helper} waves over 64*PAIRS pieces.  Its waves go to distinct SIMDs, so with
 // <= 1 workgroup per CU no rounds wave shares its SIMD.  Each pair has its own 3 x 20 KiB K+W ring; the barrier is
-// workgroup-wide, so both pairs run the same (workgroup) block range.  LIST: one pair per workgroup.
-template <bool HASH, int PAIRS, bool LIST = false>
+// workgroup-wide, so both pairs run the same (workgroup) block range.  LIST and BATCH: one pair per workgroup.
+template <bool HASH, int PAIRS, int MODE = RESIDENT>
 __global__ __launch_bounds__(128 * PAIRS) void tv_split_kernel(TvPieces p) {
-    static_assert(!LIST || PAIRS == 1, "list mode runs one pair per workgroup");
+    constexpr bool LISTED = MODE != RESIDENT;   // entries answered one byte each (finish_list), whole pieces only
+    static_assert(!LISTED || PAIRS == 1, "list and batch mode run one pair per workgroup");
     __shared__ __attribute__((aligned(16))) uint4 ring[kBufs * PAIRS * kRingWords / 4];
     ClockStamp clk;
     clk.start(p);
@@ -517,7 +541,7 @@ __global__ __launch_bounds__(128 * PAIRS) void tv_split_kernel(TvPieces p) {
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t pair = wave % PAIRS;
     const uint32_t role = wave / PAIRS;        // 0 = rounds, 1 = helper
-    const Group q = resolve_group<LIST>(p, blockIdx.x, 64u * PAIRS, pair * 64u + lane);
+    const Group q = resolve_group<MODE>(p, blockIdx.x, 64u * PAIRS, pair * 64u + lane);
     const uint32_t lds_lane = (uint32_t)(uintptr_t)(void*)(ring + pair * kBufs * (kRingWords / 4)) + lane * 16u;
     const SplitOps ops;
     if (role != 0) {
@@ -525,9 +549,9 @@ __global__ __launch_bounds__(128 * PAIRS) void tv_split_kernel(TvPieces p) {
         return;
     }
     uint32_t h[5];
-    start_state<LIST>(p, q.jj, h);
+    start_state<LISTED>(p, q.jj, h);
     rounds_wave(p, ops, q, lds_lane, wave, h);
-    if (LIST) finish_list(p, q.j < p.n, q.j, q.jj, h);
+    if (LISTED) finish_list(p, q.j < p.n, q.j, q.jj, h);
     else finish<HASH>(p, q.last_grp ? (lane == 0 && pair == 0) : q.j < p.n_main, q.jj, q.g0 + pair * 64u, h, q.last_grp);
     clk.end(p);   // (wave 0 is a rounds wave)
 }
@@ -555,8 +579,9 @@ constexpr int kTwinHalf[6][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 1, 0, 1}, {0, 0
 constexpr int kTwinWaves[6] = {0, 2, 4, 4, 4, 4};
 constexpr int kTwinPairs[6] = {0, 1, 2, 2, 1, 1};
 
-template <bool HASH, int SHAPE, bool LIST = false>
+template <bool HASH, int SHAPE, int MODE = RESIDENT>
 __global__ __launch_bounds__(64 * kTwinWaves[SHAPE]) void tv_twin_kernel(TvPieces p) {
+    constexpr bool LISTED = MODE != RESIDENT;   // (as in tv_split_kernel)
     __shared__ __attribute__((aligned(16))) uint4 ring[kBufs * kRingWords / 4];
     constexpr uint32_t span = 32u * kTwinPairs[SHAPE];
     const uint32_t lane = threadIdx.x & 63u;
@@ -564,13 +589,13 @@ __global__ __launch_bounds__(64 * kTwinWaves[SHAPE]) void tv_twin_kernel(TvPiece
     const int role = kTwinRole[SHAPE][wave];                  // 0 rounds, 1 helper, 2 idle
     const uint32_t half = kTwinHalf[SHAPE][wave];             // pieces 32*half .. +31 of the group
     // companions (blockIdx past the real grid, TV_OPT_TWIN_FILL): re-hash main workgroup (blockIdx - real) % main
-    const uint32_t nmain_wgs = ((LIST ? p.n : p.n_main) + span - 1) / span;
-    const uint32_t real_wgs = nmain_wgs + (!LIST && p.n_main < p.n ? 1u : 0u);
+    const uint32_t nmain_wgs = ((LISTED ? p.n : p.n_main) + span - 1) / span;
+    const uint32_t real_wgs = nmain_wgs + (!LISTED && p.n_main < p.n ? 1u : 0u);
     const bool companion = blockIdx.x >= real_wgs;
     const uint32_t wgi = companion ? (blockIdx.x - real_wgs) % nmain_wgs : blockIdx.x;
     // a companion keeps the instruction stream of the workgroup it copies but, unless fill_all, points every
     // lane at that workgroup's first piece: the same loads, one piece's bytes instead of 32 pieces'
-    const Group q = resolve_group<LIST>(p, wgi, span, companion && !p.fill_all ? 0u : half * 32u + (lane >> 1));
+    const Group q = resolve_group<MODE>(p, wgi, span, companion && !p.fill_all ? 0u : half * 32u + (lane >> 1));
     const uint32_t lds_lane = (uint32_t)(uintptr_t)(void*)ring + half * 1024u + lane * 16u;
     ClockStamp clk;
     clk.start(p);
@@ -584,24 +609,25 @@ __global__ __launch_bounds__(64 * kTwinWaves[SHAPE]) void tv_twin_kernel(TvPiece
         return;
     }
     uint32_t h[5];
-    start_state<LIST>(p, q.jj, h);
+    start_state<LISTED>(p, q.jj, h);
     rounds_wave(p, ops, q, lds_lane, wave, h);
     clk.end(p);              // (wave 0 is a rounds wave in every shape)
     if (companion) return;   // its digests duplicate a main workgroup's: nothing to write
     const bool even = (lane & 1u) == 0;   // one writer per lane pair
-    if (LIST) finish_list(p, even && q.j < p.n, q.j, q.jj, h);
+    if (LISTED) finish_list(p, even && q.j < p.n, q.j, q.jj, h);
     else finish<HASH, true>(p, q.last_grp ? (wave == 0 && lane == 0) : (even && q.j < p.n_main), q.jj,
                             q.g0 + half * 32u, h, q.last_grp);
 }
 
 // ------------------------------------------------------------------------------------------
 // list kernel (incremental verify): lane j verifies shard piece idx[j]; same compression path as
-// the lane kernel.
+// the lane kernel.  MODE: LIST, or BATCH (launch position j is any torrent's piece, see resolve_group).
 // ------------------------------------------------------------------------------------------
+template <int MODE>
 __global__ __launch_bounds__(256) void tv_list_kernel(TvPieces p) {
     const uint32_t gw = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (gw * 64u >= p.n) return;   // (the grid is whole 4-wave workgroups)
-    const Group q = resolve_group<true>(p, gw, 64u, threadIdx.x & 63u);
+    const Group q = resolve_group<MODE>(p, gw, 64u, threadIdx.x & 63u);
     const WaveGeom& g = q.g;
     const uint8_t* piece = q.piece;
     uint32_t h[5];
@@ -756,13 +782,32 @@ hipError_t tv_launch_verify_list(const TvPieces& p, int kernel, hipStream_t s, u
     if (kernel == TV_KERNEL_TWIN) {
         const unsigned real = (p.n + 31) / 32;
         grid = p.fill_to > real ? p.fill_to : real;
-        launch(tv_twin_kernel<false, 1, true>, grid, 128, s, p);
+        launch(tv_twin_kernel<false, 1, LIST>, grid, 128, s, p);
     } else if (kernel == TV_KERNEL_SPLIT) {
         grid = (p.n + 63) / 64;
-        launch(tv_split_kernel<false, 1, true>, grid, 128, s, p);
+        launch(tv_split_kernel<false, 1, LIST>, grid, 128, s, p);
     } else {
         grid = (p.n + 255) / 256;
-        launch(tv_list_kernel, grid, 256, s, p);
+        launch(tv_list_kernel<LIST>, grid, 256, s, p);
+    }
+    if (workgroups) *workgroups = grid;
+    return hipGetLastError();
+}
+
+// One workgroup per group of tv_batch_span(kernel) positions (lane: four groups, one per wave); no companions.
+hipError_t tv_launch_verify_batch(const TvPieces& p, int kernel, hipStream_t s, uint32_t* workgroups) {
+    if (workgroups) *workgroups = 0;
+    if (p.n == 0) return hipSuccess;
+    unsigned grid;
+    if (kernel == TV_KERNEL_TWIN) {
+        grid = (p.n + 31) / 32;
+        launch(tv_twin_kernel<false, 1, BATCH>, grid, 128, s, p);
+    } else if (kernel == TV_KERNEL_SPLIT) {
+        grid = (p.n + 63) / 64;
+        launch(tv_split_kernel<false, 1, BATCH>, grid, 128, s, p);
+    } else {
+        grid = (p.n + 255) / 256;
+        launch(tv_list_kernel<BATCH>, grid, 256, s, p);
     }
     if (workgroups) *workgroups = grid;
     return hipGetLastError();

@@ -5,7 +5,8 @@
 // and the tail table of a hybrid call (hybrid_tails) and a hybrid stream's geometry and column pad ranges
 // (hybrid_stream_geometry, hybrid_col_range), the pad chunks of a hybrid list entry (hybrid_list_chunk;
 // tests/c/plan_hybrid_list_main.cpp, tests/test_plan_hybrid_list.py) and the stream engine's copy plan and row walk
-// (for_row_copies, walk_row_files), as plain host code with no HIP in it, so they are unit-tested
+// (for_row_copies, walk_row_files) and the launch order and group geometry of a batch (batch_plan;
+// tests/c/plan_batch_main.cpp, tests/test_plan_batch.py), as plain host code with no HIP in it, so they are unit-tested
 // on the CPU (tests/c/plan_test.cpp, tests/c/walk_main.cpp, tests/c/plan_v2_main.cpp, tests/c/plan_v2_blocks_main.cpp,
 // tests/c/plan_codec_main.cpp, tests/c/plan_list_main.cpp, tests/c/plan_hybrid_main.cpp,
 // tests/c/plan_hybrid_stream_main.cpp, tests/c/plan_stream_rows_main.cpp; tests/test_plan.py, test_plan_v2.py,
@@ -556,6 +557,59 @@ TV_PLAN_HD inline uint64_t hybrid_list_chunks(uint64_t piece_bytes, uint64_t tot
 TV_PLAN_HD inline bool hybrid_list_chunk(uint64_t piece_bytes, uint64_t total, uint64_t L, uint64_t piece, uint32_t k,
                                          uint64_t* b, uint64_t* e) {
     return hybrid_col_chunk(piece_bytes, total, L, piece, 0, L, k, b, e);
+}
+
+// ---- the launch order and group geometry of a batch (tv_batch.hip: tv_batch_verify) -----------------------------------
+//
+// lens: the length of every piece of the batch, in (torrent, piece) order; span: the entries of a group of the chosen
+// kernel form (32 twin, 64 split and lane).  The entries are launched longest first (a stable sort by SHA-1 block
+// count, so neighbouring pieces of a torrent stay neighbours and the longest serial chains start first) in groups of
+// `span` consecutive launch positions.  A group's waves run ONE block range (the kernels' barrier protocol), given by
+// its record: raw blocks [0, fast_end) for every member, blocks up to `end` on the padded-block path, every member
+// updating its digest below nb_min.  The padded-block path is the slow one, so a group is CLOSED EARLY when the next
+// entry would make nb_max - nfull_min exceed max(kBatchCutBlocks, nb_max / kBatchCutShare) -- at most 1 / kBatchCutShare
+// of a group's blocks run there -- and is then padded to `span` with copies of its own last entry (origin -1).  Both
+// constants are design parameters, not measurements.  The last group is not padded: the kernels point its spare lanes
+// at the launch's last entry, one of its members.
+// fast_end * 64 <= len for every member of a group: no raw-block load leaves any member's bytes (the kernels' memory
+// safety; tests/c/plan_batch_main.cpp, tests/test_plan_batch.py check it as an invariant).
+struct BatchGroup {
+    uint32_t fast_end, end, nb_min;   // min len / 64, max blocks, min blocks over the group's members
+};
+constexpr uint64_t kBatchCutBlocks = 8;
+constexpr uint64_t kBatchCutShare = 8;
+inline uint64_t sha1_blocks(uint64_t len) { return (len + 8) / 64 + 1; }   // (a piece of length 0 still has one)
+
+// launch[t]: the entry launch position t hashes; origin[t]: the entry it answers (-1: padding); groups[g]: positions
+// [g * span, (g + 1) * span).
+inline void batch_plan(uint64_t n, const uint64_t* lens, uint32_t span, std::vector<uint32_t>* launch,
+                       std::vector<int64_t>* origin, std::vector<BatchGroup>* groups) {
+    launch->clear();
+    origin->clear();
+    groups->clear();
+    std::vector<uint32_t> order(n);
+    for (uint64_t k = 0; k < n; k++) order[k] = (uint32_t)k;
+    std::stable_sort(order.begin(), order.end(),
+                     [&](uint32_t a, uint32_t b) { return sha1_blocks(lens[a]) > sha1_blocks(lens[b]); });
+    for (uint64_t i = 0; i < n;) {
+        const uint64_t nb_max = sha1_blocks(lens[order[i]]), cut = std::max(kBatchCutBlocks, nb_max / kBatchCutShare);
+        uint64_t nfull_min = lens[order[i]] / 64, nb_min = nb_max;
+        uint32_t taken = 0;
+        for (; taken < span && i < n; taken++, i++) {
+            const uint64_t len = lens[order[i]];
+            if (nb_max - std::min(nfull_min, len / 64) > cut) break;   // (never the group's first entry: 1 or 2 <= cut)
+            nfull_min = std::min(nfull_min, len / 64);
+            nb_min = std::min(nb_min, sha1_blocks(len));
+            launch->push_back(order[i]);
+            origin->push_back((int64_t)order[i]);
+        }
+        if (i < n)   // closed early (or full): every group but the last is whole
+            for (; taken < span; taken++) {
+                launch->push_back(launch->back());
+                origin->push_back(-1);
+            }
+        groups->push_back({(uint32_t)nfull_min, (uint32_t)nb_max, (uint32_t)nb_min});
+    }
 }
 
 }  // namespace tvi

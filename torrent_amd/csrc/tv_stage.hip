@@ -99,7 +99,7 @@ extern "C" {
 int tv_stage(tv_ctx* c, uint64_t linear_offset, const uint8_t* src, uint64_t len) {
     if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
     std::lock_guard<std::mutex> g(c->mu);
-    int rc = require_layout(c, false, true);
+    int rc = require_layout(c, false, true, /*batch_ok=*/true);
     if (rc) return rc;
     if (!src && len) return fail(c, TV_ERR_ARG, "src is NULL");
     if (linear_offset + len < linear_offset) return fail(c, TV_ERR_ARG, "offset + len overflows");
@@ -117,7 +117,7 @@ int tv_stage_many(tv_ctx* c, uint64_t n, const uint64_t* linear_offsets, const u
                   const uint64_t* lens) {
     if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
     std::lock_guard<std::mutex> g(c->mu);
-    int rc = require_layout(c, false, true);
+    int rc = require_layout(c, false, true, /*batch_ok=*/true);
     if (rc) return rc;
     if (n == 0) return TV_OK;
     if (!linear_offsets || !srcs || !lens) return fail(c, TV_ERR_ARG, "NULL argument");
@@ -209,7 +209,7 @@ int tv_stage_many(tv_ctx* c, uint64_t n, const uint64_t* linear_offsets, const u
 int tv_read(tv_ctx* c, uint64_t linear_offset, uint8_t* dst, uint64_t len) {
     if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
     std::lock_guard<std::mutex> g(c->mu);
-    int rc = require_layout(c, false, true);
+    int rc = require_layout(c, false, true, /*batch_ok=*/true);
     if (rc) return rc;
     if (!dst && len) return fail(c, TV_ERR_ARG, "dst is NULL");
     if (linear_offset + len < linear_offset) return fail(c, TV_ERR_ARG, "offset + len overflows");
@@ -253,7 +253,7 @@ int tv_read(tv_ctx* c, uint64_t linear_offset, uint8_t* dst, uint64_t len) {
 int tv_fill_synthetic(tv_ctx* c, uint64_t seed) {
     if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
     std::lock_guard<std::mutex> g(c->mu);
-    int rc = require_layout(c, false, true);
+    int rc = require_layout(c, false, true, /*batch_ok=*/true);
     if (rc) return rc;
     if (!c->count) return TV_OK;
     if (c->slots) return fail(c, TV_ERR_STATE, "tv_fill_synthetic: a slot pool (TV_OPT_LIST_SLOTS) holds no shard");
@@ -273,7 +273,7 @@ int tv_fill_synthetic(tv_ctx* c, uint64_t seed) {
         TV_HIP(c, hipStreamSynchronize(c->stream));
         return TV_OK;
     }
-    TV_HIP(c, tv_launch_fill(c->d_payload, c->stride, c->first, (uint32_t)c->count, c->L, seed, c->stream));
+    TV_HIP(c, tv_launch_fill(c->d_payload + c->region, c->stride, c->first, (uint32_t)c->count, c->L, seed, c->stream));
     TV_HIP(c, hipStreamSynchronize(c->stream));
     return TV_OK;
 }

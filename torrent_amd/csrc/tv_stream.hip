@@ -33,6 +33,11 @@ namespace tvi {
 // other buffer: for v1 pieces one SHA-1 launch (chaining values persist in d_state; the last column pads, compares
 // and writes the bitfield).  Host memory in flight: the ring.
 
+// A stream call with no stream begun: TV_ERR_STATE and `text` (a batch layout, where none can begin: its own text).
+static int no_stream(tv_ctx* c, const char* text) {
+    return c->batch_on ? batch_refused(c) : fail(c, TV_ERR_STATE, "%s", text);
+}
+
 // The row rule of the begun stream: the piece's valid bytes inside the column, 0 when the piece ends before it.  A v1
 // piece has piece_len bytes (piece.ts:16-19: only the torrent's last piece is short); a v2 or hybrid piece has its
 // table's (st.v2_bytes), so any row may be short or empty: every file ends a piece.
@@ -315,7 +320,7 @@ static int unit_launch(tv_ctx* c, int buf, uint64_t j0, uint64_t wcount, uint64_
 
 int stream_next_locked(tv_ctx* c, tv_stream_req* req) {
     StreamState& st = c->st;
-    if (!st.active) return fail(c, TV_ERR_STATE, "tv_stream_begin has not been called");
+    if (!st.active) return no_stream(c, "tv_stream_begin has not been called");
     if (st.outstanding)
         return fail(c, TV_ERR_STATE, "request %llu is still outstanding (commit it first)", (unsigned long long)st.req.seq);
     *req = tv_stream_req{};
@@ -343,7 +348,7 @@ int stream_next_locked(tv_ctx* c, tv_stream_req* req) {
 int stream_commit_locked(tv_ctx* c, const tv_stream_req* req, const uint8_t* src, uint64_t pitch, bool pinned,
                          uint64_t rows_copy) {
     StreamState& st = c->st;
-    if (!st.active) return fail(c, TV_ERR_STATE, "tv_stream_begin has not been called");
+    if (!st.active) return no_stream(c, "tv_stream_begin has not been called");
     if (!st.outstanding) return fail(c, TV_ERR_STATE, "no outstanding request (call tv_stream_next)");
     if (!req || req->seq != st.req.seq || req->piece != st.req.piece || req->rows != st.req.rows)
         return fail(c, TV_ERR_ARG, "the request does not match outstanding request %llu", (unsigned long long)st.req.seq);
@@ -401,7 +406,7 @@ int stream_commit_locked(tv_ctx* c, const tv_stream_req* req, const uint8_t* src
 // v1_out / v2_out (optional; tv_hybrid_stream_end): a hybrid stream's own two bitfields; bitfield_out is their AND.
 int stream_end_locked(tv_ctx* c, uint8_t* bitfield_out, uint8_t* v1_out = nullptr, uint8_t* v2_out = nullptr) {
     StreamState& st = c->st;
-    if (!st.active) return fail(c, TV_ERR_STATE, "tv_stream_begin has not been called");
+    if (!st.active) return no_stream(c, "tv_stream_begin has not been called");
     if (st.hash) {
         stream_abort_locked(c);
         return fail(c, TV_ERR_STATE, "the active stream is a creation stream (it ends with tv_stream_hash_end); aborted");
@@ -454,7 +459,7 @@ int stream_end_locked(tv_ctx* c, uint8_t* bitfield_out, uint8_t* v1_out = nullpt
 // digest codec, in piece order.  Every refusal comes before the first byte is written.
 int stream_hash_end_locked(tv_ctx* c, uint8_t* digests_out, uint8_t* roots_out) {
     StreamState& st = c->st;
-    if (!st.active) return fail(c, TV_ERR_STATE, "tv_stream_hash_begin has not been called");
+    if (!st.active) return no_stream(c, "tv_stream_hash_begin has not been called");
     if (!st.hash) {
         stream_abort_locked(c);
         return fail(c, TV_ERR_STATE, "the active stream is a verify stream (it ends with tv_stream_end); aborted");
@@ -1048,7 +1053,7 @@ int tv_stream_commit_from(tv_ctx* c, const tv_stream_req* req, const uint8_t* sr
 int tv_stream_unreadable(tv_ctx* c, uint64_t piece) {
     if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
     std::lock_guard<std::mutex> g(c->mu);
-    if (!c->st.active) return fail(c, TV_ERR_STATE, "tv_stream_begin has not been called");
+    if (!c->st.active) return no_stream(c, "tv_stream_begin has not been called");
     if (c->st.hash)   // (the stream stays active: tv_stream_abort gives it up)
         return fail(c, TV_ERR_STATE, "tv_stream_unreadable: a creation stream cannot skip a piece");
     if (piece < c->first || piece >= c->first + c->count)
@@ -1086,7 +1091,7 @@ int tv_stream_fill_synthetic(tv_ctx* c, const tv_stream_req* req, uint64_t seed)
     if (!c) return fail(nullptr, TV_ERR_ARG, "ctx is NULL");
     std::lock_guard<std::mutex> g(c->mu);
     const StreamState& st = c->st;
-    if (!st.active || !st.outstanding) return fail(c, TV_ERR_STATE, "no outstanding request (call tv_stream_next)");
+    if (!st.active || !st.outstanding) return no_stream(c, "no outstanding request (call tv_stream_next)");
     if (!req || req->seq != st.req.seq) return fail(c, TV_ERR_ARG, "the request does not match the outstanding one");
     const tv_stream_req r = st.req;
     uint8_t* slot = c->ring[st.slot];

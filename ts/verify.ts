@@ -54,6 +54,11 @@ const SYMBOLS = {
   },
   tv_verify_list: { parameters: ["pointer", "pointer", "u64", "pointer"], result: "i32", nonblocking: true },
   tv_hash: { parameters: ["pointer", "pointer"], result: "i32", nonblocking: true },
+  // The batch layout (many v1 torrents, one launch): bound so that the table covers the header; a TS host function
+  // for it (the counterpart of torrent_amd/batch.py) is not part of this module yet.
+  tv_set_batch_layout: { parameters: ["pointer", "u64", "pointer", "pointer", "pointer"], result: "i32", nonblocking: true },
+  tv_batch_select: { parameters: ["pointer", "u64"], result: "i32" },
+  tv_batch_verify: { parameters: ["pointer", "pointer", "pointer"], result: "i32", nonblocking: true },
   // BitTorrent v2 (SHA-256 merkle piece roots): bound so that the table covers the header; a TS host function for v2
   // (the counterpart of torrent_amd/v2.py) is not part of this module yet.
   tv_v2_set_pieces: { parameters: ["pointer", "u64", "pointer", "pointer", "pointer"], result: "i32" },
