@@ -35,6 +35,7 @@ from __future__ import annotations
 import argparse
 import hashlib
 import os
+import re
 import struct
 import sys
 
@@ -398,6 +399,9 @@ def gen_helper(src=None, off_base: int = 0):
 # followed by `s_nop 0` to keep the stream 8-byte aligned (a long misaligned run issues at ~5.07 instead of
 # 4.07 cycles), with two waits: before round 0 (reads 0-4) and round 40 (reads 5-9); the loop over the full
 # blocks (gen_twin_trip_block) pairs its 4-byte instructions instead and has no s_nop.
+# The twin kernel's rounds waves now run the role-split rounds further down (gen_roles, gen_roles_trip_block:
+# sha1_roles_asm.h) on the same helper, layout and loop shape; the rounds described here, which both lanes of a
+# pair run alike, stay generated as the stream those are measured against (tools/gen_ubench_dpp.py `trips`).
 # Buffer layout [k][wave][lane][4 words]: lane 2i+b of wave w
 # holds W[8k+b], W[8k+b+2], W[8k+b+4], W[8k+b+6] (+K) of piece 32w+i at k*2048 + w*1024 + lane*16, written
 # and read as one contiguous KiB per wave (tools/gen_ubench_dpp.py, profiles/r02/ubench_dpp.log: the rounds
@@ -572,6 +576,246 @@ def twin_rounds_loop_text() -> str:
         # code that follows (the loop over the padded tail blocks) keeps its 64-byte placement
         L += [".p2align 6", "s_nop 0", "s_nop 0"]
     return "\n".join(f'    "{l}\\n"' for l in L)
+
+
+# ---- TWIN: role-split rounds, 4.5 instructions per round ----
+# A lone wave issues one instruction per ~4.07 cycles whatever its kind, dependent or not, so the rounds wave's time
+# is its instruction count.  The two lanes of a pair therefore do not run the same rounds: of each two rounds t, t+1
+# (a PAIR of rounds), role 0 computes round t and role 1 round t+1.  In a rounds wave the roles of a piece sit 8
+# lanes apart in a row of 16: lane 16r+p (p < 8) is role 0 of the wave's piece 8r+p, lane 16r+8+p its role 1; the
+# partner is reached with DPP row_ror:8 (a swap), and bank_mask 0x3 / 0xc writes only the role-0 / role-1 lanes.
+# With a_k = `a` before round k (a_0 = h0, a_-1 = h1, R a_-2 = h2, ...), R = rotl30, registers as (role 0 | role 1),
+# the state at the start of the pair of rounds t, t+1 is
+#     W = (a_t-1 | a_t)   C = (R a_t-2 | R a_t-1)   D = (R a_t-3 | R a_t-2)   E = (R a_t-4 | R a_t-3)
+# and KW = (K+W_t | K+W_t+1) is each role's own word of the quad it read (role b reads helper lane 2i+b).  Nine
+# instructions, in an order that keeps two instructions between a VALU write and a DPP read of the register:
+#     1 ROL  = rotl5(W)                          6 Dn  = rotr7(ROL) = R(W at 1): the next D
+#     2 F    = f(W, C, D)                        7 T   = W[partner]              (a_t | a_t+1)
+#     3 G    = F + E + KW                        8 W[role 1] = ROL2[partner] + G (a_t+1 | a_t+2)
+#     4 W[role 0] = ROL[partner] + G             9 Cn  = R(T): the next C; the next E is this C
+#     5 ROL2 = rotl5(W)      (a_t+1 | a_t)
+# F and `F + e + KW` serve both rounds at once; the serial part, rotl5 and add twice, passes between the roles.
+# Both rounds of a pair fall in one 20-round group.  40 x 9 + 1 copy + 6 feed-forward = 367 VALU per block, where
+# the rounds both lanes ran alike took 405.
+# The chaining value stays in this form across the blocks of the loop: HW = (h1 | h0), HC = (h2 | R h1),
+# HD = (h3 | h2), HE = (h4 | h3) in %[h0..h3]; the first pair reads them in place (only W is copied, step 4
+# overwrites half of it), and the feed-forward is one add each, plus R(new HW) of role 0 moved into role 1 of HC.
+# Both generated functions convert from and to the plain h[5] in both lanes, once per call.
+ROLE0, ROLE1, BOTH = 0x3, 0xC, 0xF    # DPP bank_mask: the lanes an instruction writes
+DPP_DISTANCE = 2                      # instructions between a VALU write of a register and a DPP read of it
+
+
+def dpp_source(op):
+    """The register an instruction reads from another lane (or its own) through DPP, or None."""
+    return op[2] if op[0] in ("v_add_u32_dpp", "v_mov_b32_dpp") else None
+
+
+def check_dpp_distance(ins):
+    """Every DPP read in the instruction list (executed in order) is DPP_DISTANCE or more instructions after the
+    last VALU write of its source; inline asm gets no hazard padding.  A register the list has not written yet
+    counts as written just before its first instruction (the compiler's code, which knows of no DPP here)."""
+    last = {}
+    for i, op in enumerate(ins):
+        src = dpp_source(op)
+        if src is not None:
+            gap = i - last.get(src, -1) - 1
+            assert gap >= DPP_DISTANCE, f"DPP read of {src} {gap} instructions after its write (instruction {i}: {op})"
+        if op[0].startswith("v_"):
+            last[op[1]] = i
+    return True
+
+
+def _role_pairs(ins, chain, kw, reads_after=None):
+    """Append the 40 pairs of rounds of one block to ins.  chain = (W, C, D, E): the registers pair 0 reads its
+    state from (read-only when they are the loop's chaining registers %[h0..h3]; the tail block passes working
+    registers).  kw(j) = the register holding pair j's K+W word.  reads_after = (pair index, instructions) to
+    insert after that pair.  Working registers: W = r0, D = r1, G = r2, and r3, r4, t0 taken in turn for
+    C / E / ROL.  Returns the registers of the final (W, C, D, E)."""
+    W, D, G = "r0", "r1", "r2"
+    free = [x for x in ("r3", "r4", "t0") if x not in chain]
+    pool = {"r3", "r4", "t0"}
+    w_rd, C, d_rd, E = chain
+    if w_rd != W:
+        ins.append(("v_mov_b32", W, w_rd))
+    for j in range(40):
+        rol = free.pop(0)
+        ins.append(("v_alignbit_b32", rol, w_rd, w_rd, 27))                       # 1
+        ins.append(_fop(2 * j, G, w_rd, C, d_rd))                                 # 2
+        ins.append(("v_add3_u32", G, G, E, kw(j)))                                # 3
+        if E in pool:
+            free.append(E)
+        ins.append(("v_add_u32_dpp", W, rol, G, ("ror8", ROLE0)))                 # 4
+        rol2 = free.pop(0)
+        ins.append(("v_alignbit_b32", rol2, W, W, 27))                            # 5
+        ins.append(("v_alignbit_b32", D, rol, rol, 7))                            # 6
+        ins.append(("v_mov_b32_dpp", rol, W, ("ror8", BOTH)))                     # 7
+        ins.append(("v_add_u32_dpp", W, rol2, G, ("ror8", ROLE1)))                # 8
+        ins.append(("v_alignbit_b32", rol, rol, rol, 2))                          # 9
+        free.append(rol2)
+        w_rd, C, d_rd, E = W, rol, D, C
+        if reads_after is not None and reads_after[0] == j:
+            ins += reads_after[1]
+    return W, C, D, E
+
+
+def gen_roles(off_base: int = 0):
+    """One role-split TWIN rounds block with its own 10 reads issued first (tv_sha1_twin_lds: the padded tail
+    blocks).  Operands as gen_lds: r0-4 (out), t0-1 (tmp), h0-4 (in, the plain chaining value in both lanes), addr
+    (this lane's LDS byte address).  r = the plain state after round 79 in both lanes.  Two waits, before pair 0
+    (reads 0-4) and pair 20 (reads 5-9), each with an s_nop that keeps the 8-byte instructions aligned."""
+    ins = [("ds_read_b128", k, off_base + k * TWIN_READ_BYTES) for k in range(10)]
+    # W = (h1 | h0), C = (h2 | R h1), D = (h3 | h2), E = (h4 | h3) in working registers
+    ins += [("v_mov_b32", "r0", "h0"), ("v_mov_b32_dpp", "r0", "h1", ("own", ROLE0)),
+            ("v_alignbit_b32", "r3", "h1", "h1", 2), ("v_mov_b32_dpp", "r3", "h2", ("own", ROLE0)),
+            ("v_mov_b32", "r1", "h2"), ("v_mov_b32_dpp", "r1", "h3", ("own", ROLE0)),
+            ("v_mov_b32", "r4", "h3"), ("v_mov_b32_dpp", "r4", "h4", ("own", ROLE0)),
+            ("s_waitcnt_lgkm", 5), ("s_nop",)]
+    W, C, D, E = _role_pairs(ins, ("r0", "r3", "r1", "r4"), lambda j: ring_reg(j // 4, j % 4),
+                             reads_after=(19, [("s_waitcnt_lgkm", 0), ("s_nop",)]))
+    # final W = (a79 | a80), C = (R a78 | R a79), D = (R a77 | R a78), E = (R a76 | R a77)  ->  plain r0..r4
+    assert (W, C, D, E) == ("r0", "t0", "r1", "r3"), (W, C, D, E)
+    ins += [("v_mov_b32", "r2", C), ("v_mov_b32_dpp", "r2", D, ("own", ROLE1)),      # r2 = R a78
+            ("v_mov_b32_dpp", "t1", W, ("ror8", BOTH)),                              # t1 = (a80 | a79)
+            ("v_mov_b32_dpp", "r4", E, ("ror8", BOTH)),
+            ("v_mov_b32_dpp", "r4", E, ("own", ROLE0)),                              # r4 = R a76
+            ("v_mov_b32_dpp", "r3", D, ("own", ROLE0)),                              # r3 = R a77 (E's register)
+            ("v_mov_b32", "r1", W), ("v_mov_b32_dpp", "r1", "t1", ("own", ROLE1)),   # r1 = a79
+            ("v_mov_b32_dpp", "r0", "t1", ("own", ROLE0))]                           # r0 = a80
+    check_dpp_distance(ins)
+    return ins
+
+
+def gen_roles_trip_block(s: int, off_next: int):
+    """One block of the two-block-trip TWIN rounds loop on register set s, chaining registers %[h0..h3] in the
+    role-split form, feed-forward included (the caller adds the barrier).  On entry this block's ten reads
+    (issued by the previous block, or the prologue) are the only LDS operations in flight; its single wait retires
+    them.  After the pair of rounds holding TWIN_TRIP_AT it issues the ten reads of the next block (buffer at
+    off_next) into the other set, whose last use was the previous block's final pair.
+    The feed-forward's four adds are 4-byte instructions, in two adjacent pairs; the barrier and the next block's
+    wait (or the trip's s_sub and s_cbranch) are a third pair, so every 8-byte instruction stays at 0 mod 8."""
+    ins = [("s_waitcnt_lgkm", 0)]
+    reads = [("ds_read_b128_abs", TWIN_SET_QUADS * (1 - s) + q, off_next + q * TWIN_READ_BYTES)
+             for q in range(TWIN_SET_QUADS)]
+    W, C, D, E = _role_pairs(ins, ("h0", "h1", "h2", "h3"), lambda j: twin_set_reg(s, j // 4, j % 4),
+                             reads_after=(TWIN_TRIP_AT // 2, reads))
+    ins += [("v_add_u32", "h0", "h0", W), ("v_add_u32", "h2", "h2", D),
+            ("v_alignbit_b32", "t1", "h0", "h0", 2),              # role 0: R(new h1), for role 1 of HC
+            ("v_add_u32", "h3", "h3", E), ("v_add_u32", "h1", "h1", C),
+            ("v_mov_b32_dpp", "h1", "t1", ("ror8", ROLE1))]
+    return ins
+
+
+def roles_loop_entry():
+    """Plain h0..h4 in both lanes -> HW, HC, HD, HE in %[h0..h3] (%[h4] is then unused), around the loop's three
+    leading scalar instructions, which stand between the compiler's last write of h and the first DPP read."""
+    return [("v_alignbit_b32", "t1", "h1", "h1", 2),
+            ("s_waitcnt_lgkm", 0), ("s_text", "s_lshr_b32 %[cnt], %[nsteps], 1"), ("s_text", "s_bitcmp1_b32 %[nsteps], 0"),
+            ("v_mov_b32_dpp", "h0", "h1", ("own", ROLE0)), ("v_mov_b32_dpp", "h1", "h2", ("own", ROLE0)),
+            ("v_mov_b32_dpp", "h2", "h3", ("own", ROLE0)), ("v_mov_b32_dpp", "h3", "h4", ("own", ROLE0)),
+            ("v_mov_b32_dpp", "h1", "t1", ("own", ROLE1))]
+
+
+def roles_loop_exit():
+    """HW, HC, HD, HE -> the plain h0..h4 in both lanes (after the loop's closing wait)."""
+    return [("s_waitcnt_lgkm", 0),
+            ("v_mov_b32_dpp", "t1", "h0", ("ror8", BOTH)),        # (h0 | h1)
+            ("v_mov_b32_dpp", "h4", "h3", ("ror8", BOTH)), ("v_mov_b32_dpp", "h4", "h3", ("own", ROLE0)),
+            ("v_mov_b32_dpp", "h3", "h2", ("own", ROLE0)), ("v_mov_b32_dpp", "h2", "h1", ("own", ROLE0)),
+            ("v_mov_b32_dpp", "h1", "h0", ("own", ROLE0)), ("v_mov_b32_dpp", "h1", "t1", ("own", ROLE1)),
+            ("v_mov_b32_dpp", "h0", "t1", ("own", ROLE0))]
+
+
+def roles_rounds_stream(nsteps: int):
+    """The instructions roles_rounds_loop_text executes for nsteps blocks, in order (twin_trips_walk), for the
+    emulator and the DPP-distance check: entry conversion, prologue reads, the blocks with their barriers, exit
+    conversion.  The s_sub / s_cbranch / s_branch between trips are left out, which only shortens distances."""
+    walk = twin_trips_walk(nsteps)   # the blocks in the order the loop text's control flow runs them
+    assert [buf for _, buf, _ in walk] == [k % LDS_BUFS for k in range(nsteps)]
+    ins = roles_loop_entry()
+    ins += [("ds_read_b128_abs", TWIN_SET_QUADS * walk[0][0] + q, q * TWIN_READ_BYTES) for q in range(TWIN_SET_QUADS)]
+    for k, (s, _, nxt) in enumerate(walk):
+        assert k == 0 or (walk[k - 1][0] != s and walk[k - 1][2] == walk[k][1])   # the reads the block before issued
+        ins += gen_roles_trip_block(s, nxt * RING_BYTES) + [("s_barrier",)]
+    return ins + roles_loop_exit()
+
+
+def _roles_block_lines(s: int, nxt: int):
+    return _emit_lines(gen_roles_trip_block(s, nxt * RING_BYTES))
+
+
+def _set_base(s: int) -> int:
+    return RING_BASE + 4 * TWIN_SET_QUADS * s
+
+
+def roles_block_macro():
+    """The body of the assembler macro `kw, rd, off` that stands for a block of the loop: the block on register set 0
+    with its K+W registers written v[\\kw+i], the registers its reads fill v[\\rd+i:\\rd+j] and their offsets
+    \\off+n.  The seven blocks of the loop text differ in nothing else, so the header holds the block once."""
+    kw0, rd0, off = _set_base(0), _set_base(1), RING_BYTES
+    body = []
+    for l in _roles_block_lines(0, 1):
+        m = re.match(r"ds_read_b128 v\[(\d+):(\d+)\], (\S+) offset:(\d+)$", l)
+        if m:
+            lo, hi, n = int(m.group(1)), int(m.group(2)), int(m.group(4))
+            body.append(f"ds_read_b128 v[\\rd+{lo - rd0}:\\rd+{hi - rd0}], {m.group(3)} offset:\\off+{n - off}")
+        else:
+            body.append(re.sub(r"\bv(\d+)\b", lambda m: f"v[\\kw+{int(m.group(1)) - kw0}]", l))
+    return body
+
+
+def expand_roles_block(body, kw: int, rd: int, off: int):
+    """What the assembler makes of the macro for these arguments, as the lines _emit_lines would have written."""
+    out = []
+    for l in body:
+        l = re.sub(r"v\[\\rd\+(\d+):\\rd\+(\d+)\]", lambda m: f"v[{rd + int(m.group(1))}:{rd + int(m.group(2))}]", l)
+        l = re.sub(r"v\[\\kw\+(\d+)\]", lambda m: f"v{kw + int(m.group(1))}", l)
+        out.append(re.sub(r"offset:\\off\+(\d+)", lambda m: f"offset:{off + int(m.group(1))}", l))
+    return out
+
+
+def roles_rounds_loop_text() -> str:
+    """The role-split TWIN rounds wave over nsteps (>= 1) blocks from ring buffer 0 in two-block trips: the control
+    flow, LDS ordering and 64-byte placement of twin_rounds_loop_text, with gen_roles_trip_block as the block
+    (written once, as a macro, and checked here to expand to every block's own lines) between the entry and exit
+    conversions of the chaining value."""
+    plan = twin_trips_plan()
+    body = roles_block_macro()
+    assert all("\\" not in l for l in _roles_block_lines(0, 1))
+
+    def prologue(s):
+        return _emit_lines([("ds_read_b128_abs", TWIN_SET_QUADS * s + q, q * TWIN_READ_BYTES)
+                            for q in range(TWIN_SET_QUADS)])
+
+    def block(s, nxt):
+        # 4-byte instructions only in adjacent pairs (gen_roles_trip_block): every 8-byte instruction sits at
+        # 0 mod 8 and the loop needs no s_nop
+        args = (_set_base(s), _set_base(1 - s), nxt * RING_BYTES)
+        assert expand_roles_block(body, *args) == _roles_block_lines(s, nxt), (s, nxt)
+        return ["tv_roles_block_%= {}, {}, {}".format(*args)] + (STAMP_SEQ if STAMP else ["s_barrier"])
+
+    L = [".macro tv_roles_block_%= kw, rd, off"] + body + [".endm"]
+    L += _emit_lines(roles_loop_entry()) + ["s_cbranch_scc1 L_rodd_%="]
+    L += prologue(0) + ["s_sub_u32 %[cnt], %[cnt], 1", "s_branch L_rloop_%="]
+    # odd block count: one single-block trip on set 1, then into the loop at the pair starting on buffer 1
+    s, _, nxt = plan["pre"]
+    L += ["L_rodd_%=:"] + prologue(s) + [".p2align 3", "s_nop 0"] + block(s, nxt)
+    L += ["s_sub_u32 %[cnt], %[cnt], 1", "s_cbranch_scc1 L_rdone_%=", f"s_branch L_rpair{plan['odd_entry']}_%="]
+    if TWIN_RALIGN is not None:
+        L += [".p2align 6"] + ["s_nop 0"] * (1 + 2 * int(TWIN_RALIGN))
+    else:
+        L += [".p2align 3", "s_nop 0"]
+    L.append("L_rloop_%=:")
+    for p in range(LDS_BUFS):
+        if p:
+            L.append(f"L_rpair{p}_%=:")
+        for s, _, nxt in plan["loop"][2 * p:2 * p + 2]:
+            L += block(s, nxt)
+        L += ["s_sub_u32 %[cnt], %[cnt], 1",
+              "s_cbranch_scc1 L_rdone_%=" if p < LDS_BUFS - 1 else "s_cbranch_scc0 L_rloop_%="]
+    L += ["L_rdone_%=:"] + _emit_lines(roles_loop_exit())
+    if TWIN_RALIGN is not None:
+        L += [".p2align 6", "s_nop 0", "s_nop 0"]   # (the statement ends at 8 mod 64, as twin_rounds_loop_text's)
+    return "\n".join('    "{}\\n"'.format(l.replace("\\", "\\\\")) for l in L)
 
 
 def rounds_loop_text() -> str:
@@ -797,6 +1041,8 @@ def emulate(ins, regs: dict, lds: dict | None = None, addr: int = 0, on_barrier=
             wr(op[1], v(op[2]) ^ v(op[3]))
         elif o == "v_add_u32":
             wr(op[1], (v(op[2]) + v(op[3])) & M32)
+        elif o == "v_mov_b32":
+            wr(op[1], v(op[2]))
         elif o == "v_perm_b32":   # D.byte[i] = byte sel.byte[i] of {S0:S1} (0-3: S1, 4-7: S0; 12: 0x00)
             cat = ((v(op[2]) << 32) | v(op[3])).to_bytes(8, "little")
             sel = v(op[4]).to_bytes(4, "little")
@@ -823,7 +1069,7 @@ def emulate(ins, regs: dict, lds: dict | None = None, addr: int = 0, on_barrier=
         elif o == "s_barrier":
             if on_barrier is not None:
                 on_barrier({a for _, _, adrs in pending for a in adrs})
-        elif o == "s_nop":
+        elif o in ("s_nop", "s_text"):   # (s_text: a scalar instruction of the loop's control flow, as written)
             pass
         else:
             raise ValueError(o)
@@ -833,12 +1079,29 @@ def emulate(ins, regs: dict, lds: dict | None = None, addr: int = 0, on_barrier=
 
 
 def emulate_twin(ins, regs2, lds, addrs, on_barrier=None, pend=None, drain: bool = True):
-    """Run an instruction list on the two lanes of a TWIN pair in lockstep (regs2 / addrs per lane).
-    v_add_u32_dpp reads its first source from the owning lane (op[4]); every other instruction runs per
-    lane through emulate(), with each lane's in-flight reads carried across instructions."""
+    """Run an instruction list on the two lanes of a TWIN pair in lockstep (regs2 / addrs per lane: lane b is
+    helper lane 2i + b, or role b of a role-split rounds wave).  v_add_u32_dpp with a lane number reads its first
+    source from that lane of the pair (op[4]).  With (ctrl, bank_mask) instead, it and v_mov_b32_dpp read their
+    first source through DPP -- ctrl "ror8" = from the partner, "own" = from the lane itself -- and write only the
+    lanes of bank_mask (ROLE0, ROLE1 or BOTH).  Every other instruction runs per lane through emulate(), with
+    each lane's in-flight reads carried across instructions."""
     pend = pend if pend is not None else ([], [])
     for op in ins:
-        if op[0] == "v_add_u32_dpp":
+        if op[0] in ("v_add_u32_dpp", "v_mov_b32_dpp") and isinstance(op[-1], tuple):
+            dst, src, (ctrl, bank) = op[1], op[2], op[-1]
+            src1 = op[3] if op[0] == "v_add_u32_dpp" else None
+            assert bank in (ROLE0, ROLE1, BOTH) and ctrl in ("ror8", "own"), op
+            vals = {}
+            for ln in range(2):
+                if not bank & (ROLE0, ROLE1)[ln]:
+                    continue
+                frm = 1 - ln if ctrl == "ror8" else ln
+                assert all(src not in rs for rs, _, _ in pend[frm]), f"DPP read of {src} in flight"
+                assert all(src1 not in rs and dst not in rs for rs, _, _ in pend[ln]), "in-flight register"
+                vals[ln] = (regs2[frm][src] + (regs2[ln][src1] if src1 is not None else 0)) & M32
+            for ln, val in vals.items():
+                regs2[ln][dst] = val
+        elif op[0] == "v_add_u32_dpp":
             _, dst, src, src1, b = op
             vals = []
             for ln in range(2):
@@ -919,6 +1182,12 @@ def _check_block(block: bytes, h):
         for ln in range(2):
             got = [(h[i] + regs2[ln][f"r{i}"]) & M32 for i in range(5)]
             assert got == exp, f"SHA1_TWIN mismatch (lane {ln})"
+        # role-split rounds: roles 0 and 1 of that piece read helper lanes 2 and 3's words
+        regs2 = [dict(base), dict(base)]
+        emulate_twin(gen_roles(0), regs2, lds, [1024 + 2 * 16, 1024 + 3 * 16])
+        for ln in range(2):
+            got = [(h[i] + regs2[ln][f"r{i}"]) & M32 for i in range(5)]
+            assert got == exp, f"SHA1_ROLES mismatch (role {ln})"
     return exp
 
 
@@ -1003,8 +1272,9 @@ def check_split_mid_stream(blocks, h, pre: bool = False):
     return [regs[f"h{i}"] for i in range(5)]
 
 
-def check_twin_stream(blocks, h):
-    """The TWIN rounds loop over consecutive blocks as twin_rounds_loop_text lays it out, for the lane pair
+def check_twin_stream(blocks, h, roles: bool = False):
+    """The TWIN rounds loop over consecutive blocks as twin_rounds_loop_text lays it out (roles: the role-split loop,
+    roles_rounds_stream, with the DPP-distance rule checked over the whole stream), for the lane pair
     of piece 0, against the helper protocol (as check_rounds_stream): at the barrier ending block k, block
     k+3's buffer is poisoned and block k+2 written; a read in flight there must not be rewritten."""
     lds = {}
@@ -1030,6 +1300,12 @@ def check_twin_stream(blocks, h):
             put(k + 2, kws[k + 2], in_flight)
 
     regs2 = [{f"h{i}": h[i] for i in range(5)} for _ in range(2)]
+    if roles:
+        ins = roles_rounds_stream(len(blocks))
+        check_dpp_distance(ins)
+        emulate_twin(ins, regs2, lds, [0, 16], on_barrier=on_barrier)
+        assert all(regs2[0][f"h{i}"] == regs2[1][f"h{i}"] for i in range(5)), "twin roles disagree"
+        return [regs2[0][f"h{i}"] for i in range(5)]
     walk = twin_trips_walk(len(blocks))   # the blocks in the order the loop text's control flow runs them
     assert [buf for _, buf, _ in walk] == [k % LDS_BUFS for k in range(len(blocks))]
     ins = [("ds_read_b128_abs", TWIN_SET_QUADS * walk[0][0] + q, q * TWIN_READ_BYTES) for q in range(TWIN_SET_QUADS)]
@@ -1084,6 +1360,8 @@ def self_check():
         h0 = [0x67452301, 0xEFCDAB89, 0x98BADCFE, 0x10325476, 0xC3D2E1F0]
         h = check_twin_stream([padded[i:i + 64] for i in range(0, len(padded), 64)], h0)
         assert struct.pack(">5I", *h) == hashlib.sha1(msg).digest(), ("twin stream", n)
+        h = check_twin_stream([padded[i:i + 64] for i in range(0, len(padded), 64)], h0, roles=True)
+        assert struct.pack(">5I", *h) == hashlib.sha1(msg).digest(), ("role-split twin stream", n)
     return True
 
 
@@ -1128,6 +1406,14 @@ def _emit_lines(ins, full: bool = False):
             lines.append("s_barrier")
         elif o == "s_nop":
             lines.append("s_nop 0")
+        elif o in ("v_add_u32_dpp", "v_mov_b32_dpp") and isinstance(op[-1], tuple):
+            ctrl, bank = op[-1]
+            lines.append(f"{o} " + ", ".join(_opnd(x, full) for x in op[1:-1]) + " "
+                         + {"ror8": "row_ror:8", "own": "quad_perm:[0,1,2,3]"}[ctrl] + f" row_mask:0xf bank_mask:0x{bank:x}")
+        elif o == "v_mov_b32":
+            lines.append(f"v_mov_b32_e64 {_opnd(op[1], full)}, {_opnd(op[2], full)}")   # (8 bytes, as every VALU here)
+        elif o == "s_text":
+            lines.append(op[1])
         elif o == "v_add_u32_dpp":
             b = op[4]
             lines.append(f"v_add_u32_dpp {_opnd(op[1], full)}, {_opnd(op[2], full)}, {_opnd(op[3], full)} "
@@ -1297,6 +1583,55 @@ __device__ __forceinline__ void tv_sha1_twin_schedule_lds(const uint32_t raw[16]
 """
 
 
+ROLES_HEADER = """// GENERATED by tools/gen_sha1_asm.py -- do not edit.  Regenerate with:
+//   python3 tools/gen_sha1_asm.py
+// The instruction streams below are checked against hashlib by the generator's emulator before they are written.
+#pragma once
+#include <stdint.h>
+
+// ---- TWIN kernel, role-split rounds (tools/gen_sha1_asm.py gen_roles, gen_roles_trip_block): what the twin
+// kernel's rounds waves run.  (sha1_asm.h still carries tv_sha1_twin_lds and tv_sha1_twin_rounds_loop, the rounds
+// both lanes of a pair ran alike, for A/B builds; no kernel calls them.)  Lane 16r+p (p < 8) of a rounds wave is
+// role 0 of the wave's piece 8r+p, lane 16r+8+p its role 1, and role b's `addr` is that of helper lane 2(8r+p)+b:
+// ring + (wave & 1)*1024 + (2(8r+p)+b)*16.  Both functions take and return the plain chaining value / state in BOTH
+// lanes of a pair, and need every lane of the wave active (the roles exchange values through DPP).
+
+// One block of 80 rounds for a lane pair, with its own 10 LDS reads (waits for them before returning).
+__device__ __forceinline__ void tv_sha1_roles_lds(const uint32_t h[5], uint32_t r[5], uint32_t addr) {{
+    uint32_t t0, t1;
+    asm volatile(
+{roles_lds}
+    : [r0] "=&v"(r[0]), [r1] "=&v"(r[1]), [r2] "=&v"(r[2]), [r3] "=&v"(r[3]), [r4] "=&v"(r[4]),
+      [t0] "=&v"(t0), [t1] "=&v"(t1)
+    : [h0] "v"(h[0]), [h1] "v"(h[1]), [h2] "v"(h[2]), [h3] "v"(h[3]), [h4] "v"(h[4]), [addr] "v"(addr){addr2}
+    : {ring_clobbers}, "memory");
+}}
+
+// The TWIN rounds wave over nsteps (>= 1) blocks from ring buffer 0 in which every lane updates.  The block is
+// written once, as an assembler macro of its K+W registers, the registers its reads fill and their offset.
+__device__ __forceinline__ void tv_sha1_roles_rounds_loop(uint32_t h[5], uint32_t addr, uint32_t nsteps) {{
+    uint32_t r[5], t0, t1, cnt;
+    asm volatile(
+{roles_rounds_loop}
+    : [h0] "+v"(h[0]), [h1] "+v"(h[1]), [h2] "+v"(h[2]), [h3] "+v"(h[3]), [h4] "+v"(h[4]),
+      [r0] "=&v"(r[0]), [r1] "=&v"(r[1]), [r2] "=&v"(r[2]), [r3] "=&v"(r[3]), [r4] "=&v"(r[4]),
+      [t0] "=&v"(t0), [t1] "=&v"(t1), [cnt] "=&s"(cnt)
+    : [addr] "v"(addr){addr2}, [nsteps] "s"(nsteps)
+    : {twin_ring_clobbers}, "scc", "memory");
+}}
+"""
+
+
+def render_roles() -> str:
+    """sha1_roles_asm.h, written beside sha1_asm.h."""
+    ring = ", ".join(f'"v{RING_BASE + i}"' for i in range(4 * RING_QUADS))
+    twin_ring = ", ".join(f'"v{RING_BASE + i}"' for i in range(4 * max(RING_QUADS, 2 * TWIN_SET_QUADS)))
+    addr2 = ', [addr2] "v"(addr + 65536u)' if LDS_BUFS * RING_BYTES > 65536 else ""
+    return ROLES_HEADER.format(roles_lds='    ".p2align 3\\n"\n' + emit(gen_roles(0), False),
+                               roles_rounds_loop=roles_rounds_loop_text(), ring_clobbers=ring,
+                               twin_ring_clobbers=twin_ring, addr2=addr2)
+
+
 def render() -> str:
     ring = ", ".join(f'"v{RING_BASE + i}"' for i in range(4 * RING_QUADS))
     hregs = list(range(HW_BASE, HW_BASE + 16)) + [HT, HT2] + list(range(HOUT_BASE, HOUT_BASE + 4 * HOUT_QUADS))
@@ -1322,15 +1657,18 @@ def render() -> str:
                              ring_clobbers=ring, twin_ring_clobbers=twin_ring, twin_helper_clobbers=h2, twin_loop_clobbers=h2loop, addr2=addr2))
 
 
-def _stamp_patch(txt: str) -> str:
+STAMP_FNS = (("tv_sha1_rounds_loop", "uint32_t nsteps,\n", '[cnt] "=&s"(cnt)\n'),
+             ("tv_sha1_helper_loop", "uint32_t nraw, uint32_t addr,\n", '[inc] "=&s"(inc)\n'),
+             ("tv_sha1_twin_rounds_loop", "uint32_t nsteps) {\n", '[cnt] "=&s"(cnt)\n'),
+             ("tv_sha1_twin_helper_loop", "uint32_t addr, uint32_t psel,\n", '[inc] "=&s"(inc)\n'))
+STAMP_ROLES_FNS = (("tv_sha1_roles_rounds_loop", "uint32_t nsteps) {\n", '[cnt] "=&s"(cnt)\n'),)
+
+
+def _stamp_patch(txt: str, fns=STAMP_FNS) -> str:
     """STAMP builds: give tv_sha1_rounds_loop and tv_sha1_helper_loop an accumulator argument `sbar` (cycles at
     the in-loop barriers) and the SGPRs the stamps use as clobbers."""
     assert not (PIPELINED or SPLIT_MID or SPLIT_PRE), "stamps are for the shipped per-block split rounds loop"
-    for fn, sig_old, out_old in (
-            ("tv_sha1_rounds_loop", "uint32_t nsteps,\n", '[cnt] "=&s"(cnt)\n'),
-            ("tv_sha1_helper_loop", "uint32_t nraw, uint32_t addr,\n", '[inc] "=&s"(inc)\n'),
-            ("tv_sha1_twin_rounds_loop", "uint32_t nsteps) {\n", '[cnt] "=&s"(cnt)\n'),
-            ("tv_sha1_twin_helper_loop", "uint32_t addr, uint32_t psel,\n", '[inc] "=&s"(inc)\n')):
+    for fn, sig_old, out_old in fns:
         extra = fn in ("tv_sha1_helper_loop", "tv_sha1_twin_helper_loop") and STAMP >= 2
         i = txt.index(f"void {fn}(")
         j = txt.index("\n}\n", i)
@@ -1363,6 +1701,9 @@ def main():
         txt = _stamp_patch(txt)
     with open(a.out, "w") as f:
         f.write(txt)
+    if not K_IN_ROUNDS:
+        with open(os.path.join(os.path.dirname(os.path.abspath(a.out)), "sha1_roles_asm.h"), "w") as f:
+            f.write(_stamp_patch(render_roles(), STAMP_ROLES_FNS) if STAMP else render_roles())
     print(f"wrote {a.out}: FULL {len(gen_full())} instr, LDS {len(gen_lds())} instr, "
           f"HELPER {len(gen_helper())} instr")
 

@@ -16,6 +16,10 @@ Variants (one lone wave per CU, NBLK blocks per loop, s_memtime cycles per block
   nolds     base without reads and waits (VALU floor); nolds_dpp: the same with DPP adds
   d10_*     10 reads at the block start, DPP adds; waits: w10 = one per read, w5 = one per 2 reads,
             w5n = w5 + s_nop 0 after each wait (realign), w5d = each wait doubled, w2 = waits at reads 0 and 5
+  trips     the two-block-trip loop body on two register sets with the five-instruction round both lanes ran
+            alike (405 VALU per block: gen_twin_trip_block)
+  roles     the same trips with the role-split rounds the generator ships (gen_roles_trip_block: 9 instructions
+            per two rounds through row_ror:8 and bank-masked DPP, 367 VALU per block)
 Build: python3 tools/gen_ubench_dpp.py && hipcc --offload-arch=gfx950 -O3 tools/ubench_dpp.hip -o tools/ubench_dpp
 """
 from __future__ import annotations
@@ -91,6 +95,38 @@ def d10(waits: str, pre: bool = False) -> list[str]:
     return out + tail() + ([] if pre else ["s_waitcnt lgkmcnt(0)"])
 
 
+TRIP_REG = {**{f"r{i}": f"v{40 + i}" for i in range(5)}, **{f"h{i}": f"v{50 + i}" for i in range(5)},
+            "t0": "v45", "t1": "v46", "addr": "v49"}
+
+
+def trip_phys(line: str) -> str:
+    return re.sub(r"%\[(\w+)\]", lambda m: TRIP_REG[m.group(1)], line)
+
+
+def trip_reads(s: int) -> list[str]:
+    return [trip_phys(l) for l in g._emit_lines([("ds_read_b128_abs", g.TWIN_SET_QUADS * s + q, q * g.TWIN_READ_BYTES)
+                                                 for q in range(g.TWIN_SET_QUADS)])]
+
+
+def trips_alike() -> list[str]:
+    """Two blocks of the rounds both lanes of a pair run alike (gen_twin_trip_block) with their feed-forward."""
+    out = []
+    for s in range(2):
+        out += [trip_phys(l) for l in g._emit_lines(g.gen_twin_trip_block(s, 0))]
+        out.append(trip_phys("v_add_u32_e64 %[h0], %[h0], %[r0]"))
+        out += [trip_phys(f"v_add_u32 %[h{i}], %[h{i}], %[r{i}]") for i in range(1, 5)] + ["s_barrier"]
+    return out
+
+
+def trips_roles() -> list[str]:
+    out = []
+    for s in range(2):
+        out += [trip_phys(l) for l in g._emit_lines(g.gen_roles_trip_block(s, 0))] + ["s_barrier"]
+    return out
+
+
+TRIPS = {"trips": trips_alike, "roles": trips_roles}   # loop bodies of two blocks, first 4-byte instruction at 4 mod 8
+
 VARIANTS = {
     "base": lambda: base(False), "dpp20": lambda: base(True),
     "nolds": lambda: base(False, lds=False), "nolds_dpp": lambda: base(True, lds=False),
@@ -98,18 +134,27 @@ VARIANTS = {
     "d10_w5d": lambda: d10("w5d"), "d10_w2": lambda: d10("w2"),
     "d10_w2n": lambda: d10("w2n"), "d10_w3n": lambda: d10("w3n"), "d10_w1n": lambda: d10("w1n"),
     "pre_w5n": lambda: d10("w5n", True), "pre_w2n": lambda: d10("w2n", True), "pre_w1n": lambda: d10("w1n", True),
-    "pre_w1": lambda: d10("w1", True),
+    "pre_w1": lambda: d10("w1", True), **TRIPS,
 }
 PRE = {n for n in VARIANTS if n.startswith("pre_")}
 
 
 def render() -> str:
-    clob = ", ".join(f'"v{r}"' for r in list(range(40, 56)) + list(range(60, 128)))
+    clob = ", ".join(f'"v{r}"' for r in list(range(40, 56)) + list(range(60, 144)))
     kern = []
     for name, fn in VARIANTS.items():
         body = "\n".join(f'        "{l}\\n"' for l in fn())
         prologue = "\n".join(f'        "ds_read_b128 v[{64 + 4 * k}:{67 + 4 * k}], v49 offset:{k * 1024}\\n"'
                              for k in range(10)) if name in PRE else ""
+        if name in TRIPS:   # as the shipped loop: head at 4 mod 64, s_sub borrows when no trip is left
+            prologue = "\n".join(f'        "{l}\\n"' for l in trip_reads(0))
+            head = '".p2align 6\\n s_nop 0\\n"'
+            loop_end = f'"s_sub_u32 s40, s40, 1\\n"\n        "s_cbranch_scc0 L_top_%=\\n"'
+            count = NBLK // 2 - 1
+        else:
+            head = '".p2align 6\\n"'
+            loop_end = '"s_sub_u32 s40, s40, 1\\n"\n        "s_cmp_lg_u32 s40, 0\\n"\n        "s_cbranch_scc1 L_top_%=\\n"'
+            count = NBLK
         kern.append(f"""
 __global__ __launch_bounds__(64) void k_{name}(uint64_t* cyc, uint32_t* sink, uint32_t seed) {{
     __shared__ uint32_t lds[20 * 256 + 64];
@@ -121,15 +166,14 @@ __global__ __launch_bounds__(64) void k_{name}(uint64_t* cyc, uint32_t* sink, ui
     asm volatile(
         "v_mov_b32 v49, %1\\n v_mov_b32 v40, %2\\n v_mov_b32 v41, %2\\n v_mov_b32 v42, %2\\n"
         "v_mov_b32 v43, %2\\n v_mov_b32 v44, %2\\n"
-        "s_mov_b32 s40, {NBLK}\\n"
+        "v_mov_b32 v50, %2\\n v_mov_b32 v51, %2\\n v_mov_b32 v52, %2\\n v_mov_b32 v53, %2\\n v_mov_b32 v54, %2\\n"
+        "s_mov_b32 s40, {count}\\n"
 {prologue}
         "s_branch L_top_%=\\n"
-        ".p2align 6\\n"
+        {head}
         "L_top_%=:\\n"
 {body}
-        "s_sub_u32 s40, s40, 1\\n"
-        "s_cmp_lg_u32 s40, 0\\n"
-        "s_cbranch_scc1 L_top_%=\\n"
+        {loop_end}
         "s_waitcnt lgkmcnt(0)\\n v_mov_b32 %0, v40\\n"
         : "=v"(o) : "v"(addr), "v"(a) : "s40", "scc", "memory", {clob});
     asm volatile("s_waitcnt lgkmcnt(0)\\n s_memtime %0\\n s_waitcnt lgkmcnt(0)" : "=s"(t1)::"memory");

@@ -17,14 +17,15 @@
 //           ~4.07 cycles (tools/ubench_fetch.hip), so with fewer pieces than SIMDs the per-lane
 //           instruction count IS the bound; this cuts the serial stream from 613 to 405 VALU per block.
 //           For 16,384 < pieces <= 32,768 per GPU.
-//   twin  : split with TWO lanes per piece: a lane pair runs the same rounds, each lane reads only the K+W
-//           quads of its parity (10 ds_read_b128 per block) and takes the other parity's word from its
-//           partner by DPP; a two-lane helper expands the schedule by parity.  For <= 16,384 pieces per GPU
-//           (every wave still has a SIMD to itself).
+//   twin  : split with TWO lanes per piece: of every two rounds one lane of the pair computes the first and the
+//           other the second, sharing F and `F + e + KW` and passing rotl5-and-add to each other by DPP (367
+//           VALU per block); each lane reads only the K+W quads of its parity (10 ds_read_b128 per block), and
+//           a two-lane helper expands the schedule by parity.  For <= 16,384 pieces per GPU (every wave still
+//           has a SIMD to itself).
 // What the kernels share is written once: resolve_group() turns a group of a launch into each lane's piece, block
 // range and bytes (resident, list and batch mode); helper_wave() / rounds_wave() are the two wave bodies of split and twin,
 // with the barrier protocol stated above them; finish() / finish_list() write the results.  The generated blocks
-// and loops are in sha1_asm.h (tools/gen_sha1_asm.py).
+// and loops are in sha1_asm.h and sha1_roles_asm.h (tools/gen_sha1_asm.py).
 //
 // HBM layout: resident piece j (shard-local) starts at payload + j*stride, stride = L + pad
 // (pad breaks the power-of-two stride that would put all 64 lanes of a wave on one channel).
@@ -34,6 +35,7 @@
 #include <type_traits>
 
 #include "sha1_asm.h"
+#include "sha1_roles_asm.h"
 #include "tv_block.h"
 #include "tv_internal.h"
 
@@ -171,7 +173,8 @@ __device__ __forceinline__ void compress_full(uint32_t h[5], uint32_t w[16]) {
 // chaining value for the next launch of a streamed run.  `writer`: this lane owns piece jj's outputs
 // (a main-group lane below n_main, or lane 0 of the short last piece's dedicated group).  Bitfield
 // words are OR-ed into the zeroed output (the last group may share a word with a main group).
-// j0 = the wave's first piece.  TWIN: lane 2i (and its partner 2i + 1) holds piece j0 + i, j0 a multiple of 32.
+// j0 = the wave's first piece.  TWIN: lane 16r + k, k < 8, (and its partner 8 lanes up) holds piece j0 + 8r + k,
+// j0 a multiple of 32.
 template <bool HASH, bool TWIN = false>
 __device__ __forceinline__ void finish(const TvPieces& p, bool writer, uint32_t jj, uint32_t j0,
                                        const uint32_t h[5], bool last_grp) {
@@ -194,11 +197,8 @@ __device__ __forceinline__ void finish(const TvPieces& p, bool writer, uint32_t 
     for (int k = 0; k < 5; k++) ok &= (h[k] == p.digests[(uint64_t)k * p.dcount + jj]);
     uint64_t mask = __ballot(ok);
     if ((threadIdx.x & 63) == 0) {
-        if (TWIN && !last_grp) {   // the even lanes' bits -> bits 0..31, then to the wave's half of its word
-            mask &= 0x5555555555555555ull;
-            mask = (mask | (mask >> 1)) & 0x3333333333333333ull;
-            mask = (mask | (mask >> 2)) & 0x0F0F0F0F0F0F0F0Full;
-            mask = (mask | (mask >> 4)) & 0x00FF00FF00FF00FFull;
+        if (TWIN && !last_grp) {   // the role-0 lanes' bytes -> bits 0..31, then to the wave's half of its word
+            mask &= 0x00FF00FF00FF00FFull;
             mask = (mask | (mask >> 8)) & 0x0000FFFF0000FFFFull;
             mask = (mask | (mask >> 16)) & 0x00000000FFFFFFFFull;
             mask <<= j0 & 63;
@@ -432,10 +432,10 @@ struct TwinOps {
     }
     template <typename... Stamp>
     __device__ __forceinline__ void rounds_loop(uint32_t h[5], uint32_t lds, uint32_t nsteps, Stamp&... st) const {
-        tv_sha1_twin_rounds_loop(h, lds, nsteps, st...);
+        tv_sha1_roles_rounds_loop(h, lds, nsteps, st...);
     }
     __device__ __forceinline__ void rounds_block(const uint32_t h[5], uint32_t r[5], uint32_t lds) const {
-        tv_sha1_twin_lds(h, r, lds);
+        tv_sha1_roles_lds(h, r, lds);
     }
 };
 
@@ -495,7 +495,7 @@ __device__ __forceinline__ void helper_wave(const TvPieces& p, const Ops& ops, c
 
 // Blocks [b0, min(end, nb_min)), where every lane of the wave updates: one asm loop (rounds, h += r, barrier).  The
 // rest only in a group with the short last piece: lanes past their final block keep their digest (both lanes of a
-// twin pair hold the same piece, so the DPP partner is always in step).
+// twin pair hold the same piece and every lane runs every block's rounds, so the DPP partner is always in step).
 template <typename Ops>
 __device__ __forceinline__ void rounds_wave(const TvPieces& p, const Ops& ops, const Group& q, uint32_t lds_lane,
                                             uint32_t wave, uint32_t h[5]) {
@@ -558,12 +558,15 @@ __global__ __launch_bounds__(128 * PAIRS) void tv_split_kernel(TvPieces p) {
 
 // ------------------------------------------------------------------------------------------
 // twin kernel: the split kernel with TWO lanes per piece in every wave.  A workgroup is rounds waves 0, 1
-// and helper waves 2, 3 over 64 pieces; in each wave lane 2i + b runs piece 32(wave & 1) + i and owns its
-// schedule words of parity b (tools/gen_sha1_asm.py gen_twin / gen_helper2).  Rounds: both lanes of a pair
-// run the same rounds; lane b reads only its own K+W words and each round's `e + KW` add takes KW from lane
-// t % 2 of the pair through DPP: 10 ds_read_b128 per block instead of 20.  The loop over the full blocks runs
-// two blocks per trip on two register sets for the K+W quads: serial stream 405 VALU + 10 LDS + 1 wait +
-// barrier per block and one s_sub + s_cbranch per two blocks.  Helper: 192 VALU + 10 ds_write_b128 per block
+// and helper waves 2, 3 over 64 pieces.  Helper: lane 2i + b runs piece 32(wave & 1) + i and owns its schedule
+// words of parity b (tools/gen_sha1_asm.py gen_helper2).  Rounds: lanes 16r + k and 16r + 8 + k (k < 8) are
+// roles 0 and 1 of piece 32(wave & 1) + 8r + k; of every two rounds role 0 computes the first and role 1 the
+// second, from one F and one `F + e + KW` for both, and the rotl5-and-add chain passes between them through DPP
+// (row_ror:8): 9 instructions per two rounds (gen_roles).  Role b reads only helper lane 2i + b's K+W words: 10
+// ds_read_b128 per block instead of 20.  The loop over the full blocks runs two blocks per trip on two register
+// sets for the K+W quads: serial stream 367 VALU + 10 LDS + 1 wait + barrier per block and one s_sub +
+// s_cbranch per two blocks.  Every lane of a rounds wave stays active through all of its blocks (lanes past
+// their piece's end run them too and discard the result).  Helper: 192 VALU + 10 ds_write_b128 per block
 // (W[32..79] from the parity-closed recurrence W[t] = rotl2(W[t-6] ^ W[t-16] ^ W[t-28] ^ W[t-32])), half a
 // split helper's stream.  K+W ring: 3 x 20 KiB, the helpers two blocks ahead, one workgroup barrier per block.
 // Four waves per 64 pieces fill the SIMDs up to 16,384 pieces (cfg2: 256 workgroups, one per CU).
@@ -595,15 +598,19 @@ __global__ __launch_bounds__(64 * kTwinWaves[SHAPE]) void tv_twin_kernel(TvPiece
     const uint32_t wgi = companion ? (blockIdx.x - real_wgs) % nmain_wgs : blockIdx.x;
     // a companion keeps the instruction stream of the workgroup it copies but, unless fill_all, points every
     // lane at that workgroup's first piece: the same loads, one piece's bytes instead of 32 pieces'
-    const Group q = resolve_group<MODE>(p, wgi, span, companion && !p.fill_all ? 0u : half * 32u + (lane >> 1));
-    const uint32_t lds_lane = (uint32_t)(uintptr_t)(void*)ring + half * 1024u + lane * 16u;
+    // the wave's piece of this lane, and the lane's half of it: helper lane 2i + b has parity b of piece i; rounds
+    // lane 16r + 8b + k (k < 8) is role b of piece 8r + k, and reads what helper lane 2i + b wrote
+    const uint32_t part = role == 0 ? (lane >> 3) & 1u : lane & 1u;
+    const uint32_t pc = role == 0 ? (lane >> 4) * 8u + (lane & 7u) : lane >> 1;
+    const Group q = resolve_group<MODE>(p, wgi, span, companion && !p.fill_all ? 0u : half * 32u + pc);
+    const uint32_t lds_lane = (uint32_t)(uintptr_t)(void*)ring + half * 1024u + (2u * pc + part) * 16u;
     ClockStamp clk;
     clk.start(p);
     if (role == 2) {
         idle_wave(q.g);
         return;
     }
-    const TwinOps ops{(lane & 1u) ? 0x07060504u : 0x03020100u};
+    const TwinOps ops{(lane & 1u) ? 0x07060504u : 0x03020100u};   // (read by helper lanes only)
     if (role == 1) {
         helper_wave(p, ops, q, lds_lane, wave);
         return;
@@ -613,9 +620,9 @@ __global__ __launch_bounds__(64 * kTwinWaves[SHAPE]) void tv_twin_kernel(TvPiece
     rounds_wave(p, ops, q, lds_lane, wave, h);
     clk.end(p);              // (wave 0 is a rounds wave in every shape)
     if (companion) return;   // its digests duplicate a main workgroup's: nothing to write
-    const bool even = (lane & 1u) == 0;   // one writer per lane pair
-    if (LISTED) finish_list(p, even && q.j < p.n, q.j, q.jj, h);
-    else finish<HASH, true>(p, q.last_grp ? (wave == 0 && lane == 0) : (even && q.j < p.n_main), q.jj,
+    const bool role0 = part == 0;   // one writer per lane pair
+    if (LISTED) finish_list(p, role0 && q.j < p.n, q.j, q.jj, h);
+    else finish<HASH, true>(p, q.last_grp ? (wave == 0 && lane == 0) : (role0 && q.j < p.n_main), q.jj,
                             q.g0 + half * 32u, h, q.last_grp);
 }
 
