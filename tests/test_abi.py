@@ -62,16 +62,21 @@ def test_asm_generator_emulator():
     assert r.returncode == 0 and "ok" in r.stdout, r.stderr
 
 
-@pytest.mark.parametrize("env", [{"TV_GEN_PAIRXOR": "0"}, {"TV_GEN_KROUNDS": "1"}, {"TV_GEN_HPAIR": "1"},
-                                 {"TV_GEN_PIPE": "1", "TV_GEN_RING": "20"}, {"TV_GEN_BUFS": "2"},
-                                 {"TV_GEN_TWIN_ISSUE": "end"}, {"TV_GEN_TWIN_ISSUE": "spread"},
-                                 {"TV_GEN_TWIN_PRE": "0"}, {"TV_GEN_TWIN_WAITS": "0-2-4-6-8", "TV_GEN_TWIN_ISSUE": "end"},
-                                 {"TV_GEN_SPLIT_MID": "1", "TV_GEN_RING": "20"}, {"TV_GEN_SPLIT_PRE": "1"}])
+@pytest.mark.parametrize("env", [{"TV_GEN_PAIRXOR": "0"}, {"TV_GEN_RING": "20"}, {"TV_GEN_HWAIT": "0"},
+                                 {"TV_GEN_TWIN_TRIP_AT": "59"}, {"TV_GEN_BUFS": "2"}, {"TV_GEN_LALIGN": "0"}])
 def test_asm_generator_emulator_options(env):
     """The generator's A/B options (tools/build_variants.py) still emit streams that compute SHA-1."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_sha1_asm.py"), "--check"],
                        capture_output=True, text=True, env=dict(os.environ, **env))
     assert r.returncode == 0 and "ok" in r.stdout, r.stderr
+
+
+def test_asm_generator_refuses_an_unknown_switch():
+    """A TV_GEN_* name the generator does not read (a typo, a retired option) is an error that names it, not a
+    default build."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_sha1_asm.py"), "--check"],
+                       capture_output=True, text=True, env=dict(os.environ, TV_GEN_FOO="1"))
+    assert r.returncode != 0 and "TV_GEN_FOO" in r.stderr and "ok" not in r.stdout, (r.stdout, r.stderr)
 
 
 @pytest.mark.parametrize("stamp", ["1", "2"])
@@ -89,7 +94,7 @@ def test_asm_generator_stamp_headers(tmp_path, stamp):
     assert "tv_sha1_rounds_loop(uint32_t h[5], uint32_t addr, uint32_t nsteps, uint32_t& sbar," in h
     assert ('uint32_t& sbar, uint32_t& svm, uint32_t& slg,' in h) == (stamp == "2")
     assert h.count('"s88", "s89", "s90", "s91"') == 4      # split and twin: rounds and helper loops
-    assert "tv_sha1_twin_rounds_loop(uint32_t h[5], uint32_t addr, uint32_t nsteps, uint32_t& sbar) {" in h
+    assert "tv_sha1_roles_rounds_loop(uint32_t h[5], uint32_t addr, uint32_t nsteps, uint32_t& sbar) {" in h
     assert ("%[svm]" in h) == (stamp == "2") and "%[sbar]" in h
     if stamp == "2":   # the drain stamp needs the drain: the twin helper's, and the split helper's only with the
         # pre-round-4 wait (TV_GEN_HWAIT=0)
@@ -109,7 +114,13 @@ def test_generated_header_is_current(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_sha1_asm.py"), "--out",
                         str(tmp_path / "h.h")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    assert (tmp_path / "h.h").read_text() == open(os.path.join(ROOT, "torrent_amd", "csrc", "sha1_asm.h")).read()
+    assert os.listdir(tmp_path) == ["h.h"]          # --out names the only file the generator writes
+    h = (tmp_path / "h.h").read_text()
+    assert h == open(os.path.join(ROOT, "torrent_amd", "csrc", "sha1_asm.h")).read()
+    assert not os.path.exists(os.path.join(ROOT, "torrent_amd", "csrc", "sha1_roles_asm.h"))
+    assert re.findall(r"^__device__ __forceinline__ void (\w+)\(", h, re.M) == [
+        "tv_sha1_full", "tv_sha1_lds", "tv_sha1_helper_loop", "tv_sha1_rounds_loop", "tv_sha1_schedule_lds",
+        "tv_sha1_roles_lds", "tv_sha1_roles_rounds_loop", "tv_sha1_twin_helper_loop", "tv_sha1_twin_schedule_lds"]
 
 
 def test_no_oracle_in_product_path():

@@ -7,7 +7,7 @@ generator paired the schedule's 4-byte xors and aligned the block.  These tests 
     8-byte offset from its start;
   * in the built library, the lane kernel's main loop has almost no misaligned 8-byte instructions, the
     split kernel's rounds loop no misaligned run longer than five (runs up to five are free), and the twin
-    kernel's rounds loop (five 8-byte instructions per round) none at all and no padding s_nop, its head at
+    kernel's rounds loop (nine 8-byte instructions per two rounds) none at all and no padding s_nop, its head at
     4 mod 64 and its helper loop's at 60 mod 64 (the 64-byte placement is worth ~1 % at cfg2).
 """
 import os
@@ -63,7 +63,7 @@ def test_built_hot_loops_alignment():
     assert rounds, rep["split"]
     for r in rounds:
         assert max(int(k) for k in r["runs"]) <= 5, r
-    # the twin rounds loop (3 blocks of 80 five-instruction rounds, all 8-byte): fully aligned, and no s_nop
+    # the twin rounds loop (6 blocks of 40 nine-instruction pairs of rounds, all 8-byte): fully aligned, and no s_nop
     twin = [r for r in rep["twin"] if r["instrs"] >= 1000 and r["eight_byte"] > 0.9 * r["instrs"]]
     assert twin, rep["twin"]
     for r in twin:

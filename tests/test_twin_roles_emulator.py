@@ -6,7 +6,8 @@ pair: DPP reads from the partner, role-masked writes, the LDS ring under the hel
 random chaining values: a message of a random prefix, 1 .. 7 blocks through the stream under test, and its padding;
 the prefix and the padding go through the plain compression below, and the digest must be hashlib's of the whole
 message.  Then the distance rule for DPP reads on every stream, a mis-ordered stream that must trip it, the loop
-text's block macro against the emulated block, and the committed headers against the generator.
+text's block macro against the emulated block, the split kernel's rounds loop under the same helper protocol with a
+stream that reads one barrier early and must trip it, and the committed header against the generator.
 """
 import hashlib
 import os
@@ -106,7 +107,7 @@ def test_loop_of_1_to_7_blocks(n):
         rng = random.Random(1000 * n + seed)
         nprefix = rng.randrange(0, 3)
         msg, h = _message(rng, nprefix, n, rng.randrange(0, 64))
-        h = g.check_twin_stream(_blocks(msg[64 * nprefix:64 * (nprefix + n)]), h, roles=True)
+        h = g.check_twin_stream(_blocks(msg[64 * nprefix:64 * (nprefix + n)]), h)
         assert _finish(h, msg, nprefix + n) == hashlib.sha1(msg).digest(), (n, seed)
     seen = {(s, buf) for m in range(1, 8) for s, buf, _ in g.twin_trips_walk(m)}
     assert seen == {(s, buf) for s in range(2) for buf in range(3)}
@@ -171,8 +172,65 @@ def test_a_misordered_stream_trips_the_distance_check():
         g.check_dpp_distance([("v_mov_b32_dpp", "h0", "h1", ("own", g.ROLE0))])
 
 
+@pytest.mark.parametrize("n", range(1, 8))
+def test_split_loop_of_1_to_7_blocks(n):
+    """The split kernel's rounds loop as shipped (one block per message block on buffers 0, 1, 2, 0, ...) under the
+    same helper protocol, with random chaining values."""
+    ins = g.split_rounds_stream(n)
+    assert ins == [op for k in range(n) for op in g.split_rounds_block(k)] + [("s_waitcnt_lgkm", 0)]
+    assert sum(op == ("s_barrier",) for op in ins) == n and sum(op[0] == "ds_read_b128" for op in ins) == 20 * n
+    for seed in range(3):
+        rng = random.Random(2000 * n + seed)
+        nprefix = rng.randrange(0, 3)
+        msg, h = _message(rng, nprefix, n, rng.randrange(0, 64))
+        h = g.check_split_stream(_blocks(msg[64 * nprefix:64 * (nprefix + n)]), h)
+        assert _finish(h, msg, nprefix + n) == hashlib.sha1(msg).digest(), (n, seed)
+
+
+def _split_stream_with_block_2_read_early(barrier: int, wait: bool):
+    """The three-block split stream with block 2's leading reads issued before the given barrier (0 or 1; its own
+    place is after barrier 1), into register quads past the ring, and its first 60 rounds taking their words from
+    there: nothing differs from the shipped stream but when those reads go out."""
+    good, block2 = g.split_rounds_stream(3), g.split_rounds_block(2)
+    start2 = len(good) - 1 - len(block2)
+    assert good[start2:-1] == block2 and all(op[0] == "ds_read_b128" for op in block2[:g.READ_AHEAD])
+    spare = 20
+    early = [("ds_read_b128_abs", spare + q, off) for _, q, off in block2[:g.READ_AHEAD]]
+    rest, t = [], 0
+    for op in block2[g.READ_AHEAD:]:
+        if op[0] == "v_add_u32" and op[1].startswith("r"):       # round t's `e + KW`
+            if t < 4 * g.READ_AHEAD:
+                assert op[2] == g.ring_reg(t // 4, t % 4)
+                op = (op[0], op[1], f"v{g.RING_BASE + 4 * (spare + t // 4) + t % 4}", op[3])
+            t += 1
+        rest.append(op)
+    assert t == 80
+    at = [i for i, op in enumerate(good) if op == ("s_barrier",)][barrier]
+    return good[:at] + early + ([("s_waitcnt_lgkm", 0)] if wait else []) + good[at:start2] + rest + good[-1:]
+
+
+def test_a_read_one_barrier_early_trips_the_protocol_model():
+    """Block k + 1 is in LDS before the barrier that starts block k, so a block may issue the next block's leading
+    reads before its own closing barrier.  One barrier earlier is too early: block k + 2 is written at the barrier
+    that ends block k at the latest, into the buffer handed back at the barrier before.  Such a stream trips the
+    model: the in-flight assert when the reads cross that barrier, a wrong digest when they were waited for."""
+    rng = random.Random(31)
+    msg, h = _message(rng, 1, 3, 17)
+    blocks, want = _blocks(msg[64:256]), hashlib.sha1(msg).digest()
+    for wait in (False, True):       # one barrier ahead of the shipped place: allowed
+        got = g.check_split_stream(blocks, h, _split_stream_with_block_2_read_early(1, wait))
+        assert _finish(got, msg, 4) == want
+    with pytest.raises(AssertionError, match="rewritten while a ds_read of it is in flight"):
+        g.check_split_stream(blocks, h, _split_stream_with_block_2_read_early(0, False))
+    got = g.check_split_stream(blocks, h, _split_stream_with_block_2_read_early(0, True))
+    assert _finish(got, msg, 4) != want
+
+
 def test_generated_headers_are_current():
     with open(os.path.join(ROOT, "torrent_amd", "csrc", "sha1_asm.h")) as f:
-        assert f.read() == g.render()
-    with open(os.path.join(ROOT, "torrent_amd", "csrc", "sha1_roles_asm.h")) as f:
-        assert f.read() == g.render_roles()
+        h = f.read()
+    assert h == g.render()
+    assert not os.path.exists(os.path.join(ROOT, "torrent_amd", "csrc", "sha1_roles_asm.h"))
+    assert re.findall(r"^__device__ __forceinline__ void (\w+)\(", h, re.M) == [
+        "tv_sha1_full", "tv_sha1_lds", "tv_sha1_helper_loop", "tv_sha1_rounds_loop", "tv_sha1_schedule_lds",
+        "tv_sha1_roles_lds", "tv_sha1_roles_rounds_loop", "tv_sha1_twin_helper_loop", "tv_sha1_twin_schedule_lds"]

@@ -1,8 +1,9 @@
 """Build A/B variants of libtorrent_verify.so from generator settings (tools/gen_sha1_asm.py TV_GEN_*).
 
     python tools/build_variants.py name:KEY=VAL,KEY=VAL [name2:...]
-e.g.  python tools/build_variants.py base:BUFS=2,PIPE=0,RING=16 pipe:BUFS=3,PIPE=1,RING=20
-A key D_<MACRO> is passed to hipcc as -D<MACRO>=VAL instead (e.g. lane3:D_TV_LANE_DEPTH=3).
+e.g.  python tools/build_variants.py at19:TWIN_TRIP_AT=19 at59:TWIN_TRIP_AT=59,TWIN_RALIGN=1
+A key D_<MACRO> is passed to hipcc as -D<MACRO>=VAL instead (e.g. lane3:D_TV_LANE_DEPTH=3).  A key the generator
+does not read fails the build.
 
 Each variant's header is generated into torrent_amd/csrc/sha1_asm.h, the library is linked to
 build/variants/libtv_<name>.so, and the shipped header is regenerated at the end.  Load a variant with

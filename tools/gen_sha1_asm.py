@@ -16,9 +16,9 @@ SHA1_FULL   one 64-byte block, message schedule computed in-asm (16-word rolling
 SHA1_LDS    the 80 rounds only (400 VALU); W[0..79] comes from LDS as 20 ds_read_b128
             (layout [t/4][lane][4 words], conflict-free), kept 15 quads ahead in an 80-VGPR
             ring of PHYSICAL registers (a 128-bit asm operand cannot be split in AMDGPU asm).
-            The split kernel's rounds loop is one pipelined stream over its blocks: the reads
-            run 15 quads ahead across block boundaries (gen_rounds_block; 3 LDS buffers, the
-            helper two blocks ahead), checked by check_rounds_stream against the helper's
+            The split kernel's rounds loop runs this block once per message block, its 15
+            leading reads as a burst at the block's start (split_rounds_block; 3 LDS buffers,
+            the helper two blocks ahead), checked by check_split_stream against the helper's
             protocol.
 
 Round (roles rotate statically; the new `a` is written into the old `e` register):
@@ -49,23 +49,22 @@ M32 = 0xFFFFFFFF
 # 1,794 cycles against 1,894 with 7 in flight (tools/gen_ubench_rounds.py, profiles/r01/ubench_rounds.log).
 RING_BASE = 64
 # (the TV_GEN_* environment variables select build variants for A/B measurements; the defaults are
-# the shipped configuration)
+# the shipped configuration).  A TV_GEN_* name that is not one of these is an error, not a default build
+# labelled as a variant.
+SWITCHES = ("RING", "RA", "WAIT", "BUFS", "PAIRXOR", "ALIGN", "LALIGN", "HWAIT", "STAMP", "TWIN_RALIGN", "TWIN_HALIGN",
+            "SPLIT_RALIGN", "SPLIT_HALIGN", "TWIN_TRIP_AT")
+_unknown = sorted(k for k in os.environ if k.startswith("TV_GEN_") and k[len("TV_GEN_"):] not in SWITCHES)
+if _unknown:
+    raise ValueError("unknown generator switch in the environment: " + ", ".join(_unknown))
 RING_QUADS = int(os.environ.get("TV_GEN_RING", "16"))   # register quads of the K+W ring
 READ_AHEAD = int(os.environ.get("TV_GEN_RA", "15"))   # quads in flight ahead of the one being consumed
 WAIT_EVERY = int(os.environ.get("TV_GEN_WAIT", "4"))    # one s_waitcnt per WAIT_EVERY quads
 LDS_BUFS = int(os.environ.get("TV_GEN_BUFS", "3"))      # K+W buffers per pair; the helper runs LDS_BUFS-1 blocks ahead
-# PIPELINED = 1: the rounds reads run 15 quads ahead ACROSS block boundaries (gen_rounds_block).  Measured
-# 4 % slower than a burst of 15 reads at each block's start (13.69 vs 12.95 ms at cfg2,
-# profiles/r02/split_variants.jsonl): LDS data returning under the VALU stream costs more issue cycles
-# than a burst landing while the wave waits.  Kept as a checked option; the shipped build is 0.
-PIPELINED = os.environ.get("TV_GEN_PIPE", "0") == "1"
+# (The split rounds stream with its reads 15 quads ahead ACROSS block boundaries, or issued mid-block or after
+# round 79, K added by the rounds wave, and the helper's schedule in pairs were measured slower or no faster
+# and are no longer generated: profiles/design_history_r01-r05.md section 4.)
 PAIR_XOR = os.environ.get("TV_GEN_PAIRXOR", "1") == "1"   # lane compression: schedule words two at a time
 ALIGN_FULL = os.environ.get("TV_GEN_ALIGN", "1") == "1"   # lane compression block starts 8-byte aligned
-HELPER_PAIR = os.environ.get("TV_GEN_HPAIR", "0") == "1"  # split helper: schedule in pairs (4-byte ops paired)
-K_IN_ROUNDS = os.environ.get("TV_GEN_KROUNDS", "0") == "1"  # split: the rounds wave adds K (v_add3 with an SGPR)
-HELPER_X = os.environ.get("TV_GEN_HX", "")   # timing probes only: novalu / nowrite / noload (digests are wrong)
-ROUNDS_X = os.environ.get("TV_GEN_RX", "")   # timing probe only: nowait = the split rounds loop without its LDS-return
-                                             # waits (digests are wrong; barriers unchanged)
 # Diagnostic builds only (tools/split_stamps.py): STAMP = 1 brackets the split kernel's in-loop barriers (rounds and
 # helper waves) with shader-clock reads into SGPRs s[88:91] and accumulates the cycles spent at them in an SGPR
 # operand; the kernels then need -DTV_STAMPS=1.  The default header is unchanged.
@@ -87,11 +86,10 @@ STAMP_SEQ = _stamped("s_barrier", "sbar")
 HELPER_WAIT = os.environ.get("TV_GEN_HWAIT", "mid")
 LOOP_ALIGN = os.environ.get("TV_GEN_LALIGN", "1") == "1"  # split loops: .p2align 3 before every block body
 HELPER_AHEAD = LDS_BUFS - 1
-assert not PIPELINED or (LDS_BUFS >= 3 and RING_QUADS == 20), "the pipelined stream needs 3 buffers and a 20-quad ring"
 # physical VGPRs of the helper (schedule) block: 16-word W window, xor3 temp, 3 output quads
 HW_BASE = 80
 HT = 96
-HT2 = 97   # second schedule temp (HELPER_PAIR)
+HT2 = 97   # (no instruction uses it; it stays in the clobber lists, which the register allocation depends on)
 HOUT_BASE = 100
 HOUT_QUADS = 3
 
@@ -202,10 +200,7 @@ def gen_lds(off_base: int = 0, lead_wait: bool = True):
             ins.append(("s_waitcnt_lgkm", min(15, max(0, issued - need))))   # (lgkmcnt is 4 bits)
         A, B, C, D, E = roles(t)
         e_src = R.rd(E)
-        if K_IN_ROUNDS:
-            ins.append(("v_add3_u32", R.wr(E), e_src, f"k{t // 20}", ring_reg(g, t % 4)))
-        else:
-            ins.append(("v_add_u32", R.wr(E), ring_reg(g, t % 4), e_src))
+        ins.append(("v_add_u32", R.wr(E), ring_reg(g, t % 4), e_src))
         if t % 4 == 3 and g + READ_AHEAD < 20:
             ins.append(("ds_read_b128", g + READ_AHEAD, off_base + (g + READ_AHEAD) * 1024))
             issued = g + READ_AHEAD
@@ -218,128 +213,13 @@ def gen_lds(off_base: int = 0, lead_wait: bool = True):
     return ins
 
 
-def gen_rounds_block(off_cur: int, off_next: int):
-    """One block of the split kernel's PIPELINED rounds stream.  On entry quads 0..14 of this block are in
-    flight (issued by the previous block, or the loop prologue); after consuming quad g the read of quad
-    g + 15 is issued -- past quad 19 that is quad g - 5 of the NEXT block, from its buffer at off_next -- so
-    READ_AHEAD quads stay in flight across block boundaries and no block starts on an LDS latency bubble.
-    Then h += r and the workgroup barrier.  Needs the helper two blocks ahead (LDS_BUFS = 3): the next
-    block was written before the barrier that started this one."""
-    ins = []
-    R = Regs()
-    allowed = READ_AHEAD - WAIT_EVERY   # reads still in flight once quads g .. g+WAIT_EVERY-1 retired
-    for t in range(80):
-        g = t // 4
-        if t % 4 == 0 and g % WAIT_EVERY == 0:
-            ins.append(("s_waitcnt_lgkm", allowed))
-        A, B, C, D, E = roles(t)
-        e_src = R.rd(E)
-        if K_IN_ROUNDS:
-            ins.append(("v_add3_u32", R.wr(E), e_src, f"k{t // 20}", ring_reg(g, t % 4)))
-        else:
-            ins.append(("v_add_u32", R.wr(E), ring_reg(g, t % 4), e_src))
-        if t % 4 == 3:
-            q = g + READ_AHEAD
-            ins.append(("ds_read_b128", q % 20, off_cur + q * 1024 if q < 20 else off_next + (q - 20) * 1024))
-        ins.append(("v_alignbit_b32", "t0", R.rd(A), R.rd(A), 27))
-        ins.append(_fop(t, "t1", R.rd(B), R.rd(C), R.rd(D)))
-        b_src = R.rd(B)
-        ins.append(("v_alignbit_b32", R.wr(B), b_src, b_src, 2))
-        ins.append(("v_add3_u32", R.rd(E), R.rd(E), "t0", "t1"))
-    assert R.cur == [f"r{i}" for i in range(5)]
-    for i in range(5):
-        ins.append(("v_add_u32", f"h{i}", f"h{i}", f"r{i}"))
-    ins.append(("s_barrier",))
-    return ins
-
-
-SPLIT_MID = os.environ.get("TV_GEN_SPLIT_MID", "0") == "1"   # split rounds loop: next block's reads mid-block
-SPLIT_PRE = os.environ.get("TV_GEN_SPLIT_PRE", "0") == "1"   # split rounds loop: next block's 15 reads after round 79
-
-
-def gen_split_pre_block(off_cur: int, off_next: int):
-    """One block of the split rounds wave whose first READ_AHEAD reads were issued by the previous block: the
-    shipped per-block stream (gen_lds) without its leading reads, followed after round 79 by the next block's
-    leading reads (so they land during h += r and the barrier instead of after it), then h += r and the
-    barrier.  Safe for the same reason as the twin kernel's: the next block was written before the barrier
-    that started this one, and its buffer is not rewritten before the barrier that ends it."""
-    body = gen_lds(off_cur, lead_wait=False)
-    lead = [op for op in body[:READ_AHEAD] if op[0] == "ds_read_b128"]
-    assert len(lead) == READ_AHEAD
-    ins = body[READ_AHEAD:]
-    ins += [("ds_read_b128", q, off_next + q * 1024) for q in range(READ_AHEAD)]
-    for i in range(5):
-        ins.append(("v_add_u32", f"h{i}", f"h{i}", f"r{i}"))
-    ins.append(("s_barrier",))
-    return ins
-
-
-def gen_split_mid_block(off_cur: int, off_next: int):
-    """One block of the split rounds wave with the NEXT block's first 10 K+W quads issued inside this block (the
-    mid-block issue the twin kernel's one-block loop had): on entry quads 0-9 of this block are in
-    flight; it issues quads 10-14 at its start, quad 15+g after consuming quad g (g < 5), the next block's quads
-    0-4 after round 39 and 5-9 after round 59 (each batch behind a wait that keeps at most 15 reads in flight,
-    lgkmcnt's 4-bit limit), then h += r and the barrier.  Ring of 20 register quads, slot = quad.  The helper's
-    protocol makes it safe: the next block was written before the barrier that started this one."""
-    assert RING_QUADS == 20
-    ins, order = [], [("cur", q) for q in range(10)]   # reads in flight on entry, oldest first
-    retired = 0                                         # reads of `order` known retired
-
-    def wait_for(key):
-        nonlocal retired
-        i = order.index(key)
-        if i >= retired:
-            ins.append(("s_waitcnt_lgkm", min(15, len(order) - 1 - i)))
-            retired = i + 1
-
-    def issue(tag, q):
-        assert len(order) - retired < 15 or True
-        ins.append(("ds_read_b128", q, (off_cur if tag == "cur" else off_next) + q * 1024))
-        order.append((tag, q))
-
-    for q in range(10, 15):
-        issue("cur", q)
-    R = Regs()
-    for t in range(80):
-        g = t // 4
-        if t % 4 == 0:
-            wait_for(("cur", g))
-        A, B, C, D, E = roles(t)
-        e_src = R.rd(E)
-        ins.append(("v_add_u32", R.wr(E), ring_reg(g, t % 4), e_src))
-        ins.append(("v_alignbit_b32", "t0", R.rd(A), R.rd(A), 27))
-        ins.append(_fop(t, "t1", R.rd(B), R.rd(C), R.rd(D)))
-        b_src = R.rd(B)
-        ins.append(("v_alignbit_b32", R.wr(B), b_src, b_src, 2))
-        ins.append(("v_add3_u32", R.rd(E), R.rd(E), "t0", "t1"))
-        if t % 4 == 3 and g < 5:
-            issue("cur", 15 + g)
-        if t == 39:
-            wait_for(("cur", 14))
-            for q in range(5):
-                issue("next", q)
-        if t == 59:
-            wait_for(("cur", 19))
-            for q in range(5, 10):
-                issue("next", q)
-    assert R.cur == [f"r{i}" for i in range(5)]
-    # at most 15 in flight at every issue, counting every read not yet waited for as in flight
-    inflight, waited = 0, 0
-    for op in ins:
-        if op[0] == "ds_read_b128":
-            inflight += 1
-            assert inflight <= 15, "more than 15 LDS reads in flight"
-        elif op[0] == "s_waitcnt_lgkm":
-            inflight = min(inflight, op[1])
-    for i in range(5):
-        ins.append(("v_add_u32", f"h{i}", f"h{i}", f"r{i}"))
-    ins.append(("s_barrier",))
-    return ins
-
-
-def rounds_prologue(off: int = 0):
-    """Issue quads 0 .. READ_AHEAD-1 of the first block (buffer at off)."""
-    return [("ds_read_b128", g, off + g * 1024) for g in range(READ_AHEAD)]
+def split_rounds_block(k: int):
+    """Block k of the split kernel's rounds loop, as rounds_loop_text writes it and check_split_stream runs it:
+    the 80 rounds on ring buffer k % LDS_BUFS with their own reads, 15 as a burst at the start (a burst landing
+    while the wave waits costs fewer issue cycles than LDS data returning under the VALU stream), every read
+    waited for inside the block; then h += r and the workgroup barrier."""
+    return (gen_lds(k % LDS_BUFS * RING_BYTES, lead_wait=False)
+            + [("v_add_u32", f"h{i}", f"h{i}", f"r{i}") for i in range(5)] + [("s_barrier",)])
 
 
 def hw(t: int) -> str:
@@ -350,64 +230,47 @@ def gen_helper(src=None, off_base: int = 0):
     """Helper (schedule) block: src = 16 registers holding the block's words as loaded
     (little-endian; default operands raw0-15), sel (sgpr 0x00010203), addr (vgpr, LDS byte address
     of this lane in ring buffer 0), k0-3 (sgpr).  Writes K+W[t] for t = 0..79 to LDS at
-    addr + off_base + (t/4)*1024 as [t/4][lane][4] (one ds_write_b128 per quad).
-    With HELPER_PAIR the schedule of a quad runs as two pairs (W[t], W[t+1]), each bitop3, bitop3, xor,
-    xor, alignbit, alignbit, so the 4-byte instructions (the xors and the four K adds) come in pairs and
-    the 8-byte ones keep their alignment."""
+    addr + off_base + (t/4)*1024 as [t/4][lane][4] (one ds_write_b128 per quad)."""
     if src is None:
         src = [f"raw{i}" for i in range(16)]
     ins = []
     for i in range(16):
         ins.append(("v_perm_b32", hw(i), 0, src[i], "sel"))
     for q in range(20):
-        if q >= 4 and HELPER_PAIR:
-            for p in range(2):
-                ts = (4 * q + 2 * p, 4 * q + 2 * p + 1)
-                tmp = (f"v{HT}", f"v{HT2}")
-                for i, t in enumerate(ts):
-                    ins.append(("v_bitop3_b32", tmp[i], hw(t - 3), hw(t - 8), hw(t - 14), 0x96))
-                for i, t in enumerate(ts):
-                    ins.append(("v_xor_b32", hw(t), tmp[i], hw(t)))
-                for t in ts:
-                    ins.append(("v_alignbit_b32", hw(t), hw(t), hw(t), 31))
-        elif q >= 4:
+        if q >= 4:
             for i in range(4):
                 t = 4 * q + i
                 ins.append(("v_bitop3_b32", f"v{HT}", hw(t - 3), hw(t - 8), hw(t - 14), 0x96))
                 ins.append(("v_xor_b32", hw(t), f"v{HT}", hw(t)))
                 ins.append(("v_alignbit_b32", hw(t), hw(t), hw(t), 31))
-        qoff = off_base + q * 1024
-        if K_IN_ROUNDS:     # the rounds wave adds K: W[4q..4q+3] go to LDS straight from the window
-            ins.append(("ds_write_b128", HW_BASE + ((4 * q) & 15), qoff))
-            continue
         o = HOUT_BASE + 4 * (q % HOUT_QUADS)
         for j in range(4):
             ins.append(("v_add_u32", f"v{o + j}", f"k{q // 5}", hw(4 * q + j)))
-        ins.append(("ds_write_b128", o, qoff))
+        ins.append(("ds_write_b128", o, off_base + q * 1024))
     return ins
 
 
 # ---- TWIN: two lanes per piece, in the rounds waves AND the helper waves ----
-# A twin workgroup is 2 rounds waves + 2 helper waves over 64 pieces; in every wave lane 2i+b runs piece
-# 32w+i and owns the schedule words of PARITY b.  Rounds: both lanes of a pair run the same 80 rounds on the
-# same state; lane b reads only its own K+W words (10 ds_read_b128 per block instead of 20) and round t's
-# `e + KW` add takes KW from lane t%2 of the pair through DPP (quad_perm [b,b,2+b,2+b]).  Helper: both lanes
-# expand W[16..31] with the standard recurrence, then keep their own parity (v_perm with a per-lane selector)
-# and expand W[32..79] with W[t] = rotl2(W[t-6] ^ W[t-16] ^ W[t-28] ^ W[t-32]), whose terms all have t's
-# parity: 192 VALU + 10 ds_write_b128 per block and lane instead of 308 + 20 (gen_helper2).  Every round is
-# five 8-byte instructions, so in the single block (gen_twin, the padded tail blocks) each 4-byte s_waitcnt is
-# followed by `s_nop 0` to keep the stream 8-byte aligned (a long misaligned run issues at ~5.07 instead of
-# 4.07 cycles), with two waits: before round 0 (reads 0-4) and round 40 (reads 5-9); the loop over the full
-# blocks (gen_twin_trip_block) pairs its 4-byte instructions instead and has no s_nop.
-# The twin kernel's rounds waves now run the role-split rounds further down (gen_roles, gen_roles_trip_block:
-# sha1_roles_asm.h) on the same helper, layout and loop shape; the rounds described here, which both lanes of a
-# pair run alike, stay generated as the stream those are measured against (tools/gen_ubench_dpp.py `trips`).
-# Buffer layout [k][wave][lane][4 words]: lane 2i+b of wave w
-# holds W[8k+b], W[8k+b+2], W[8k+b+4], W[8k+b+6] (+K) of piece 32w+i at k*2048 + w*1024 + lane*16, written
-# and read as one contiguous KiB per wave (tools/gen_ubench_dpp.py, profiles/r02/ubench_dpp.log: the rounds
-# stream alone 1,723-1,758 vs 1,818 cycles per block for the shipped 20-read stream).
+# A twin workgroup is 2 rounds waves + 2 helper waves over 64 pieces.
+# Helper (gen_helper2): lane 2i+b of helper wave w runs piece 32w+i and owns the schedule words of PARITY b.
+# Both lanes expand W[16..31] with the standard recurrence, then keep their own parity (v_perm with a per-lane
+# selector) and expand W[32..79] with W[t] = rotl2(W[t-6] ^ W[t-16] ^ W[t-28] ^ W[t-32]), whose terms all have
+# t's parity: 192 VALU + 10 ds_write_b128 per block and lane instead of the split helper's 308 + 20.
+# Buffer layout [k][wave][lane][4 words]: helper lane 2i+b of wave w holds W[8k+b], W[8k+b+2], W[8k+b+4],
+# W[8k+b+6] (+K) of piece 32w+i at k*2048 + w*1024 + lane*16, written and read as one contiguous KiB per wave,
+# so a rounds lane issues 10 ds_read_b128 per block where the split kernel's issues 20 (tools/gen_ubench_dpp.py,
+# profiles/r02/ubench_dpp.log).
+# Rounds: the two lanes of a piece divide every pair of rounds between them as ROLES (gen_roles,
+# gen_roles_trip_block, further down); role b reads the words helper lane 2i+b wrote.  The loop over the full
+# blocks runs in two-block trips on two register sets (next section), its 4-byte instructions in adjacent pairs
+# and no s_nop.  The single block (gen_roles: the padded tail blocks) issues its own ten reads and has two
+# waits, each followed by `s_nop 0`, so that its 8-byte instructions stay 8-byte aligned (a long misaligned
+# run issues at ~5.07 instead of 4.07 cycles).
+# The rounds the roles replaced -- both lanes of a pair running the same five 8-byte instructions per round,
+# 405 VALU per block, lane t%2's K+W word through DPP quad_perm -- are no longer generated here;
+# tools/gen_ubench_dpp.py writes them itself for `trips`, the comparator the roles were measured against
+# (profiles/twin_roles/ubench_roles.log).
 TWIN_READ_BYTES = 2048
-TWIN_WAITS = tuple(int(x) for x in os.environ.get("TV_GEN_TWIN_WAITS", "0-5").split("-"))   # reads waited for, in pairs
 # 64-byte placement of the twin loops: rounds loop head at (4 + 8 k) mod 64 for TV_GEN_TWIN_RALIGN = k, helper
 # loop head at 4 m mod 64 for TV_GEN_TWIN_HALIGN = m ("none": wherever the code before them puts them).  The
 # rounds loop at 4 mod 64 (and the helper's at 60) is 0.7-1.6 % faster at cfg2 than at 28, 52 or 60
@@ -424,29 +287,6 @@ TWIN_HALIGN = None if TWIN_HALIGN == "none" else TWIN_HALIGN
 SPLIT_RALIGN = os.environ.get("TV_GEN_SPLIT_RALIGN", "6")
 SPLIT_HALIGN = os.environ.get("TV_GEN_SPLIT_HALIGN")
 SPLIT_RALIGN = None if SPLIT_RALIGN == "none" else SPLIT_RALIGN
-
-
-def gen_twin(off_base: int = 0):
-    """One TWIN rounds block with its own 10 reads issued first (tv_sha1_twin_lds: the padded tail blocks).
-    Operands as gen_lds: r0-4 (out), t0-1 (tmp), h0-4 (in), addr (this lane's LDS byte address)."""
-    ins = [("ds_read_b128", k, off_base + k * TWIN_READ_BYTES) for k in range(10)]
-    R = Regs()
-    for t in range(80):
-        k, b = t // 8, t % 2
-        if t % 8 == 0 and k in TWIN_WAITS:
-            nxt = [x for x in TWIN_WAITS if x > k]
-            ins.append(("s_waitcnt_lgkm", 10 - nxt[0] if nxt else 0))   # reads k .. (next wait - 1) retired
-            ins.append(("s_nop",))
-        A, B, C, D, E = roles(t)
-        e_src = R.rd(E)
-        ins.append(("v_add_u32_dpp", R.wr(E), ring_reg(k, (t % 8) // 2), e_src, b))
-        ins.append(("v_alignbit_b32", "t0", R.rd(A), R.rd(A), 27))
-        ins.append(_fop(t, "t1", R.rd(B), R.rd(C), R.rd(D)))
-        b_src = R.rd(B)
-        ins.append(("v_alignbit_b32", R.wr(B), b_src, b_src, 2))
-        ins.append(("v_add3_u32", R.rd(E), R.rd(E), "t0", "t1"))
-    assert R.cur == [f"r{i}" for i in range(5)]
-    return ins
 
 
 # ---- TWIN rounds loop: two-block trips ----
@@ -469,30 +309,6 @@ TWIN_SET_QUADS = 10
 
 def twin_set_reg(s: int, k: int, j: int) -> str:
     return f"v{RING_BASE + 4 * (TWIN_SET_QUADS * s + k) + j}"
-
-
-def gen_twin_trip_block(s: int, off_next: int):
-    """One block of the two-block-trip TWIN rounds loop on register set s.  On entry this block's ten reads
-    (issued by the previous block, or the prologue) are the only LDS operations in flight; its single wait
-    retires them.  After round TWIN_TRIP_AT it issues the ten reads of the next block (buffer at off_next)
-    into the other set, whose last use was the previous block's round 79."""
-    ins = [("s_waitcnt_lgkm", 0)]
-    R = Regs()
-    for t in range(80):
-        k, b = t // 8, t % 2
-        A, B, C, D, E = roles(t)
-        e_src = R.rd(E)
-        ins.append(("v_add_u32_dpp", R.wr(E), twin_set_reg(s, k, (t % 8) // 2), e_src, b))
-        ins.append(("v_alignbit_b32", "t0", R.rd(A), R.rd(A), 27))
-        ins.append(_fop(t, "t1", R.rd(B), R.rd(C), R.rd(D)))
-        b_src = R.rd(B)
-        ins.append(("v_alignbit_b32", R.wr(B), b_src, b_src, 2))
-        ins.append(("v_add3_u32", R.rd(E), R.rd(E), "t0", "t1"))
-        if t == TWIN_TRIP_AT:
-            ins += [("ds_read_b128_abs", TWIN_SET_QUADS * (1 - s) + q, off_next + q * TWIN_READ_BYTES)
-                    for q in range(TWIN_SET_QUADS)]
-    assert R.cur == [f"r{i}" for i in range(5)]
-    return ins
 
 
 def twin_trips_plan():
@@ -527,55 +343,6 @@ def twin_trips_walk(nsteps: int):
             return out
         cnt -= 1
         pair = (pair + 1) % LDS_BUFS
-
-
-def twin_rounds_loop_text() -> str:
-    """The TWIN rounds wave over nsteps (>= 1) blocks from ring buffer 0 in two-block trips (twin_trips_plan).
-    LDS ordering, with the helper two blocks ahead: block j + 1 was written before the barrier that started
-    block j, so block j may read it at any round; and the lgkmcnt(0) that starts block j + 1 retires those
-    reads of buffer (j + 1) % 3 before the barrier that ends block j + 1, after which the helper may rewrite
-    that buffer.  No read is in flight across more than one barrier.  The reads the final block issues (of the
-    helper's spare block) are drained at L_rdone."""
-    plan = twin_trips_plan()
-
-    def prologue(s):
-        return _emit_lines([("ds_read_b128_abs", TWIN_SET_QUADS * s + q, q * TWIN_READ_BYTES)
-                            for q in range(TWIN_SET_QUADS)])
-
-    def block(s, nxt):
-        # 4-byte instructions only in even groups: [wait] of a block pairs with the 4-byte tail of the block
-        # before it (four e32 h adds, barrier, and after a pair s_sub + s_cbranch), so every 8-byte
-        # instruction sits at 0 mod 8 and the loop needs no s_nop
-        body = _emit_lines(gen_twin_trip_block(s, nxt * RING_BYTES))
-        body.append("v_add_u32_e64 %[h0], %[h0], %[r0]")
-        body.extend(f"v_add_u32 %[h{i}], %[h{i}], %[r{i}]" for i in range(1, 5))
-        return body + (STAMP_SEQ if STAMP else ["s_barrier"])
-
-    L = ["s_waitcnt lgkmcnt(0)", "s_lshr_b32 %[cnt], %[nsteps], 1", "s_bitcmp1_b32 %[nsteps], 0",
-         "s_cbranch_scc1 L_rodd_%="]
-    L += prologue(0) + ["s_sub_u32 %[cnt], %[cnt], 1", "s_branch L_rloop_%="]
-    # odd block count: one single-block trip on set 1, then into the loop at the pair starting on buffer 1
-    s, _, nxt = plan["pre"]
-    L += ["L_rodd_%=:"] + prologue(s) + [".p2align 3", "s_nop 0"] + block(s, nxt)
-    L += ["s_sub_u32 %[cnt], %[cnt], 1", "s_cbranch_scc1 L_rdone_%=", f"s_branch L_rpair{plan['odd_entry']}_%="]
-    if TWIN_RALIGN is not None:
-        L += [".p2align 6"] + ["s_nop 0"] * (1 + 2 * int(TWIN_RALIGN))
-    else:
-        L += [".p2align 3", "s_nop 0"]
-    L.append("L_rloop_%=:")
-    for p in range(LDS_BUFS):
-        if p:
-            L.append(f"L_rpair{p}_%=:")
-        for s, _, nxt in plan["loop"][2 * p:2 * p + 2]:
-            L += block(s, nxt)
-        L += ["s_sub_u32 %[cnt], %[cnt], 1",
-              "s_cbranch_scc1 L_rdone_%=" if p < LDS_BUFS - 1 else "s_cbranch_scc0 L_rloop_%="]
-    L += ["L_rdone_%=:", "s_waitcnt lgkmcnt(0)"]
-    if TWIN_RALIGN is not None:
-        # the statement ends at 8 mod 64, where the one-block loop (3 blocks, head at 4 mod 64) ended: the
-        # code that follows (the loop over the padded tail blocks) keeps its 64-byte placement
-        L += [".p2align 6", "s_nop 0", "s_nop 0"]
-    return "\n".join(f'    "{l}\\n"' for l in L)
 
 
 # ---- TWIN: role-split rounds, 4.5 instructions per round ----
@@ -659,7 +426,7 @@ def _role_pairs(ins, chain, kw, reads_after=None):
 
 
 def gen_roles(off_base: int = 0):
-    """One role-split TWIN rounds block with its own 10 reads issued first (tv_sha1_twin_lds: the padded tail
+    """One role-split TWIN rounds block with its own 10 reads issued first (tv_sha1_roles_lds: the padded tail
     blocks).  Operands as gen_lds: r0-4 (out), t0-1 (tmp), h0-4 (in, the plain chaining value in both lanes), addr
     (this lane's LDS byte address).  r = the plain state after round 79 in both lanes.  Two waits, before pair 0
     (reads 0-4) and pair 20 (reads 5-9), each with an s_nop that keeps the 8-byte instructions aligned."""
@@ -774,10 +541,14 @@ def expand_roles_block(body, kw: int, rd: int, off: int):
 
 
 def roles_rounds_loop_text() -> str:
-    """The role-split TWIN rounds wave over nsteps (>= 1) blocks from ring buffer 0 in two-block trips: the control
-    flow, LDS ordering and 64-byte placement of twin_rounds_loop_text, with gen_roles_trip_block as the block
-    (written once, as a macro, and checked here to expand to every block's own lines) between the entry and exit
-    conversions of the chaining value."""
+    """The TWIN rounds wave over nsteps (>= 1) blocks from ring buffer 0 in two-block trips (twin_trips_plan), with
+    gen_roles_trip_block as the block (written once, as a macro, and checked here to expand to every block's own
+    lines) between the entry and exit conversions of the chaining value.
+    LDS ordering, with the helper two blocks ahead: block j + 1 was written before the barrier that started
+    block j, so block j may read it at any round; and the lgkmcnt(0) that starts block j + 1 retires those
+    reads of buffer (j + 1) % 3 before the barrier that ends block j + 1, after which the helper may rewrite
+    that buffer.  No read is in flight across more than one barrier.  The reads the final block issues (of the
+    helper's spare block) are drained at L_rdone."""
     plan = twin_trips_plan()
     body = roles_block_macro()
     assert all("\\" not in l for l in _roles_block_lines(0, 1))
@@ -814,47 +585,29 @@ def roles_rounds_loop_text() -> str:
               "s_cbranch_scc1 L_rdone_%=" if p < LDS_BUFS - 1 else "s_cbranch_scc0 L_rloop_%="]
     L += ["L_rdone_%=:"] + _emit_lines(roles_loop_exit())
     if TWIN_RALIGN is not None:
-        L += [".p2align 6", "s_nop 0", "s_nop 0"]   # (the statement ends at 8 mod 64, as twin_rounds_loop_text's)
+        # the statement ends at 8 mod 64 whatever its length: the code that follows (the loop over the padded
+        # tail blocks) keeps its 64-byte placement
+        L += [".p2align 6", "s_nop 0", "s_nop 0"]
     return "\n".join('    "{}\\n"'.format(l.replace("\\", "\\\\")) for l in L)
 
 
 def rounds_loop_text() -> str:
     """The split kernel's rounds wave over nsteps (>= 1) blocks in which every lane updates, starting
-    at ring buffer 0: one pipelined stream (gen_rounds_block) over buffers 0, 1, 2, 0, ... -- 80 rounds
-    from K+W in LDS, h += r, barrier per block.  One asm statement, so no compiler bookkeeping or
-    asm-boundary s_nop between blocks.  The reads issued ahead for the block after the last one are
-    drained before it returns."""
+    at ring buffer 0: split_rounds_block on buffers 0, 1, 2, 0, ... -- 80 rounds from K+W in LDS, h += r,
+    barrier per block.  One asm statement, so no compiler bookkeeping or asm-boundary s_nop between
+    blocks."""
     L = ["s_waitcnt lgkmcnt(0)", "s_mov_b32 %[cnt], %[nsteps]"]
-    if PIPELINED:
-        L.extend(_emit_lines(rounds_prologue(0)))
-    if SPLIT_MID:
-        L.extend(_emit_lines([("ds_read_b128", q, q * 1024) for q in range(10)]))
-    if SPLIT_PRE:
-        L.extend(_emit_lines([("ds_read_b128", q, q * 1024) for q in range(READ_AHEAD)]))
     if SPLIT_RALIGN is not None:
         L.append(".p2align 6")
         L.extend(["s_nop 0"] * (2 * int(SPLIT_RALIGN)))
     L.append("L_rloop_%=:")
     for k in range(LDS_BUFS):
-        if SPLIT_PRE:
-            if LOOP_ALIGN:
-                L.append(".p2align 3")
-            L.extend(_emit_lines(gen_split_pre_block(k * RING_BYTES, ((k + 1) % LDS_BUFS) * RING_BYTES)))
-        elif SPLIT_MID:
-            if LOOP_ALIGN:
-                L.append(".p2align 3")
-            L.extend(_emit_lines(gen_split_mid_block(k * RING_BYTES, ((k + 1) % LDS_BUFS) * RING_BYTES)))
-        elif PIPELINED:
-            L.extend(_emit_lines(gen_rounds_block(k * RING_BYTES, ((k + 1) % LDS_BUFS) * RING_BYTES)))
-        else:   # per-block stream: its 15 reads issued at the block's start
-            if LOOP_ALIGN:
-                L.append(".p2align 3")
-            body = _emit_lines(gen_lds(k * RING_BYTES, lead_wait=False))
-            if ROUNDS_X == "nowait":
-                body = [x for x in body if not x.startswith("s_waitcnt")]
-            L.extend(body)
-            L.extend(f"v_add_u32 %[h{i}], %[h{i}], %[r{i}]" for i in range(5))
-            L.extend(STAMP_SEQ if STAMP else ["s_barrier"])   # (every LDS read of the block has been waited)
+        if LOOP_ALIGN:
+            L.append(".p2align 3")
+        block = split_rounds_block(k)
+        assert block[-1] == ("s_barrier",)   # (every LDS read of the block has been waited for)
+        L.extend(_emit_lines(block[:-1]))
+        L.extend(STAMP_SEQ if STAMP else ["s_barrier"])
         L += ["s_sub_u32 %[cnt], %[cnt], 1", "s_cmp_eq_u32 %[cnt], 0",
               "s_cbranch_scc1 L_rdone_%=" if k < LDS_BUFS - 1 else "s_cbranch_scc0 L_rloop_%="]
     L += ["L_rdone_%=:", "s_waitcnt lgkmcnt(0)"]
@@ -929,16 +682,10 @@ def helper_loop_text(twin: bool = False) -> str:
         L.extend(_stamped("s_waitcnt vmcnt(4)", "svm") if STAMP >= 2 else ["s_waitcnt vmcnt(4)"])
         body = (gen_helper2 if twin else gen_helper)([f"v{pbase + i}" for i in range(16)], off_base)
         perms, rest = body[:16], body[16:]
-        # timing-only experiments (wrong digests): drop a class of the helper's work, keep its barriers
-        if HELPER_X == "novalu":
-            rest = [op for op in rest if op[0] == "ds_write_b128"]
-        elif HELPER_X == "nowrite":
-            rest = [op for op in rest if op[0] != "ds_write_b128"]
         if LOOP_ALIGN:
             L.append(".p2align 3")
         L.extend(_emit_lines(perms))
-        if HELPER_X != "noload":
-            loads(pbase)    # the perms have read pbase: refill it with the block 2 ahead
+        loads(pbase)    # the perms have read pbase: refill it with the block 2 ahead
         advance()
         if LOOP_ALIGN:
             L.append(".p2align 3")
@@ -1080,14 +827,13 @@ def emulate(ins, regs: dict, lds: dict | None = None, addr: int = 0, on_barrier=
 
 def emulate_twin(ins, regs2, lds, addrs, on_barrier=None, pend=None, drain: bool = True):
     """Run an instruction list on the two lanes of a TWIN pair in lockstep (regs2 / addrs per lane: lane b is
-    helper lane 2i + b, or role b of a role-split rounds wave).  v_add_u32_dpp with a lane number reads its first
-    source from that lane of the pair (op[4]).  With (ctrl, bank_mask) instead, it and v_mov_b32_dpp read their
-    first source through DPP -- ctrl "ror8" = from the partner, "own" = from the lane itself -- and write only the
-    lanes of bank_mask (ROLE0, ROLE1 or BOTH).  Every other instruction runs per lane through emulate(), with
-    each lane's in-flight reads carried across instructions."""
+    helper lane 2i + b, or role b of a rounds wave).  v_add_u32_dpp and v_mov_b32_dpp end with (ctrl, bank_mask):
+    they read their first source through DPP -- ctrl "ror8" = from the partner, "own" = from the lane itself -- and
+    write only the lanes of bank_mask (ROLE0, ROLE1 or BOTH).  Every other instruction runs per lane through
+    emulate(), with each lane's in-flight reads carried across instructions."""
     pend = pend if pend is not None else ([], [])
     for op in ins:
-        if op[0] in ("v_add_u32_dpp", "v_mov_b32_dpp") and isinstance(op[-1], tuple):
+        if op[0] in ("v_add_u32_dpp", "v_mov_b32_dpp"):
             dst, src, (ctrl, bank) = op[1], op[2], op[-1]
             src1 = op[3] if op[0] == "v_add_u32_dpp" else None
             assert bank in (ROLE0, ROLE1, BOTH) and ctrl in ("ror8", "own"), op
@@ -1101,15 +847,6 @@ def emulate_twin(ins, regs2, lds, addrs, on_barrier=None, pend=None, drain: bool
                 vals[ln] = (regs2[frm][src] + (regs2[ln][src1] if src1 is not None else 0)) & M32
             for ln, val in vals.items():
                 regs2[ln][dst] = val
-        elif op[0] == "v_add_u32_dpp":
-            _, dst, src, src1, b = op
-            vals = []
-            for ln in range(2):
-                assert all(src not in rs for rs, _, _ in pend[b]), f"DPP read of {src} in flight"
-                assert all(src1 not in rs and dst not in rs for rs, _, _ in pend[ln]), "in-flight register"
-                vals.append((regs2[b][src] + regs2[ln][src1]) & M32)
-            for ln in range(2):
-                regs2[ln][dst] = vals[ln]
         elif op[0] == "s_barrier":
             if on_barrier is not None:
                 on_barrier({a for ln in range(2) for _, _, adrs in pend[ln] for a in adrs})
@@ -1156,38 +893,30 @@ def _check_block(block: bytes, h):
     lds = {}
     emulate(gen_helper(), regs, lds, 0)
     for t in range(80):
-        assert lds[1024 * (t // 4) + 4 * (t % 4)] == (ww[t] + (0 if K_IN_ROUNDS else K[t // 20])) & M32, \
-            "SHA1_HELPER mismatch"
+        assert lds[split_word_addr(t)] == (ww[t] + K[t // 20]) & M32, "SHA1_HELPER mismatch"
     # LDS rounds consume the helper's output
     regs = dict(base)
     emulate(gen_lds(), regs, lds, 0)
     got = [(h[i] + regs[f"r{i}"]) & M32 for i in range(5)]
     assert got == exp, "SHA1_LDS mismatch"
     # TWIN: the helper's twin layout for piece 33 (helper lane 33; rounds wave 1, lanes 2 and 3)
-    if not K_IN_ROUNDS:
-        hregs = []
-        for ln in range(2):
-            regs = {"sel": 0x00010203, "psel": (0x03020100, 0x07060504)[ln]}
-            regs.update({f"k{i}": K[i] for i in range(4)})
-            regs.update({f"raw{i}": int.from_bytes(block[4 * i:4 * i + 4], "little") for i in range(16)})
-            hregs.append(regs)
-        lds = {}
-        # piece 33: lanes 2 and 3 of wave 1 (helper wave 3 writes where rounds wave 1 reads)
-        emulate_twin(gen_helper2(), hregs, lds, [1024 + 2 * 16, 1024 + 3 * 16])
-        for t in range(80):
-            a = 1024 + (t // 8) * TWIN_READ_BYTES + (2 + t % 2) * 16 + 4 * ((t % 8) // 2)
-            assert lds[a] == (ww[t] + K[t // 20]) & M32, "SHA1_HELPER2 mismatch"
-        regs2 = [dict(base), dict(base)]
-        emulate_twin(gen_twin(0), regs2, lds, [1024 + 2 * 16, 1024 + 3 * 16])
-        for ln in range(2):
-            got = [(h[i] + regs2[ln][f"r{i}"]) & M32 for i in range(5)]
-            assert got == exp, f"SHA1_TWIN mismatch (lane {ln})"
-        # role-split rounds: roles 0 and 1 of that piece read helper lanes 2 and 3's words
-        regs2 = [dict(base), dict(base)]
-        emulate_twin(gen_roles(0), regs2, lds, [1024 + 2 * 16, 1024 + 3 * 16])
-        for ln in range(2):
-            got = [(h[i] + regs2[ln][f"r{i}"]) & M32 for i in range(5)]
-            assert got == exp, f"SHA1_ROLES mismatch (role {ln})"
+    hregs = []
+    for ln in range(2):
+        regs = {"sel": 0x00010203, "psel": (0x03020100, 0x07060504)[ln]}
+        regs.update({f"k{i}": K[i] for i in range(4)})
+        regs.update({f"raw{i}": int.from_bytes(block[4 * i:4 * i + 4], "little") for i in range(16)})
+        hregs.append(regs)
+    lds = {}
+    # piece 33: lanes 2 and 3 of wave 1 (helper wave 3 writes where rounds wave 1 reads)
+    emulate_twin(gen_helper2(), hregs, lds, [1024 + 2 * 16, 1024 + 3 * 16])
+    for t in range(80):
+        assert lds[1024 + 2 * 16 + twin_word_addr(t)] == (ww[t] + K[t // 20]) & M32, "SHA1_HELPER2 mismatch"
+    # the rounds: roles 0 and 1 of that piece read helper lanes 2 and 3's words
+    regs2 = [dict(base), dict(base)]
+    emulate_twin(gen_roles(0), regs2, lds, [1024 + 2 * 16, 1024 + 3 * 16])
+    for ln in range(2):
+        got = [(h[i] + regs2[ln][f"r{i}"]) & M32 for i in range(5)]
+        assert got == exp, f"SHA1_ROLES mismatch (role {ln})"
     return exp
 
 
@@ -1197,126 +926,71 @@ def _kw_words(block: bytes):
     ww = list(struct.unpack(">16I", block)) + [0] * 64
     for t in range(16, 80):
         ww[t] = rotl(ww[t - 3] ^ ww[t - 8] ^ ww[t - 14] ^ ww[t - 16], 1)
-    return [(ww[t] + (0 if K_IN_ROUNDS else K[t // 20])) & M32 for t in range(80)]
+    return [(ww[t] + K[t // 20]) & M32 for t in range(80)]
 
 
-def check_rounds_stream(blocks, h):
-    """The pipelined rounds stream over consecutive blocks, run exactly as rounds_loop_text lays it out
-    (prologue, blocks on buffers 0, 1, 2, 0, ...), against the helper's protocol: blocks 0 and 1 are in
-    LDS at the start; at the barrier that ends block k (B_{k+1}) block k+3's buffer is poisoned (the real
-    helper may be writing it from then on) and block k+2 is written (the latest moment the protocol
-    allows).  A read of a block too early, or of a buffer after it was handed back, returns wrong words."""
-    lds = {}
+def split_word_addr(t: int) -> int:
+    """Where the split helper's lane 0 writes K+W[t] of a block, from its buffer's base ([t/4][lane][4 words])."""
+    return 1024 * (t // 4) + 4 * (t % 4)
 
-    def put(m, words, in_flight=frozenset()):
-        base = (m % LDS_BUFS) * RING_BYTES
+
+def twin_word_addr(t: int) -> int:
+    """The same for the lane pair 0, 1 of the twin layout ([k][wave][lane][4 words], lane t%2 owns word t)."""
+    return (t // 8) * TWIN_READ_BYTES + (t % 2) * 16 + 4 * ((t % 8) // 2)
+
+
+class HelperProtocol:
+    """The helper wave as a rounds wave may rely on it, and no kinder.  Blocks 0 and 1 are in LDS at the start.  At
+    the barrier that ends block k, block k+3's buffer is poisoned (it is handed back: the real helper may be
+    writing it from then on) and block k+2 is written (the latest moment the protocol allows).  A read of a block
+    too early, or of a buffer after it was handed back, returns wrong words, and a write to an address whose read
+    is still in flight fails.  word_addr(t) places K+W[t] in a buffer: the layout under test."""
+
+    def __init__(self, blocks, word_addr):
+        self.lds, self.word_addr, self.ended = {}, word_addr, 0
+        self.kws = [_kw_words(b) for b in blocks]
+        for m in range(min(2, len(blocks))):
+            self.put(m, self.kws[m])
+
+    def put(self, block, words, in_flight=frozenset()):
+        base = (block % LDS_BUFS) * RING_BYTES
         for t in range(80):
-            a = base + 1024 * (t // 4) + 4 * (t % 4)
+            a = base + self.word_addr(t)
             assert a not in in_flight, f"LDS {a} rewritten while a ds_read of it is in flight"
-            lds[a] = words[t]
+            self.lds[a] = words[t]
 
-    kws = [_kw_words(b) for b in blocks]
-    put(0, kws[0])
-    if len(blocks) > 1:
-        put(1, kws[1])
-    state = {"k": 0}
+    def on_barrier(self, in_flight):
+        k = self.ended               # the block that just ended
+        self.ended = k + 1
+        self.put(k + 3, [0xDEADBEEF ^ t for t in range(80)], in_flight)   # handed back to the helper
+        if k + 2 < len(self.kws):
+            self.put(k + 2, self.kws[k + 2], in_flight)
 
-    def on_barrier(in_flight):
-        k = state["k"]               # the block that just ended
-        state["k"] = k + 1
-        put(k + 3, [0xDEADBEEF ^ t for t in range(80)], in_flight)   # handed back to the helper
-        if k + 2 < len(blocks):
-            put(k + 2, kws[k + 2], in_flight)
 
+def split_rounds_stream(nsteps: int):
+    """The instructions rounds_loop_text executes for nsteps blocks, in order (without its scalar control flow)."""
+    return [op for k in range(nsteps) for op in split_rounds_block(k)] + [("s_waitcnt_lgkm", 0)]
+
+
+def check_split_stream(blocks, h, ins=None):
+    """The split kernel's rounds loop over consecutive blocks (split_rounds_stream, or the stream `ins` given in
+    its place) for lane 0, against the helper protocol; returns the chaining value."""
+    helper = HelperProtocol(blocks, split_word_addr)
     regs = {f"h{i}": h[i] for i in range(5)}
-    ins = list(rounds_prologue(0))
-    for k in range(len(blocks)):
-        ins += gen_rounds_block((k % LDS_BUFS) * RING_BYTES, ((k + 1) % LDS_BUFS) * RING_BYTES)
-    ins.append(("s_waitcnt_lgkm", 0))
-    emulate(ins, regs, lds, 0, on_barrier=on_barrier)
+    emulate(split_rounds_stream(len(blocks)) if ins is None else ins, regs, helper.lds, 0, on_barrier=helper.on_barrier)
     return [regs[f"h{i}"] for i in range(5)]
 
 
-def check_split_mid_stream(blocks, h, pre: bool = False):
-    """The split rounds loop with SPLIT_MID (gen_split_mid_block) or SPLIT_PRE (gen_split_pre_block, pre=True),
-    checked like check_rounds_stream."""
-    lds = {}
-
-    def put(m, words, in_flight=frozenset()):
-        base = (m % LDS_BUFS) * RING_BYTES
-        for t in range(80):
-            a = base + 1024 * (t // 4) + 4 * (t % 4)
-            assert a not in in_flight, f"LDS {a} rewritten while a ds_read of it is in flight"
-            lds[a] = words[t]
-
-    kws = [_kw_words(b) for b in blocks]
-    put(0, kws[0])
-    if len(blocks) > 1:
-        put(1, kws[1])
-    state = {"k": 0}
-
-    def on_barrier(in_flight):
-        k = state["k"]
-        state["k"] = k + 1
-        put(k + 3, [0xDEADBEEF ^ t for t in range(80)], in_flight)
-        if k + 2 < len(blocks):
-            put(k + 2, kws[k + 2], in_flight)
-
-    regs = {f"h{i}": h[i] for i in range(5)}
-    ins = [("ds_read_b128", q, q * 1024) for q in range(READ_AHEAD if pre else 10)]
-    for k in range(len(blocks)):
-        ins += (gen_split_pre_block if pre else gen_split_mid_block)((k % LDS_BUFS) * RING_BYTES,
-                                                                     ((k + 1) % LDS_BUFS) * RING_BYTES)
-    ins.append(("s_waitcnt_lgkm", 0))
-    emulate(ins, regs, lds, 0, on_barrier=on_barrier)
-    return [regs[f"h{i}"] for i in range(5)]
-
-
-def check_twin_stream(blocks, h, roles: bool = False):
-    """The TWIN rounds loop over consecutive blocks as twin_rounds_loop_text lays it out (roles: the role-split loop,
-    roles_rounds_stream, with the DPP-distance rule checked over the whole stream), for the lane pair
-    of piece 0, against the helper protocol (as check_rounds_stream): at the barrier ending block k, block
-    k+3's buffer is poisoned and block k+2 written; a read in flight there must not be rewritten."""
-    lds = {}
-
-    def put(m, words, in_flight=frozenset()):
-        base = (m % LDS_BUFS) * RING_BYTES
-        for t in range(80):
-            a = base + (t // 8) * TWIN_READ_BYTES + (t % 2) * 16 + 4 * ((t % 8) // 2)
-            assert a not in in_flight, f"LDS {a} rewritten while a ds_read of it is in flight"
-            lds[a] = words[t]
-
-    kws = [_kw_words(b) for b in blocks]
-    put(0, kws[0])
-    if len(blocks) > 1:
-        put(1, kws[1])
-    state = {"k": 0}
-
-    def on_barrier(in_flight):
-        k = state["k"]
-        state["k"] = k + 1
-        put(k + 3, [0xDEADBEEF ^ t for t in range(80)], in_flight)
-        if k + 2 < len(blocks):
-            put(k + 2, kws[k + 2], in_flight)
-
+def check_twin_stream(blocks, h):
+    """The TWIN rounds loop over consecutive blocks as roles_rounds_loop_text lays it out (roles_rounds_stream, with
+    the DPP-distance rule checked over the whole stream), for the lane pair of piece 0, against the helper
+    protocol; returns the chaining value."""
+    helper = HelperProtocol(blocks, twin_word_addr)
     regs2 = [{f"h{i}": h[i] for i in range(5)} for _ in range(2)]
-    if roles:
-        ins = roles_rounds_stream(len(blocks))
-        check_dpp_distance(ins)
-        emulate_twin(ins, regs2, lds, [0, 16], on_barrier=on_barrier)
-        assert all(regs2[0][f"h{i}"] == regs2[1][f"h{i}"] for i in range(5)), "twin roles disagree"
-        return [regs2[0][f"h{i}"] for i in range(5)]
-    walk = twin_trips_walk(len(blocks))   # the blocks in the order the loop text's control flow runs them
-    assert [buf for _, buf, _ in walk] == [k % LDS_BUFS for k in range(len(blocks))]
-    ins = [("ds_read_b128_abs", TWIN_SET_QUADS * walk[0][0] + q, q * TWIN_READ_BYTES) for q in range(TWIN_SET_QUADS)]
-    for k in range(len(blocks)):
-        s, _, nxt = walk[k]
-        assert k == 0 or (walk[k - 1][0] != s and walk[k - 1][2] == walk[k][1])   # the reads the block before issued
-        ins += gen_twin_trip_block(s, nxt * RING_BYTES)
-        ins += [("v_add_u32", f"h{i}", f"h{i}", f"r{i}") for i in range(5)] + [("s_barrier",)]
-    ins.append(("s_waitcnt_lgkm", 0))
-    emulate_twin(ins, regs2, lds, [0, 16], on_barrier=on_barrier)
-    assert all(regs2[0][f"h{i}"] == regs2[1][f"h{i}"] for i in range(5)), "twin lanes disagree"
+    ins = roles_rounds_stream(len(blocks))
+    check_dpp_distance(ins)
+    emulate_twin(ins, regs2, helper.lds, [0, 16], on_barrier=helper.on_barrier)
+    assert all(regs2[0][f"h{i}"] == regs2[1][f"h{i}"] for i in range(5)), "twin roles disagree"
     return [regs2[0][f"h{i}"] for i in range(5)]
 
 
@@ -1332,36 +1006,18 @@ def self_check():
         for i in range(0, len(padded), 64):
             h = _check_block(padded[i:i + 64], h)
         assert struct.pack(">5I", *h) == hashlib.sha1(msg).digest(), n
-    # the split kernel's pipelined rounds stream over 1 .. 7 consecutive blocks (every buffer phase)
-    for n in ([0, 55, 64, 119, 200, 310, 400] if PIPELINED else []):
+    # the split and the TWIN rounds loops over 1 .. 7, 8, 13 and 15 consecutive blocks: every buffer phase, and both
+    # parities of the block count go round the twin loop's six-block body
+    # (the protocol model is the helper two blocks ahead, which takes three buffers)
+    for n in ([0, 55, 64, 119, 200, 310, 400, 500, 800, 900] if LDS_BUFS == 3 else []):
         msg = bytes(rng.randrange(256) for _ in range(n))
         padded = msg + b"\x80" + b"\0" * ((55 - n) % 64) + struct.pack(">Q", 8 * n)
+        blocks = [padded[i:i + 64] for i in range(0, len(padded), 64)]
         h0 = [0x67452301, 0xEFCDAB89, 0x98BADCFE, 0x10325476, 0xC3D2E1F0]
-        h = check_rounds_stream([padded[i:i + 64] for i in range(0, len(padded), 64)], h0)
-        assert struct.pack(">5I", *h) == hashlib.sha1(msg).digest(), ("stream", n)
-    # the split rounds loop with the next block's reads issued mid-block, 1 .. 7 blocks
-    for n in ([0, 55, 64, 119, 200, 310, 400] if SPLIT_MID else []):
-        msg = bytes(rng.randrange(256) for _ in range(n))
-        padded = msg + b"\x80" + b"\0" * ((55 - n) % 64) + struct.pack(">Q", 8 * n)
-        h0 = [0x67452301, 0xEFCDAB89, 0x98BADCFE, 0x10325476, 0xC3D2E1F0]
-        h = check_split_mid_stream([padded[i:i + 64] for i in range(0, len(padded), 64)], h0)
-        assert struct.pack(">5I", *h) == hashlib.sha1(msg).digest(), ("split mid stream", n)
-    for n in ([0, 55, 64, 119, 200, 310, 400] if SPLIT_PRE else []):
-        msg = bytes(rng.randrange(256) for _ in range(n))
-        padded = msg + b"\x80" + b"\0" * ((55 - n) % 64) + struct.pack(">Q", 8 * n)
-        h0 = [0x67452301, 0xEFCDAB89, 0x98BADCFE, 0x10325476, 0xC3D2E1F0]
-        h = check_split_mid_stream([padded[i:i + 64] for i in range(0, len(padded), 64)], h0, pre=True)
-        assert struct.pack(">5I", *h) == hashlib.sha1(msg).digest(), ("split pre stream", n)
-    # the TWIN rounds loop over 1 .. 7, 8, 13 and 15 consecutive blocks: every buffer phase, and both parities of
-    # the block count go round the six-block loop body
-    for n in ([0, 55, 64, 119, 200, 310, 400, 500, 800, 900] if LDS_BUFS == 3 and not K_IN_ROUNDS else []):
-        msg = bytes(rng.randrange(256) for _ in range(n))
-        padded = msg + b"\x80" + b"\0" * ((55 - n) % 64) + struct.pack(">Q", 8 * n)
-        h0 = [0x67452301, 0xEFCDAB89, 0x98BADCFE, 0x10325476, 0xC3D2E1F0]
-        h = check_twin_stream([padded[i:i + 64] for i in range(0, len(padded), 64)], h0)
+        h = check_split_stream(blocks, h0)
+        assert struct.pack(">5I", *h) == hashlib.sha1(msg).digest(), ("split stream", n)
+        h = check_twin_stream(blocks, h0)
         assert struct.pack(">5I", *h) == hashlib.sha1(msg).digest(), ("twin stream", n)
-        h = check_twin_stream([padded[i:i + 64] for i in range(0, len(padded), 64)], h0, roles=True)
-        assert struct.pack(">5I", *h) == hashlib.sha1(msg).digest(), ("role-split twin stream", n)
     return True
 
 
@@ -1406,7 +1062,7 @@ def _emit_lines(ins, full: bool = False):
             lines.append("s_barrier")
         elif o == "s_nop":
             lines.append("s_nop 0")
-        elif o in ("v_add_u32_dpp", "v_mov_b32_dpp") and isinstance(op[-1], tuple):
+        elif o in ("v_add_u32_dpp", "v_mov_b32_dpp"):
             ctrl, bank = op[-1]
             lines.append(f"{o} " + ", ".join(_opnd(x, full) for x in op[1:-1]) + " "
                          + {"ror8": "row_ror:8", "own": "quad_perm:[0,1,2,3]"}[ctrl] + f" row_mask:0xf bank_mask:0x{bank:x}")
@@ -1414,10 +1070,6 @@ def _emit_lines(ins, full: bool = False):
             lines.append(f"v_mov_b32_e64 {_opnd(op[1], full)}, {_opnd(op[2], full)}")   # (8 bytes, as every VALU here)
         elif o == "s_text":
             lines.append(op[1])
-        elif o == "v_add_u32_dpp":
-            b = op[4]
-            lines.append(f"v_add_u32_dpp {_opnd(op[1], full)}, {_opnd(op[2], full)}, {_opnd(op[3], full)} "
-                         f"quad_perm:[{b},{b},{2 + b},{2 + b}] row_mask:0xf bank_mask:0xf")
         else:
             lines.append(f"{o} " + ", ".join(_opnd(x, full) for x in op[1:]))
     return lines
@@ -1440,8 +1092,6 @@ HEADER = """// GENERATED by tools/gen_sha1_asm.py -- do not edit.  Regenerate wi
 // (its first HELPER_AHEAD - 1 writes are not followed by a barrier; it ends with as many extra barriers)
 #define TV_SHA1_LDS_BUFS {lds_bufs}
 #define TV_SHA1_HELPER_AHEAD {helper_ahead}
-// 1: the split helper writes W and the rounds wave adds K (v_add3 with an SGPR); 0: the helper writes K+W
-#define TV_SHA1_K_IN_ROUNDS {k_in_rounds}
 
 // One SHA-1 compression, schedule in-asm.  w[16] holds the big-endian message words and is
 // clobbered.  On return r = working state after round 79; caller does h += r.
@@ -1526,26 +1176,31 @@ __device__ __forceinline__ void tv_sha1_schedule_lds(const uint32_t raw[16], uin
 
 
 TWIN_HEADER = """
-// ---- TWIN kernel: two lanes per piece in the rounds and helper waves (tools/gen_sha1_asm.py gen_twin,
-// gen_helper2).  K+W buffer layout [k][wave][lane][4 words]; a lane's `addr` is ring + (wave & 1)*1024 + lane*16,
-// its `psel` 0x03020100 (even lane) / 0x07060504 (odd lane).
+// ---- TWIN kernel: two lanes per piece in the rounds and helper waves (tools/gen_sha1_asm.py gen_helper2,
+// gen_roles, gen_roles_trip_block).  K+W buffer layout [k][wave][lane][4 words]; a helper lane's `addr` is
+// ring + (wave & 1)*1024 + lane*16, its `psel` 0x03020100 (even lane) / 0x07060504 (odd lane).
+// Rounds: lane 16r+p (p < 8) of a rounds wave is role 0 of the wave's piece 8r+p, lane 16r+8+p its role 1, and
+// role b's `addr` is that of helper lane 2(8r+p)+b: ring + (wave & 1)*1024 + (2(8r+p)+b)*16.  Both rounds
+// functions take and return the plain chaining value / state in BOTH lanes of a pair, and need every lane of the
+// wave active (the roles exchange values through DPP).
 
 // One block of 80 rounds for a lane pair, with its own 10 LDS reads (waits for them before returning).
-__device__ __forceinline__ void tv_sha1_twin_lds(const uint32_t h[5], uint32_t r[5], uint32_t addr) {{
+__device__ __forceinline__ void tv_sha1_roles_lds(const uint32_t h[5], uint32_t r[5], uint32_t addr) {{
     uint32_t t0, t1;
     asm volatile(
-{twin_lds}
+{roles_lds}
     : [r0] "=&v"(r[0]), [r1] "=&v"(r[1]), [r2] "=&v"(r[2]), [r3] "=&v"(r[3]), [r4] "=&v"(r[4]),
       [t0] "=&v"(t0), [t1] "=&v"(t1)
     : [h0] "v"(h[0]), [h1] "v"(h[1]), [h2] "v"(h[2]), [h3] "v"(h[3]), [h4] "v"(h[4]), [addr] "v"(addr){addr2}
     : {ring_clobbers}, "memory");
 }}
 
-// The TWIN rounds wave over nsteps (>= 1) blocks from ring buffer 0 in which every lane updates.
-__device__ __forceinline__ void tv_sha1_twin_rounds_loop(uint32_t h[5], uint32_t addr, uint32_t nsteps) {{
+// The TWIN rounds wave over nsteps (>= 1) blocks from ring buffer 0 in which every lane updates.  The block is
+// written once, as an assembler macro of its K+W registers, the registers its reads fill and their offset.
+__device__ __forceinline__ void tv_sha1_roles_rounds_loop(uint32_t h[5], uint32_t addr, uint32_t nsteps) {{
     uint32_t r[5], t0, t1, cnt;
     asm volatile(
-{twin_rounds_loop}
+{roles_rounds_loop}
     : [h0] "+v"(h[0]), [h1] "+v"(h[1]), [h2] "+v"(h[2]), [h3] "+v"(h[3]), [h4] "+v"(h[4]),
       [r0] "=&v"(r[0]), [r1] "=&v"(r[1]), [r2] "=&v"(r[2]), [r3] "=&v"(r[3]), [r4] "=&v"(r[4]),
       [t0] "=&v"(t0), [t1] "=&v"(t1), [cnt] "=&s"(cnt)
@@ -1583,55 +1238,6 @@ __device__ __forceinline__ void tv_sha1_twin_schedule_lds(const uint32_t raw[16]
 """
 
 
-ROLES_HEADER = """// GENERATED by tools/gen_sha1_asm.py -- do not edit.  Regenerate with:
-//   python3 tools/gen_sha1_asm.py
-// The instruction streams below are checked against hashlib by the generator's emulator before they are written.
-#pragma once
-#include <stdint.h>
-
-// ---- TWIN kernel, role-split rounds (tools/gen_sha1_asm.py gen_roles, gen_roles_trip_block): what the twin
-// kernel's rounds waves run.  (sha1_asm.h still carries tv_sha1_twin_lds and tv_sha1_twin_rounds_loop, the rounds
-// both lanes of a pair ran alike, for A/B builds; no kernel calls them.)  Lane 16r+p (p < 8) of a rounds wave is
-// role 0 of the wave's piece 8r+p, lane 16r+8+p its role 1, and role b's `addr` is that of helper lane 2(8r+p)+b:
-// ring + (wave & 1)*1024 + (2(8r+p)+b)*16.  Both functions take and return the plain chaining value / state in BOTH
-// lanes of a pair, and need every lane of the wave active (the roles exchange values through DPP).
-
-// One block of 80 rounds for a lane pair, with its own 10 LDS reads (waits for them before returning).
-__device__ __forceinline__ void tv_sha1_roles_lds(const uint32_t h[5], uint32_t r[5], uint32_t addr) {{
-    uint32_t t0, t1;
-    asm volatile(
-{roles_lds}
-    : [r0] "=&v"(r[0]), [r1] "=&v"(r[1]), [r2] "=&v"(r[2]), [r3] "=&v"(r[3]), [r4] "=&v"(r[4]),
-      [t0] "=&v"(t0), [t1] "=&v"(t1)
-    : [h0] "v"(h[0]), [h1] "v"(h[1]), [h2] "v"(h[2]), [h3] "v"(h[3]), [h4] "v"(h[4]), [addr] "v"(addr){addr2}
-    : {ring_clobbers}, "memory");
-}}
-
-// The TWIN rounds wave over nsteps (>= 1) blocks from ring buffer 0 in which every lane updates.  The block is
-// written once, as an assembler macro of its K+W registers, the registers its reads fill and their offset.
-__device__ __forceinline__ void tv_sha1_roles_rounds_loop(uint32_t h[5], uint32_t addr, uint32_t nsteps) {{
-    uint32_t r[5], t0, t1, cnt;
-    asm volatile(
-{roles_rounds_loop}
-    : [h0] "+v"(h[0]), [h1] "+v"(h[1]), [h2] "+v"(h[2]), [h3] "+v"(h[3]), [h4] "+v"(h[4]),
-      [r0] "=&v"(r[0]), [r1] "=&v"(r[1]), [r2] "=&v"(r[2]), [r3] "=&v"(r[3]), [r4] "=&v"(r[4]),
-      [t0] "=&v"(t0), [t1] "=&v"(t1), [cnt] "=&s"(cnt)
-    : [addr] "v"(addr){addr2}, [nsteps] "s"(nsteps)
-    : {twin_ring_clobbers}, "scc", "memory");
-}}
-"""
-
-
-def render_roles() -> str:
-    """sha1_roles_asm.h, written beside sha1_asm.h."""
-    ring = ", ".join(f'"v{RING_BASE + i}"' for i in range(4 * RING_QUADS))
-    twin_ring = ", ".join(f'"v{RING_BASE + i}"' for i in range(4 * max(RING_QUADS, 2 * TWIN_SET_QUADS)))
-    addr2 = ', [addr2] "v"(addr + 65536u)' if LDS_BUFS * RING_BYTES > 65536 else ""
-    return ROLES_HEADER.format(roles_lds='    ".p2align 3\\n"\n' + emit(gen_roles(0), False),
-                               roles_rounds_loop=roles_rounds_loop_text(), ring_clobbers=ring,
-                               twin_ring_clobbers=twin_ring, addr2=addr2)
-
-
 def render() -> str:
     ring = ", ".join(f'"v{RING_BASE + i}"' for i in range(4 * RING_QUADS))
     hregs = list(range(HW_BASE, HW_BASE + 16)) + [HT, HT2] + list(range(HOUT_BASE, HOUT_BASE + 4 * HOUT_QUADS))
@@ -1644,31 +1250,29 @@ def render() -> str:
     h2loop = ", ".join(f'"v{i}"' for i in h2regs + list(range(P0_BASE, VL + 2)))
     # a K+W ring past 64 KiB (LDS_BUFS >= 4) addresses its upper buffers from a second register: DS offsets are 16-bit
     addr2 = ', [addr2] "v"(addr + 65536u)' if LDS_BUFS * RING_BYTES > 65536 else ""
-    return HEADER.format(addr2=addr2, k_in_rounds=int(K_IN_ROUNDS), ring_base=RING_BASE, ring_quads=RING_QUADS, lds_bufs=LDS_BUFS, helper_ahead=HELPER_AHEAD,
+    return HEADER.format(addr2=addr2, ring_base=RING_BASE, ring_quads=RING_QUADS, lds_bufs=LDS_BUFS, helper_ahead=HELPER_AHEAD,
                          full=('    ".p2align 3\\n"\n' if ALIGN_FULL else "") + emit(gen_full(), True),
                          lds=emit(gen_lds(), False), helper=emit(gen_helper(), False),
                          helper_loop=helper_loop_text(), rounds_loop=rounds_loop_text(),
                          ring_clobbers=ring, helper_clobbers=helper,
-                         loop_clobbers=loop) + ("" if K_IN_ROUNDS else TWIN_HEADER.format(
-                             twin_lds='    ".p2align 3\\n"\n' + emit(gen_twin(0), False),
-                             twin_rounds_loop=twin_rounds_loop_text(),
+                         loop_clobbers=loop) + TWIN_HEADER.format(
+                             roles_lds='    ".p2align 3\\n"\n' + emit(gen_roles(0), False),
+                             roles_rounds_loop=roles_rounds_loop_text(),
                              twin_helper_loop=helper_loop_text(twin=True),
                              twin_helper=emit(gen_helper2(), False),
-                             ring_clobbers=ring, twin_ring_clobbers=twin_ring, twin_helper_clobbers=h2, twin_loop_clobbers=h2loop, addr2=addr2))
+                             ring_clobbers=ring, twin_ring_clobbers=twin_ring, twin_helper_clobbers=h2, twin_loop_clobbers=h2loop, addr2=addr2)
 
 
 STAMP_FNS = (("tv_sha1_rounds_loop", "uint32_t nsteps,\n", '[cnt] "=&s"(cnt)\n'),
              ("tv_sha1_helper_loop", "uint32_t nraw, uint32_t addr,\n", '[inc] "=&s"(inc)\n'),
-             ("tv_sha1_twin_rounds_loop", "uint32_t nsteps) {\n", '[cnt] "=&s"(cnt)\n'),
+             ("tv_sha1_roles_rounds_loop", "uint32_t nsteps) {\n", '[cnt] "=&s"(cnt)\n'),
              ("tv_sha1_twin_helper_loop", "uint32_t addr, uint32_t psel,\n", '[inc] "=&s"(inc)\n'))
-STAMP_ROLES_FNS = (("tv_sha1_roles_rounds_loop", "uint32_t nsteps) {\n", '[cnt] "=&s"(cnt)\n'),)
 
 
-def _stamp_patch(txt: str, fns=STAMP_FNS) -> str:
-    """STAMP builds: give tv_sha1_rounds_loop and tv_sha1_helper_loop an accumulator argument `sbar` (cycles at
-    the in-loop barriers) and the SGPRs the stamps use as clobbers."""
-    assert not (PIPELINED or SPLIT_MID or SPLIT_PRE), "stamps are for the shipped per-block split rounds loop"
-    for fn, sig_old, out_old in fns:
+def _stamp_patch(txt: str) -> str:
+    """STAMP builds: give the four loops an accumulator argument `sbar` (cycles at the in-loop barriers; the helper
+    loops at level 2 also `svm` and `slg`) and the SGPRs the stamps use as clobbers."""
+    for fn, sig_old, out_old in STAMP_FNS:
         extra = fn in ("tv_sha1_helper_loop", "tv_sha1_twin_helper_loop") and STAMP >= 2
         i = txt.index(f"void {fn}(")
         j = txt.index("\n}\n", i)
@@ -1684,7 +1288,8 @@ def _stamp_patch(txt: str, fns=STAMP_FNS) -> str:
             assert seg.count(old) == 1, (fn, old)
             seg = seg.replace(old, new)
         txt = txt[:i] + seg + txt[j:]
-    return txt.replace("#define TV_SHA1_K_IN_ROUNDS", f"#define TV_SHA1_STAMP {STAMP}\n#define TV_SHA1_K_IN_ROUNDS", 1)
+    assert txt.count("#define TV_SHA1_RING_BASE") == 1
+    return txt.replace("#define TV_SHA1_RING_BASE", f"#define TV_SHA1_STAMP {STAMP}\n#define TV_SHA1_RING_BASE")
 
 
 def main():
@@ -1701,9 +1306,6 @@ def main():
         txt = _stamp_patch(txt)
     with open(a.out, "w") as f:
         f.write(txt)
-    if not K_IN_ROUNDS:
-        with open(os.path.join(os.path.dirname(os.path.abspath(a.out)), "sha1_roles_asm.h"), "w") as f:
-            f.write(_stamp_patch(render_roles(), STAMP_ROLES_FNS) if STAMP else render_roles())
     print(f"wrote {a.out}: FULL {len(gen_full())} instr, LDS {len(gen_lds())} instr, "
           f"HELPER {len(gen_helper())} instr")
 

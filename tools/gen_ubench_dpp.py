@@ -17,7 +17,7 @@ Variants (one lone wave per CU, NBLK blocks per loop, s_memtime cycles per block
   d10_*     10 reads at the block start, DPP adds; waits: w10 = one per read, w5 = one per 2 reads,
             w5n = w5 + s_nop 0 after each wait (realign), w5d = each wait doubled, w2 = waits at reads 0 and 5
   trips     the two-block-trip loop body on two register sets with the five-instruction round both lanes ran
-            alike (405 VALU per block: gen_twin_trip_block)
+            alike (405 VALU per block: alike_block below)
   roles     the same trips with the role-split rounds the generator ships (gen_roles_trip_block: 9 instructions
             per two rounds through row_ror:8 and bank-masked DPP, 367 VALU per block)
 Build: python3 tools/gen_ubench_dpp.py && hipcc --offload-arch=gfx950 -O3 tools/ubench_dpp.hip -o tools/ubench_dpp
@@ -108,11 +108,35 @@ def trip_reads(s: int) -> list[str]:
                                                  for q in range(g.TWIN_SET_QUADS)])]
 
 
+def alike_block(s: int) -> list[str]:
+    """One block of the rounds both lanes of a pair ran alike, on register set s (the twin kernel's rounds before the
+    roles; the generator no longer writes them): one wait, then five 8-byte instructions per round, round t's K+W
+    word taken from lane t%2 of the pair through DPP; after round TWIN_TRIP_AT the next block's ten reads go out
+    into the other set."""
+    out = ["s_waitcnt lgkmcnt(0)"]
+    R = g.Regs()
+    for t in range(80):
+        b = t % 2
+        A, B, C, D, E = g.roles(t)
+        e_src = R.rd(E)
+        out.append(f"v_add_u32_dpp %[{R.wr(E)}], {g.twin_set_reg(s, t // 8, (t % 8) // 2)}, %[{e_src}] "
+                   f"quad_perm:[{b},{b},{2 + b},{2 + b}] row_mask:0xf bank_mask:0xf")
+        out.append(f"v_alignbit_b32 %[t0], %[{R.rd(A)}], %[{R.rd(A)}], 27")
+        op = g._fop(t, "t1", R.rd(B), R.rd(C), R.rd(D))
+        out.append(f"v_bitop3_b32 %[t1], %[{op[2]}], %[{op[3]}], %[{op[4]}] bitop3:0x{op[5]:02x}")
+        b_src = R.rd(B)
+        out.append(f"v_alignbit_b32 %[{R.wr(B)}], %[{b_src}], %[{b_src}], 2")
+        out.append(f"v_add3_u32 %[{R.rd(E)}], %[{R.rd(E)}], %[t0], %[t1]")
+        if t == g.TWIN_TRIP_AT:
+            out += trip_reads(1 - s)
+    return [trip_phys(l) for l in out]
+
+
 def trips_alike() -> list[str]:
-    """Two blocks of the rounds both lanes of a pair run alike (gen_twin_trip_block) with their feed-forward."""
+    """Two blocks of the rounds both lanes of a pair run alike with their feed-forward."""
     out = []
     for s in range(2):
-        out += [trip_phys(l) for l in g._emit_lines(g.gen_twin_trip_block(s, 0))]
+        out += alike_block(s)
         out.append(trip_phys("v_add_u32_e64 %[h0], %[h0], %[r0]"))
         out += [trip_phys(f"v_add_u32 %[h{i}], %[h{i}], %[r{i}]") for i in range(1, 5)] + ["s_barrier"]
     return out

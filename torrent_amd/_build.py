@@ -2,8 +2,8 @@
 
     python -m torrent_amd._build            # regenerate the asm header, compile the .so
 
-The generated headers torrent_amd/csrc/sha1_asm.h and sha1_roles_asm.h are produced by tools/gen_sha1_asm.py, which
-first checks its instruction streams against hashlib in an emulator.
+The generated header torrent_amd/csrc/sha1_asm.h is produced by tools/gen_sha1_asm.py, which first checks its
+instruction streams against hashlib in an emulator.
 """
 from __future__ import annotations
 
@@ -83,7 +83,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         subprocess.check_call([sys.executable, gen, "--out", header])
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     host_srcs = [os.path.join(CSRC, s) for s in HOST_SOURCES]
-    deps = srcs + host_srcs + [header, os.path.join(CSRC, "sha1_roles_asm.h"), os.path.join(CSRC, "tv_internal.h"), os.path.join(CSRC, "tv_host.h"),
+    deps = srcs + host_srcs + [header, os.path.join(CSRC, "tv_internal.h"), os.path.join(CSRC, "tv_host.h"),
                                os.path.join(CSRC, "tv_ctx.h"), os.path.join(CSRC, "tv_options_internal.h"), EXPORTS,
                                os.path.join(CSRC, "tv_plan.h"), os.path.join(CSRC, "tv_block.h"),
                                os.path.join(CSRC, "tv_sha256.h"), os.path.join(CSRC, "tv_fileio.h"),

@@ -25,7 +25,7 @@
 // What the kernels share is written once: resolve_group() turns a group of a launch into each lane's piece, block
 // range and bytes (resident, list and batch mode); helper_wave() / rounds_wave() are the two wave bodies of split and twin,
 // with the barrier protocol stated above them; finish() / finish_list() write the results.  The generated blocks
-// and loops are in sha1_asm.h and sha1_roles_asm.h (tools/gen_sha1_asm.py).
+// and loops are in sha1_asm.h (tools/gen_sha1_asm.py).
 //
 // HBM layout: resident piece j (shard-local) starts at payload + j*stride, stride = L + pad
 // (pad breaks the power-of-two stride that would put all 64 lanes of a wave on one channel).
@@ -35,7 +35,6 @@
 #include <type_traits>
 
 #include "sha1_asm.h"
-#include "sha1_roles_asm.h"
 #include "tv_block.h"
 #include "tv_internal.h"
 
@@ -367,9 +366,9 @@ __global__ __launch_bounds__(256) void tv_lane_kernel(TvPieces p) {
 namespace {
 
 constexpr int kRingWords = 80 * 64;  // one buffer: [20 quads][64 lanes][4 words]
-// K+W buffers per pair.  The helper runs TWO blocks ahead (block j lives in buffer j % 3), so the rounds
-// wave can keep its 15 LDS reads in flight across block boundaries (tools/gen_sha1_asm.py
-// gen_rounds_block) instead of restarting them, and an LDS latency, at every block.
+// K+W buffers per pair.  The helper runs TWO blocks ahead (block j lives in buffer j % 3), so a rounds wave
+// may read block j + 1 while it runs block j (the twin loop issues those reads mid-block), and the split helper
+// need not wait for a block's LDS writes before the next barrier (tools/gen_sha1_asm.py HELPER_WAIT).
 constexpr uint32_t kBufs = TV_SHA1_LDS_BUFS;
 constexpr uint32_t kAhead = TV_SHA1_HELPER_AHEAD;
 
