@@ -132,7 +132,11 @@ def write_readme(res: dict, folder: str) -> None:
         "library drawn from 256 KiB / 1 MiB / 4 MiB pieces, every torrent with a short last piece, whose batch "
         "bitfields are checked against the loop's |",
         "| `bench_ab.json` | `bench.py --gpus 1` on the parent commit and on this one, alternating, 5 runs each, in one "
-        "session: the resident single-torrent path |", "",
+        "session: the resident single-torrent path |",
+        "| `group_tests.md` | the tests of the batch launch's mixed-length groups (`tests/batch_groups.py`, "
+        "`tests/test_batch_groups_shapes.py`, `tests/test_gpu_batch_groups.py`): what they reach, their wall time, and "
+        "which tests two deliberate edits of the digest-update mask fail; hand-written, repeated at the end of this file |",
+        "",
         f"Build `{res['build']}`, {res['gib']} GiB per leg.", "",
         "| leg | kernel ms | expectation |", "|---|---|---|",
         f"| a: {16 * res['gib']} torrents, one batch launch ({res['a_batch']['workgroups']} workgroups) | {row('a_batch')} | "
@@ -157,6 +161,9 @@ def write_readme(res: dict, folder: str) -> None:
                   f"| parent `{ab['parent_build']}` | {', '.join(f'{v:.1f}' for v in p)} | {statistics.median(p):.1f} | {min(p):.1f} |",
                   f"| this commit `{ab['branch_build']}` | {', '.join(f'{v:.1f}' for v in b)} | {statistics.median(b):.1f} | {min(b):.1f} |",
                   "", f"This commit's median is not below the parent's slowest run: {met(ok)}.", ""]
+    notes_path = os.path.join(folder, "group_tests.md")    # hand-written: the tests of the mixed-length groups
+    if os.path.exists(notes_path):
+        lines += open(notes_path).read().rstrip("\n").split("\n") + [""]
     with open(os.path.join(folder, "README.md"), "w") as f:
         f.write("\n".join(lines))
 
